@@ -18,8 +18,22 @@ pixel, samples in sequence (the per-pixel chain bounds strong scaling); "row" =
 the reference's own seeding, unmodified (main.cpp:204: one stream threaded
 through a row's pixels and samples; byte-identical to the reference binary),
 run by the speculative row engine.  All three are byte-exact against their
-oracle legs (tests/); the line also reports the other modes' throughput
-(seed_modes), timed the same way after the main run.
+oracle legs (tests/); with --full the line also reports the other modes'
+throughput (seed_modes), timed the same way after the main run.
+
+A plain run sets up, warms up, times the K steps, writes its outputs if
+--dump-outputs is given, and prints the line; everything else the bench
+measures (the other seeding modes, the index tie rule, the roofline's
+instrumented run, the CPU baseline and its parity sample, the host paths) runs
+only with --full, and its keys are null (seed_modes: empty) without it.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step
+returned as float32 / float64 .npy files: image.npy (the assembled H x W x 4
+RGBA frame, values 0..255, row 0 the lowest rendered row) and rays.npy (the
+step's ray count over all ranks).  A frame above 64 MB as float32 (sponza4k)
+is written as a fixed, seeded sample of its rows, their indices in
+image_rows.npy.  Scene, camera and seeds are deterministic, so two runs with
+the same arguments render the same inputs.
 
 Launch: `python bench.py --gpus N` with N > 1 and no launcher around it (no
 WORLD_SIZE in the environment) starts N ranks itself -- this process runs
@@ -28,7 +42,7 @@ with its code -- after checking that N GPUs are visible (nccl; the gloo
 rehearsal may put several ranks on one GPU).  Under a launcher, WORLD_SIZE must
 equal --gpus.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+Rank 0 prints ONE JSON line.  Besides the contract keys it carries, with --full,
   roofline      dominant kernel (k_path: all queries of the frame), its mean
                 launch time HIP-event timed on the stream it runs on, against
                 three counter-backed ceilings (VALU issue, L2 requests, HBM
@@ -49,7 +63,6 @@ import argparse
 import contextlib
 import json
 import os
-import socket
 import subprocess
 import sys
 import time
@@ -67,6 +80,14 @@ def parse_args(argv=None):
     ap.add_argument("--config", default="sponza1080", choices=["sponza1080", "teapot720", "suzanne360", "sponza4k"])
     ap.add_argument("--engine", default="persistent", choices=["wavefront", "persistent", "mega"])
     ap.add_argument("--seed-mode", default="sample", choices=["sample", "pixel", "row"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what is not the headline figure: the other seeding "
+                         "modes, the index tie rule, the roofline (instrumented run), the CPU baseline with its "
+                         "parity sample, the host paths (--no-compare, --compare, --no-cpu, --count-spp and "
+                         "--cpu-seconds shape these)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned (the frame, its "
+                         "ray count) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-compare", action="store_true", help="skip timing the other seeding modes")
     ap.add_argument("--compare", action="store_true",
                     help="time the other seeding modes at N>1 too (default: only at N=1, so the driver's "
@@ -81,7 +102,10 @@ def parse_args(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo = CPU rehearsal of the N>1 path "
                          "(ranks may share one GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return args
 
 
 def visible_gpus_without_hip() -> int:
@@ -123,11 +147,12 @@ def launch_ranks_if_needed() -> None:
     if ndev == 0:
         print("bench.py: no GPU visible", file=sys.stderr, flush=True)
         sys.exit(2)
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    # --standalone: the launcher's agent binds its rendezvous store to port 0
+    # itself and the ranks share that store, so no port number is picked here
+    # and handed on (a port found free and released can be taken by the time
+    # the launcher has imported torch and binds it)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--nnodes=1",
+           f"--nproc-per-node={args.gpus}", "--local-addr", "127.0.0.1", os.path.abspath(__file__)] + sys.argv[1:]
     print(f"bench.py: starting {args.gpus} ranks: {' '.join(cmd[1:])}", file=sys.stderr, flush=True)
     sys.exit(subprocess.run(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")).returncode)
 
@@ -348,6 +373,25 @@ def world_devices(ident: dict, world: int, dist_on: bool, backend: str) -> dict:
     return sharding.placement(devs, backend if dist_on else None)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(dirname: str, frame, step_rays: int) -> None:
+    """--dump-outputs: what the last timed step returned, as float .npy files.
+    A frame whose float32 copy would pass the limit is cut to a fixed, seeded
+    sample of its rows (the same rows in every run), named in image_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    h = frame.shape[0]
+    row_bytes = frame[0].size * 4
+    keep = (DUMP_LIMIT_BYTES - 10**6) // (row_bytes + 8)  # room for the headers and rays.npy
+    if keep < h:
+        rows = np.sort(np.random.default_rng(20240607).choice(h, size=keep, replace=False))
+        frame = frame[rows]
+        np.save(os.path.join(dirname, "image_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "image.npy"), frame.astype(np.float32))
+    np.save(os.path.join(dirname, "rays.npy"), np.array([step_rays], dtype=np.float64))
+
+
 @contextlib.contextmanager
 def stdout_to_stderr():
     """Point file descriptor 1 at stderr for the duration (native libraries
@@ -446,8 +490,10 @@ def main() -> None:
     redo_launches = redo_rays = 0
     redo_ms = 0.0
     last_tie_path = 0
+    last_rays = 0
     for _ in range(args.steps):
         r, st = step()
+        last_rays = r
         ties += st.tie_queries
         roots += st.root_misses
         cracks += st.crack_queries
@@ -479,8 +525,15 @@ def main() -> None:
 
     # ---- the other seeding mode, timed the same way (reported, not `value`)
     frame = image.cpu().numpy() if rank == 0 else None
+    if args.dump_outputs:
+        if dist_on:
+            r = torch.tensor([last_rays], dtype=torch.int64, device=gdev)
+            dist.all_reduce(r, op=dist.ReduceOp.SUM)
+            last_rays = int(r.item())
+        if rank == 0:
+            dump_outputs(args.dump_outputs, frame, last_rays)
     compare = {}
-    if not args.no_compare and (world == 1 or args.compare):
+    if args.full and not args.no_compare and (world == 1 or args.compare):
         for name, sd in seeds.items():
             if sd == seed:
                 continue
@@ -521,7 +574,7 @@ def main() -> None:
     # the exact-semantics contract of rounds 1-3): what the reference's own tie
     # answer costs (reported, not `value`)
     index_rule = None
-    if not args.no_compare and st0.tie_rule == 0:
+    if args.full and not args.no_compare and st0.tie_rule == 0:
         scene.set_option("tie_rule", 1)
         step()
         if dist_on:
@@ -554,12 +607,16 @@ def main() -> None:
         log(f"gathered frame: {world} ranks ({args.dist_backend}), {rays} rays")
 
     # ---- roofline of the dominant kernel (extend), from an instrumented run
-    _, _ = scene.trace_image(cam, W, H, args.count_spp, seed_mode=seed, engine=engine,
-                             band_rows=BAND_ROWS, shard=rank, num_shards=world,
-                             count_visits=True, out=tile.data_ptr())
-    cs = scene.stats()
+    cs = None
+    if args.full:
+        _, _ = scene.trace_image(cam, W, H, args.count_spp, seed_mode=seed, engine=engine,
+                                 band_rows=BAND_ROWS, shard=rank, num_shards=world,
+                                 count_visits=True, out=tile.data_ptr())
+        cs = scene.stats()
     roof = None
-    if engine == tm.ENGINE_WAVEFRONT and cs.extend_rays and ext_launches:
+    if cs is None:
+        pass
+    elif engine == tm.ENGINE_WAVEFRONT and cs.extend_rays and ext_launches:
         n_node = cs.node_visits / cs.extend_rays
         n_tri = cs.tri_tests / cs.extend_rays
         n_node_s = cs.shadow_node_visits / max(cs.shadow_rays, 1)
@@ -598,7 +655,7 @@ def main() -> None:
     # ---- CPU baseline: the reference algorithm on this host, bounded row sample
     cpu = None
     parity = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         cpu, parity = cpu_baseline(args, tris, bmin, bmax, cam, W, H, SPP, frame)
 
     if args.save:
@@ -608,7 +665,7 @@ def main() -> None:
     # ingest and PNG encode, sequential vs parallel (off the timed region, as in
     # main.cpp:122-170 / 341-342)
     host = None
-    if rank == 0:
+    if args.full:
         import tempfile
 
         def timed(fn, env, val):

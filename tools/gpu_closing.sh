@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-me
 rc=$?; tail -2 $out/pytest_gpu.log; grep -E "FAILED|ERROR" $out/pytest_gpu.log | head -20; if [ $rc -gt 1 ]; then exit $rc; fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { echo "smoke rc=$?"; tail $out/smoke.log; exit 1; }
 grep "smoke ok" $out/smoke.log
-timeout -k 10 600 python3 bench.py --steps $steps --warmup 2 > $out/bench.json 2> $out/bench.err || { echo "bench rc=$?"; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full --steps $steps --warmup 2 > $out/bench.json 2> $out/bench.err || { echo "bench rc=$?"; tail -20 $out/bench.err; exit 1; }
 python3 -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], {k: v.get('value') for k, v in d['seed_modes'].items()}, d['roofline']['bound'], d['roofline']['frac'], d['cpu_baseline']['value'], d['parity_sample'], d['reference_octree'])"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/prof -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-compare > $out/prof_bench.json 2> $out/prof.err
 rc=$?; echo "prof rc=$rc"; if [ $rc -ne 0 ]; then exit $rc; fi

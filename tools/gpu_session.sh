@@ -12,6 +12,6 @@ grep -E "FAILED|ERROR" $out/pytest_gpu.log | head -40
 tail -2 $out/pytest_gpu.log
 # 0 = all passed, 1 = some failed: the GPU is fine; anything else (crash, timeout) ends the session
 if [ $rc -gt 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
-timeout -k 10 400 python bench.py "$@" > $out/bench.json 2> $out/bench.err || { echo "bench rc=$?"; tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full "$@" > $out/bench.json 2> $out/bench.err || { echo "bench rc=$?"; tail -20 $out/bench.err; exit 1; }
 python3 -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], {k: v.get('value') for k, v in d['seed_modes'].items()}, d['roofline']['frac'], d.get('parity_sample'), d.get('reference_octree'))"
 echo session-done
