@@ -19,7 +19,9 @@
 //   7. k_tri_pre      leaf-ordered TriPre records
 //   8. k_bvh4_level   top-down collapse to the 4-wide quantised BVH, one launch
 //                     per level (greedy largest-area opening, or the SAH-optimal
-//                     forests of k_sah_level)
+//                     forests of k_sah_level); a PLOC tree too deep for the
+//                     traversal stack is built again with equal areas paired
+//                     up, and failing that the Karras tree is collapsed
 // The build is outside the timed region of the reference (main.cpp:312 vs
 // :319) and of bench.py; it is timed separately (Scene::build_ms).
 #include <hip/hip_runtime.h>
@@ -29,6 +31,7 @@
 #include <algorithm>
 #include <string>
 #include <chrono>
+#include <functional>
 #include <cmath>
 #include <mutex>
 #include <thread>
@@ -326,7 +329,7 @@ __global__ void __launch_bounds__(kBlock) k_ploc_init(int32_t n, Soa6 leaf, cons
     cb.hx[i] = leaf.hx[o]; cb.hy[i] = leaf.hy[o]; cb.hz[i] = leaf.hz[o];
 }
 
-__global__ void __launch_bounds__(kBlock) k_ploc_nn(int32_t N, int r, Soa6 cb, int32_t* __restrict__ nn)
+__global__ void __launch_bounds__(kBlock) k_ploc_nn(int32_t N, int r, int pair, Soa6 cb, int32_t* __restrict__ nn)
 {
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
@@ -338,7 +341,12 @@ __global__ void __launch_bounds__(kBlock) k_ploc_nn(int32_t N, int r, Soa6 cb, i
         if (j == i) continue;
         float d = half_area(fminf(lx, cb.lx[j]), fminf(ly, cb.ly[j]), fminf(lz, cb.lz[j]),
                             fmaxf(hx, cb.hx[j]), fmaxf(hy, cb.hy[j]), fmaxf(hz, cb.hz[j]));
-        if (d < best) {  // ascending j: ties keep the lower index
+        // Equal areas keep the lower index (ascending j).  pair: they take the
+        // smaller i ^ j instead, as delta() orders equal keys: of the pairs at
+        // the least area the one with the least i ^ j is mutual, so identical
+        // boxes merge as (0,1), (2,3), ... in one pass, where the lower index
+        // makes only (0,1) mutual and the tree a chain (build_lbvh retries with it).
+        if (d < best || (pair && d == best && (uint32_t)(i ^ j) < (uint32_t)(i ^ bj))) {
             best = d;
             bj = j;
         }
@@ -781,6 +789,73 @@ int radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* tkeys, uint32_t* 
 
 size_t radix_sort_hist_words(int32_t n) { return 256 * (size_t)std::max(1, blocks_for(n, kSortTile)); }
 
+namespace {
+
+// Leaf-ordered triangle records and the top-down collapse of one binary tree
+// (Karras or PLOC) to the BVH4Q in s.nodes4, one launch per level.  Returns 0,
+// -1 (HIP or memory error), or 1: the tree is too deep for the traversal stack
+// (the levels stop as soon as that is known, so a chain of n nodes costs
+// kStackTotal / 3 launches, not n / 3).
+template <class Alloc>
+int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2* trange, Soa6 leaf,
+                  const uint32_t* tvals, Soa6 tib, int troot, int2* fr0, int2* fr1, uint32_t* c4, Alloc& alloc)
+{
+    const int32_t n = s.n, m = s.n_nodes;
+    hipStream_t st = s.stream;
+    k_tri_pre<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, tvals, s.tri_pre);
+    const int leaf_max = s.opt.leaf_max;
+    s.leaf_max = leaf_max;
+    // collapse=1: SAH-optimal collapse (fewer, fuller nodes: 13.2k vs 16.7k
+    // on the sponza stand-in, but measured ~2% slower there); default greedy
+    // largest-area opening
+    const bool sah = s.opt.collapse == 1 && n >= 2;
+    uint32_t* dec = nullptr;
+    if (sah) {
+        const SahCost cost{1.0f, s.opt.sah_c_leaf, s.opt.sah_c_tri};
+        int32_t* ord = (int32_t*)alloc((size_t)m * 4);
+        float4* Fc = (float4*)alloc((size_t)m * sizeof(float4));
+        dec = (uint32_t*)alloc((size_t)m * 4);
+        if (!ord || !Fc || !dec) return -1;
+        std::vector<int> off = {0, 1};
+        uint32_t zero = 0, cnt = 0;
+        if (hipMemcpyAsync(ord, &troot, 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        while (off.back() > off[off.size() - 2]) {  // BFS: one level of internal nodes per launch
+            const int b0 = off[off.size() - 2], b1 = off.back();
+            if (hipMemcpyAsync(c4, &zero, 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+            k_bfs_level<<<blocks_for(b1 - b0, kBlock), kBlock, 0, st>>>(tchild, ord + b0, b1 - b0, ord + b1, c4);
+            if (hipMemcpyAsync(&cnt, c4, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) return -1;
+            off.push_back(b1 + (int)cnt);
+        }
+        for (int L = (int)off.size() - 3; L >= 0; --L)  // deepest level first
+            k_sah_level<<<blocks_for(off[L + 1] - off[L], kBlock), kBlock, 0, st>>>(
+                tchild, trange, leaf, tvals, tib, ord + off[L], off[L + 1] - off[L], Fc, dec, leaf_max, cost);
+    }
+    int2 root = make_int2(troot, 0);
+    uint32_t hc[2] = {1u, 0u};
+    if (hipMemcpyAsync(fr0, &root, sizeof(root), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(c4, hc, sizeof(hc), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    int nf = 1, levels = 0;
+    int2 *fa = fr0, *fb = fr1;
+    while (nf > 0) {
+        k_bvh4_level<<<blocks_for(nf, kBlock), kBlock, 0, st>>>(tchild, trange, leaf, tvals, tib, fa, nf,
+                                                                fb, c4, s.nodes4, leaf_max, n, dec);
+        ++levels;
+        if (hipMemcpyAsync(hc, c4, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) return -1;
+        nf = (int)hc[1];
+        hc[1] = 0;
+        if (hipMemcpyAsync(c4 + 1, &hc[1], 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+        std::swap(fa, fb);
+        s.n_nodes4 = (int32_t)hc[0];
+        s.depth4 = levels;
+        if (3 * levels + 1 > kStackTotal) return 1;
+    }
+    return 0;
+}
+
+}  // namespace
+
 int build_lbvh(Scene& s, const float* d_tris9)
 {
     const int32_t n = s.n;
@@ -881,6 +956,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
         Soa6 tib = ib;
         const uint32_t* tvals = vi;
         int troot = n == 1 ? ~0 : 0;
+        std::function<int(int)> run_ploc;
         if (ploc) {
             const int r = s.opt.ploc_radius;  // search radius; node visits vs r measured in DESIGN.md
             int32_t* cidA = (int32_t*)alloc(nn * 4);
@@ -907,98 +983,69 @@ int build_lbvh(Scene& s, const float* d_tris9)
             }
             auto soa = [](float* b, size_t k) { return Soa6{b, b + k, b + 2 * k, b + 3 * k, b + 4 * k, b + 5 * k}; };
             Soa6 cbA = soa(cbAb, nn), cbB = soa(cbBb, nn), pib = soa(pibb, mm);
-            if (hipMemsetAsync(pcounter, 0, 4, st) != hipSuccess || hipMemsetAsync(poff, 0, mm * 4, st) != hipSuccess) {
-                rc = -1;
-                break;
-            }
-            k_ploc_init<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, leaf, vi, cidA, cbA);
-            int N = n, it = 0;
-            while (N > 1) {
-                k_ploc_nn<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, r, cbA, nnb);
-                k_ploc_merge<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, nnb, cidA, cbA, valid, pchild, pib,
-                                                                       psize, piter, it, pcounter);
-                uint32_t tail[2];
-                if (hipMemcpyAsync(pos, valid, (size_t)N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = -1; break; }
-                k_scan_1block<<<1, 1024, 0, st>>>(pos, N);
-                if (hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipMemcpyAsync(&tail[1], valid + N - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-                k_ploc_compact<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, valid, pos, cidA, cbA, cidB, cbB);
-                std::swap(cidA, cidB);
-                std::swap(cbA, cbB);
-                int next = (int)(tail[0] + tail[1]);
-                if (next >= N) { set_error("build: PLOC made no progress"); rc = -2; break; }
-                N = next;
-                ++it;
-            }
+            // one PLOC build over the sorted leaves into pchild / prange / pib /
+            // pvals; pair: k_ploc_nn's rule for equal areas
+            run_ploc = [=, &s](int pair) mutable -> int {
+                if (hipMemsetAsync(pcounter, 0, 4, st) != hipSuccess || hipMemsetAsync(poff, 0, mm * 4, st) != hipSuccess)
+                    return -1;
+                k_ploc_init<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, leaf, vi, cidA, cbA);
+                int N = n, it = 0;
+                while (N > 1) {
+                    k_ploc_nn<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, r, pair, cbA, nnb);
+                    k_ploc_merge<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, nnb, cidA, cbA, valid, pchild, pib,
+                                                                           psize, piter, it, pcounter);
+                    uint32_t tail[2];
+                    if (hipMemcpyAsync(pos, valid, (size_t)N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
+                    k_scan_1block<<<1, 1024, 0, st>>>(pos, N);
+                    if (hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipMemcpyAsync(&tail[1], valid + N - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        hipStreamSynchronize(st) != hipSuccess) return -1;
+                    k_ploc_compact<<<blocks_for(N, kBlock), kBlock, 0, st>>>(N, valid, pos, cidA, cbA, cidB, cbB);
+                    std::swap(cidA, cidB);
+                    std::swap(cbA, cbB);
+                    int next = (int)(tail[0] + tail[1]);
+                    if (next >= N) { set_error("build: PLOC made no progress"); return -2; }
+                    N = next;
+                    ++it;
+                }
+                for (int k = it - 1; k >= 0; --k)
+                    k_ploc_offsets<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, k, piter, pchild, psize, poff, new_slot);
+                k_ploc_relabel<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, pchild, poff, psize, prange, new_slot);
+                k_ploc_vals<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, new_slot, vi, pvals);
+                s.ploc_iters = it;
+                return 0;
+            };
+            rc = run_ploc(0);
             if (rc) break;
-            for (int k = it - 1; k >= 0; --k)
-                k_ploc_offsets<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, k, piter, pchild, psize, poff, new_slot);
-            k_ploc_relabel<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, pchild, poff, psize, prange, new_slot);
-            k_ploc_vals<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, new_slot, vi, pvals);
             tchild = pchild;
             trange = prange;
             tib = pib;
             tvals = pvals;
             troot = m - 1;  // the last merge creates the root
-            s.ploc_iters = it;
         }
-        k_tri_pre<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, tvals, s.tri_pre);
-        // binary tree -> BVH4Q, top-down, one launch per level
-        const int leaf_max = s.opt.leaf_max;
-        s.leaf_max = leaf_max;
-        // collapse=1: SAH-optimal collapse (fewer, fuller nodes: 13.2k vs 16.7k
-        // on the sponza stand-in, but measured ~2% slower there); default greedy
-        // largest-area opening
-        const bool sah = s.opt.collapse == 1 && n >= 2;
-        uint32_t* dec = nullptr;
-        if (sah) {
-            const SahCost cost{1.0f, s.opt.sah_c_leaf, s.opt.sah_c_tri};
-            int32_t* ord = (int32_t*)alloc((size_t)m * 4);
-            float4* Fc = (float4*)alloc((size_t)m * sizeof(float4));
-            dec = (uint32_t*)alloc((size_t)m * 4);
-            if (!ord || !Fc || !dec) { set_error("build: out of device memory"); rc = -1; break; }
-            std::vector<int> off = {0, 1};
-            uint32_t zero = 0, cnt = 0;
-            if (hipMemcpyAsync(ord, &troot, 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
-            while (off.back() > off[off.size() - 2]) {  // BFS: one level of internal nodes per launch
-                const int b0 = off[off.size() - 2], b1 = off.back();
-                if (hipMemcpyAsync(c4, &zero, 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
-                k_bfs_level<<<blocks_for(b1 - b0, kBlock), kBlock, 0, st>>>(tchild, ord + b0, b1 - b0, ord + b1, c4);
-                if (hipMemcpyAsync(&cnt, c4, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-                off.push_back(b1 + (int)cnt);
-            }
-            if (rc) break;
-            for (int L = (int)off.size() - 3; L >= 0; --L)  // deepest level first
-                k_sah_level<<<blocks_for(off[L + 1] - off[L], kBlock), kBlock, 0, st>>>(
-                    tchild, trange, leaf, tvals, tib, ord + off[L], off[L + 1] - off[L], Fc, dec, leaf_max, cost);
+        // binary tree -> BVH4Q.  A PLOC tree too deep for the traversal stack is
+        // a chain: among clusters with one and the same box (coincident or
+        // zero-size triangles, duplicated faces) "the lower index" makes only
+        // clusters 0 and 1 mutual neighbours, one merge per pass.  It is built
+        // again with equal areas paired up; every tree that fits keeps the
+        // first rule and stays as it was.  Clusters whose unions nest (ever
+        // larger boxes around one point) chain under either rule: then the
+        // Karras tree, already built and bounded in depth by the key and index
+        // bits, is collapsed instead, and builder_iters = 0 says so.
+        int crc = collapse_bvh4(s, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
+        if (crc == 1 && ploc) {
+            crc = run_ploc(1);
+            if (crc == 0) crc = collapse_bvh4(s, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
         }
-        int2 root = make_int2(troot, 0);
-        uint32_t hc[2] = {1u, 0u};
-        if (hipMemcpyAsync(fr0, &root, sizeof(root), hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(c4, hc, sizeof(hc), hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
-        int nf = 1, levels = 0;
-        int2 *fa = fr0, *fb = fr1;
-        while (nf > 0) {
-            k_bvh4_level<<<blocks_for(nf, kBlock), kBlock, 0, st>>>(tchild, trange, leaf, tvals, tib, fa, nf,
-                                                                    fb, c4, s.nodes4, leaf_max, n, dec);
-            ++levels;
-            if (hipMemcpyAsync(hc, c4, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-            nf = (int)hc[1];
-            hc[1] = 0;
-            if (hipMemcpyAsync(c4 + 1, &hc[1], 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
-            std::swap(fa, fb);
+        if (crc == 1 && ploc) {
+            s.ploc_iters = 0;
+            crc = collapse_bvh4(s, d_tris9, child, range, leaf, vi, ib, 0, fr0, fr1, c4, alloc);
         }
-        if (rc) break;
-        s.n_nodes4 = (int32_t)hc[0];
-        s.depth4 = levels;
-        if (3 * levels + 1 > kStackTotal) {
-            set_error("build_lbvh: BVH4 depth " + std::to_string(levels) + " exceeds the traversal stack");
-            rc = -2;
-            break;
+        if (crc == 1) {
+            set_error("build_lbvh: BVH4 depth exceeds the traversal stack (" + std::to_string(s.depth4) + " levels)");
+            crc = -2;
         }
+        rc = crc;
     } while (0);
     hipError_t e = hipGetLastError();
     hipError_t e2 = hipStreamSynchronize(st);
