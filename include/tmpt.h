@@ -40,7 +40,10 @@ extern "C" {
                               (tmpt_stats.crack_queries, octree_flat), tmpt_stats.redo_launches /
                               redo_ms (k_redo apart from the k_path launches);
                               9: tmpt_stats.tie_path (how the last render answered the
-                              octree's queries, and whether the deferred form fell back) */
+                              octree's queries, and whether the deferred form fell back);
+                              still 9, additive: tmpt_render_aov and tmpt_aov_pixel (the AOV pass) and
+                              the render option aov_group -- no struct above changed, so the version
+                              did not: callers detect the entry point by its symbol */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -157,6 +160,28 @@ typedef struct {
     int32_t reserved_stats;
 } tmpt_stats;
 
+/* One pixel of the AOV pass (tmpt_render_aov), 32 B: the guide buffers of a
+ * sample-seeded frame, from the camera rays that frame traces.  The camera ray
+ * of sample s of pixel (x, y) is the one TraceImageBody forms (main.cpp:209-221)
+ * from the sample's own RNG state, sample_seed(s, pixel_seed(x, y, width))
+ * (TMPT_SEED_SAMPLE above); it is answered as HitScene answers the beauty
+ * render's camera ray (main.cpp:91), and a hit takes Scatter's shadow query
+ * and light term (main.cpp:53-72).  Every sum is float32, starts at 0.0f, is
+ * taken in sample order s = 0 .. spp-1 (part of the contract, as the colour
+ * sum's order is), a miss adding nothing, and is then multiplied by
+ * spp_recip = 1.0f / (float)spp, as the colour is (main.cpp:188, 221-223). */
+typedef struct {
+    float    normal[3]; /* sum over the pixel's samples of the hit normal exactly as HitScene returns it
+                           (geometric, not flipped towards the ray), times spp_recip */
+    float    depth;     /* sum of the hit t, times spp_recip */
+    float    direct;    /* sum of the first bounce's light scalar, times spp_recip: fmax(0, dot(kLightDir, nl))
+                           (main.cpp:66-67) where it is > 0 and the shadow query (main.cpp:59) misses,
+                           else nothing.  Times albedo * kLightColor this is bounce 0's outLightE (main.cpp:67) */
+    int32_t  tri_id;    /* closest triangle of sample 0, or -1 */
+    uint32_t hits;      /* samples whose camera ray hit (coverage = hits / spp) */
+    uint32_t lit;       /* of them, those that added to `direct` */
+} tmpt_aov_pixel;
+
 /* ---- host side: scene ingest and camera (not kernels) ------------------- */
 
 /* LoadScene (main.cpp:122-170) over objParseFile (objparser.cpp:304-355):
@@ -262,7 +287,10 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *   redo_cap         test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown
  *   redo_inline      test hook (1): 0 leaves every dropped sample to the second launch
- *                    that otherwise takes only those the main launch's tail did not */
+ *                    that otherwise takes only those the main launch's tail did not
+ *   aov_group        tmpt_render_aov: lanes that share a pixel, each tracing every aov_group-th
+ *                    sample (0 = auto: the largest of them that spp fills; or 1, 2, 4, 8, 16); the
+ *                    records are the same for every value */
 int tmpt_scene_create_ex(const float* tris, int32_t n, int32_t device, const char* options, tmpt_scene** out);
 int tmpt_scene_set_option(tmpt_scene* scene, const char* key, double value);
 int tmpt_scene_get_option(const tmpt_scene* scene, const char* key, double* value);
@@ -322,6 +350,26 @@ int tmpt_scene_hit_ranged(const tmpt_scene* scene, const float* rays8, int64_t n
  * *ray_count = every HitScene call (main.cpp:57,91), counted in uint64. */
 int tmpt_render(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
                 uint8_t* rgba_out, uint64_t* ray_count);
+/* The AOV pass of desc's shard: one tmpt_aov_pixel per pixel into out
+ * (tmpt_tile_rows(desc) * width records, the compact tile layout of
+ * tmpt_render, row 0 = the lowest rendered row).  One closest-hit query per
+ * sample and one shadow query per hit -- the primary rays of a
+ * TMPT_SEED_SAMPLE render of the same desc, with its jitter, lens samples,
+ * octree root test and tie rule, so the buffers line up with that frame.
+ * Reads width, height, spp, band_rows, shard, num_shards, flags and
+ * wait_stream (TMPT_FLAG_OUT_DEVICE: out is a device pointer, 16-byte aligned;
+ * TMPT_FLAG_WAIT_STREAM as in tmpt_render); engine is not read.  -22 unless
+ * seed_mode is TMPT_SEED_SAMPLE (the only seeding where the primary rays are
+ * a function of pixel and sample), spp_begin and spp_count are 0,
+ * TMPT_FLAG_COUNT_VISITS is clear and the sizes are within tmpt_render's
+ * limits.  *ray_count = pixels * spp closest-hit queries + one shadow query
+ * per hit (counted even where a zero cosine skips it, as main.cpp:57 counts).
+ * tmpt_get_stats afterwards: render_ms, extend_ms, extend_rays, shadow_rays,
+ * extend_launches = 1, tie_queries, root_misses, crack_queries.  The call
+ * leaves the scene's progressive state alone: it may run between two passes
+ * of a progressive render.  Render option aov_group sets the lanes per pixel. */
+int tmpt_render_aov(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
+                    tmpt_aov_pixel* out, uint64_t* ray_count);
 /* main.cpp:312-331 over several devices in ONE process (SURVEY.md §8e's
  * single-process form): a scene per entry of devices[] (created here, freed on
  * return), the frame's rows dealt round-robin to them (1-row bands), one host

@@ -1,0 +1,302 @@
+"""The AOV pass (tmpt_render_aov / Scene.trace_aov) against the CPU oracle, bit
+for bit: the expectation is composed on the host from the oracle's own pieces
+(pixel_seed, sample_seed, the RNG draws, get_ray, hit_batch), the light scalar
+restated in numpy float32 in tmpt_math.h's operation order, the sums taken in
+sample order.  No tolerances: float fields are compared as bits."""
+import ctypes
+import functools
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+import toymeshpathtracer_amd as tm
+from conftest import ROOT, data
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+CHECK_LIB = os.path.join(ROOT, "toymeshpathtracer_amd", "_lib_check", "libtmpt.so")
+
+
+def _dot(a, b):  # glm: (x*x' + y*y') + z*z', one rounding per operation
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _normalize(v):  # v * (1 / sqrt(dot(v, v)))
+    return v * (f32(1) / np.sqrt(_dot(v, v)))
+
+
+LIGHT = _normalize(np.array([-0.7, 1.0, 0.5], f32))
+
+
+def _light_cosine(n, d):
+    nl = np.where((_dot(n, d) < 0)[:, None], n, -n)
+    c = _dot(np.broadcast_to(LIGHT, nl.shape), nl)
+    return np.where(c > 0, c, f32(0)).astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def _load(name):
+    return tm.load_scene(data(name))
+
+
+@functools.lru_cache(maxsize=None)
+def _expect(name, w, h, spp, index=False):
+    """(records[h, w], per-sample counts) of the whole frame from the oracle."""
+    tris, bmin, bmax = _load(name)
+    cam = tm.Camera.for_scene(bmin, bmax, w, h).as_array()
+    osc = (oracle.Scene(tris, accel=oracle.ACCEL_BVH, tie=oracle.TIE_INDEX, bmin=bmin, bmax=bmax) if index else
+           oracle.Scene(tris, accel=oracle.ACCEL_OCTREE, tie=oracle.TIE_VISIT, bmin=bmin, bmax=bmax))
+    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
+    rays = np.zeros((h, w, spp, 6), f32)
+    for y in range(h):
+        for x in range(w):
+            seed = oracle.pixel_seed(x, y, w)
+            for s in range(spp):
+                st = oracle.sample_seed(seed, s)
+                r = oracle.float01_seq(st, 2)
+                state = int(oracle.xorshift_seq(st, 2)[1])
+                o, d, _ = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
+                rays[y, x, s, :3], rays[y, x, s, 3:] = o, d
+    flat = rays.reshape(-1, 6)
+    ids, hits = osc.hit_batch(flat, 0.001, 1.0e7)
+    hit = ids >= 0
+    lc = _light_cosine(hits[:, 3:6], flat[:, 3:6])
+    want_shadow = hit & (lc > 0)
+    sids, _ = osc.hit_batch(np.concatenate([hits[:, 0:3], np.broadcast_to(LIGHT, (len(flat), 3))], 1), 0.001, 1.0e7)
+    lit = want_shadow & (sids < 0)
+    shape = (h, w, spp)
+    hit, lit, lc, ids = hit.reshape(shape), lit.reshape(shape), lc.reshape(shape), ids.reshape(shape)
+    nrm, t = hits[:, 3:6].reshape(shape + (3,)), hits[:, 6].reshape(shape)
+    rec = np.zeros((h, w), tm.AOV_DTYPE)
+    nsum, dsum, lsum = np.zeros((h, w, 3), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
+    for s in range(spp):  # float32 sums in sample order; a miss adds nothing
+        nsum = np.where(hit[..., s, None], nsum + nrm[..., s, :], nsum)
+        dsum = np.where(hit[..., s], dsum + t[..., s], dsum)
+        lsum = np.where(lit[..., s], lsum + lc[..., s], lsum)
+    recip = f32(1) / f32(spp)
+    rec["normal"], rec["depth"], rec["direct"] = nsum * recip, dsum * recip, lsum * recip
+    rec["tri_id"] = np.where(hit[..., 0], ids[..., 0], -1)
+    rec["hits"], rec["lit"] = hit.sum(-1), lit.sum(-1)
+    per_pixel = hit.sum(-1)
+    counts = dict(hits=int(hit.sum()), misses=int((~hit).sum()),
+                  shadowed=int((want_shadow.reshape(shape) & ~lit).sum()),
+                  partial=int(((per_pixel > 0) & (per_pixel < spp)).sum()))
+    return rec, counts
+
+
+def _scene(name, index=False):
+    tris, bmin, bmax = _load(name)
+    return tm.Scene(tris, bounds=(bmin, bmax), options="tie_rule=index" if index else None)
+
+
+def _cam(name, w, h):
+    _, bmin, bmax = _load(name)
+    return tm.Camera.for_scene(bmin, bmax, w, h)
+
+
+def _same(got, want):
+    """Every field of every record, floats as bits."""
+    for f in tm.AOV_DTYPE.names:
+        a, b = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
+        bad = np.argwhere((a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape))
+        assert len(bad) == 0, f"{f}: {len(bad)} differ, first at {bad[0]}: {a[tuple(bad[0])]} vs {b[tuple(bad[0])]}"
+    assert got.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize("name,w,h,spp,index", [("suzanne.obj", 32, 18, 4, False), ("teapot.obj", 24, 14, 2, False),
+                                                ("cube.obj", 16, 9, 3, False), ("cube.obj", 16, 9, 3, True)])
+def test_aov_matches_oracle(gpu, name, w, h, spp, index):
+    want, n = _expect(name, w, h, spp, index)
+    print(name, w, h, spp, "index" if index else "octree", n)
+    # the oracle's own data covers every branch of the pass
+    lo = dict(hits=1, misses=1, shadowed=1, partial=1) if index else dict(hits=200, misses=100, shadowed=20, partial=5)
+    for k, v in lo.items():
+        assert n[k] >= v, (k, n)
+    with _scene(name, index) as sc:
+        got, rays = sc.trace_aov(_cam(name, w, h), w, h, spp)
+        st = sc.stats()
+    assert got.shape == (h, w) and got.dtype == tm.AOV_DTYPE
+    _same(got, want)
+    assert rays == w * h * spp + n["hits"]
+    assert st.extend_rays == w * h * spp and st.shadow_rays == n["hits"]
+    assert st.extend_launches == 1 and st.render_ms > 0
+
+
+@pytest.mark.parametrize("spp", [5, 1])
+def test_aov_group_sizes_identical(gpu, spp):
+    """37 pixels a row is no multiple of any group count per wave, and 5 (or 1)
+    samples are neither a multiple of nor at least G: idle lanes, partial
+    rounds and tickets that straddle rows, the same record every time."""
+    w, h = 37, 11
+    want, _ = _expect("suzanne.obj", w, h, spp)
+    cam = _cam("suzanne.obj", w, h)
+    seen = {}
+    with _scene("suzanne.obj") as sc:
+        for g in (1, 2, 4, 8, 16, 0):
+            sc.set_option("aov_group", g)
+            assert sc.get_option("aov_group") == g
+            seen[g] = sc.trace_aov(cam, w, h, spp)
+    _same(seen[1][0], want)
+    for g, (rec, rays) in seen.items():
+        assert rec.tobytes() == seen[1][0].tobytes(), g
+        assert rays == seen[1][1], g
+
+
+def test_aov_shards_assemble(gpu):
+    w, h, spp, band, shards = 37, 11, 3, 2, 3
+    cam = _cam("suzanne.obj", w, h)
+    with _scene("suzanne.obj") as sc:
+        full, rays = sc.trace_aov(cam, w, h, spp)
+        frame = np.zeros((h, w), tm.AOV_DTYPE)
+        seen, total = np.zeros(h, int), 0
+        for k in range(shards):
+            tile, r = sc.trace_aov(cam, w, h, spp, band_rows=band, shard=k, num_shards=shards)
+            ys = tm.tile_row_to_y(w, h, band, k, shards)
+            assert tile.shape == (len(ys), w)
+            frame[ys] = tile
+            seen[ys] += 1
+            total += r
+    assert (seen == 1).all()
+    assert frame.tobytes() == full.tobytes()
+    assert total == rays
+    _same(full, _expect("suzanne.obj", w, h, spp)[0])
+
+
+def test_aov_device_output_after_caller_stream(gpu):
+    """out = a torch tensor's device pointer, filled on torch's current stream
+    just before the call: the pass is ordered after the fill (wait_stream)."""
+    import torch
+
+    w, h, spp = 32, 18, 4
+    cam = _cam("suzanne.obj", w, h)
+    with _scene("suzanne.obj") as sc:
+        host, rays = sc.trace_aov(cam, w, h, spp)
+        tile = torch.empty((h, w, tm.AOV_DTYPE.itemsize), dtype=torch.uint8, device="cuda:0")
+        assert tile.data_ptr() % 16 == 0
+        tile.fill_(7)
+        none, rays_dev = sc.trace_aov(cam, w, h, spp, out=tile.data_ptr())
+        got = tile.cpu().numpy().view(tm.AOV_DTYPE).reshape(h, w)
+    assert none is None and rays_dev == rays
+    assert got.tobytes() == host.tobytes()
+
+
+def test_aov_leaves_render_state_alone(gpu):
+    w, h, spp = 32, 18, 8
+    cam = _cam("suzanne.obj", w, h)
+    with _scene("suzanne.obj") as sc:
+        before, rays0 = sc.trace_image(cam, w, h, spp, seed_mode=tm.SEED_SAMPLE)
+        aov, _ = sc.trace_aov(cam, w, h, spp)
+        after, rays1 = sc.trace_image(cam, w, h, spp, seed_mode=tm.SEED_SAMPLE)
+        assert np.array_equal(before, after) and rays0 == rays1
+        passes = sc.trace_progressive(cam, w, h, spp, [3, 5], seed_mode=tm.SEED_SAMPLE)
+        done, _, r_a = next(passes)
+        assert done == 3
+        between, _ = sc.trace_aov(cam, w, h, spp)  # between two passes of the sequence
+        done, last, r_b = next(passes)
+        assert done == spp
+    assert np.array_equal(last, before) and r_a + r_b == rays0
+    assert between.tobytes() == aov.tobytes()
+
+
+def test_aov_argument_errors(gpu):
+    w, h, spp = 16, 9, 2
+    cam = _cam("cube.obj", w, h)._to_c()
+    out = np.zeros((h, w), tm.AOV_DTYPE)
+    rays = ctypes.c_uint64()
+
+    def call(handle, desc, ptr):
+        rc = tm._render_aov(handle, ctypes.byref(cam), ctypes.byref(desc), ptr, ctypes.byref(rays))
+        return rc, tm._last_error().decode()
+
+    with _scene("cube.obj") as sc:
+        p = out.ctypes.data_as(ctypes.c_void_p)
+        for desc, msg in ((tm._desc(w, h, spp, tm.SEED_ROW), "seed_mode"),
+                          (tm._desc(w, h, spp, tm.SEED_PIXEL), "seed_mode"),
+                          (tm._desc(w, h, spp, tm.SEED_SAMPLE, spp_begin=1), "spp_begin"),
+                          (tm._desc(w, h, spp, tm.SEED_SAMPLE, flags=tm.FLAG_COUNT_VISITS), "COUNT_VISITS"),
+                          (tm._desc(0, h, spp, tm.SEED_SAMPLE), "width"),
+                          (tm._desc(w, h, 2000, tm.SEED_SAMPLE), "samplesPerPixel")):
+            rc, err = call(sc._h, desc, p)
+            assert rc == -22 and msg in err, (rc, err)
+        rc, err = call(sc._h, tm._desc(w, h, spp, tm.SEED_SAMPLE), None)
+        assert rc == -22 and "null" in err, (rc, err)
+        rc, err = call(sc._h, tm._desc(w, h, spp, tm.SEED_SAMPLE), p)  # and the good call still runs
+        assert rc == 0, err
+    assert rays.value == w * h * spp + int(out["hits"].sum())
+
+
+def _unit(v):
+    return np.minimum(np.maximum(v, f32(0)), f32(1))
+
+
+def test_aov_cli_pngs(gpu, tmp_path):
+    from PIL import Image
+
+    w, h, spp = 32, 18, 4
+    cli = os.path.join(os.path.dirname(tm.lib_path), "tmpt")
+    prefix = str(tmp_path / "g")
+    r = subprocess.run([cli, str(w), str(h), str(spp), data("suzanne.obj"), "--aov", prefix, "--seed", "sample",
+                        "--out", str(tmp_path / "frame.png")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    with _scene("suzanne.obj") as sc:
+        rec, _ = sc.trace_aov(_cam("suzanne.obj", w, h), w, h, spp)
+
+    def png(kind):
+        return np.asarray(Image.open(f"{prefix}_{kind}.png").convert("RGBA"))[::-1]  # flipped on write
+
+    want = np.full((h, w, 4), 255, np.uint8)
+    want[..., :3] = (_unit(rec["normal"] * f32(0.5) + f32(0.5)) * f32(255)).astype(np.uint8)
+    assert np.array_equal(png("normal"), want)
+    want[..., :3] = (_unit(np.sqrt(rec["direct"])) * f32(255)).astype(np.uint8)[..., None]
+    assert np.array_equal(png("direct"), want)
+    covered = rec["hits"] > 0
+    assert covered.any() and not covered.all()
+    d = rec["depth"][covered] * f32(spp) / rec["hits"][covered].astype(f32)
+    grey = np.zeros((h, w), np.uint8)
+    grey[covered] = ((f32(1) - (d - d.min()) / (d.max() - d.min())) * f32(255)).astype(np.uint8)
+    want[..., :3] = grey[..., None]
+    assert np.array_equal(png("depth"), want)
+    r = subprocess.run([cli, str(w), str(h), str(spp), data("suzanne.obj"), "--aov", prefix, "--gpus", "2"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--aov" in r.stdout
+
+
+CHILD = r'''
+import hashlib, json, sys
+sys.path.insert(0, sys.argv[1])
+import toymeshpathtracer_amd as tm
+tris, bmin, bmax = tm.load_scene(sys.argv[2])
+out = {}
+try:
+    with tm.Scene(tris, bounds=(bmin, bmax)) as sc:
+        rec, rays = sc.trace_aov(tm.Camera.for_scene(bmin, bmax, 32, 18), 32, 18, 4)
+    out = {"records": hashlib.sha256(rec.tobytes()).hexdigest(), "rays": rays}
+except tm.TmptError as e:
+    out["error"] = str(e)
+print(json.dumps(out))
+'''
+
+
+@pytest.mark.skipif(not os.path.exists(CHECK_LIB),
+                    reason="checked build not built (make -C toymeshpathtracer_amd/csrc CHECK=1)")
+def test_aov_checked_build(gpu):
+    """The checked library (device index tests compiled in) computes the same
+    records and no check fails (no -30)."""
+    env = dict(os.environ, TMPT_NO_TORCH="1", TMPT_LIB_PATH=CHECK_LIB)
+    env.pop("TMPT_CHECK_SELFTEST", None)
+    r = subprocess.run([sys.executable, "-c", CHILD, ROOT, data("suzanne.obj")], capture_output=True, text=True,
+                       timeout=240, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert "error" not in got, got
+    assert "device index check failed" not in r.stderr
+    with _scene("suzanne.obj") as sc:
+        rec, rays = sc.trace_aov(_cam("suzanne.obj", 32, 18), 32, 18, 4)
+    assert got == {"records": hashlib.sha256(rec.tobytes()).hexdigest(), "rays": rays}

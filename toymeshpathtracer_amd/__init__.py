@@ -12,6 +12,8 @@ reference                   here
 ``BuildOctree`` scene.h:26  :meth:`Scene.build_octree` (+ :func:`octree_bounds`, main.cpp:312)
 ``Scene::HitScene`` :36     :meth:`Scene.hit_scene` / :meth:`Scene.hit_scene_batch`
 ``TraceImageBody`` :180     :meth:`Scene.trace_image` (parallel_for, main.cpp:329)
+(none: guide buffers)       :meth:`Scene.trace_aov` (:data:`AOV_DTYPE` records: normal, depth, direct
+                            light, triangle id, coverage of a sample-seeded frame's camera rays)
 ``stbi_write_png`` :342     :func:`write_png`
 ==========================  ==============================================
 
@@ -31,11 +33,16 @@ __all__ = [
     "Camera", "Scene", "Hit", "RenderStats", "load_scene", "write_png", "device_count",
     "SEED_ROW", "SEED_PIXEL", "SEED_SAMPLE", "ENGINE_WAVEFRONT", "ENGINE_MEGAKERNEL", "ENGINE_PERSISTENT", "lib_path", "TmptError",
     "tile_rows", "tile_row_to_y", "render_multi", "octree_bounds", "octree_digest", "octree_flags",
+    "AOV_DTYPE",
 ]
 
 SEED_ROW, SEED_PIXEL, SEED_SAMPLE = 0, 1, 2
 ENGINE_WAVEFRONT, ENGINE_MEGAKERNEL, ENGINE_PERSISTENT = 0, 1, 2
 FLAG_OUT_DEVICE, FLAG_COUNT_VISITS, FLAG_WAIT_STREAM, FLAG_REQUIRE_RCCL = 1, 2, 4, 8
+
+#: tmpt_aov_pixel (include/tmpt.h), one record of :meth:`Scene.trace_aov`, 32 bytes
+AOV_DTYPE = np.dtype([("normal", np.float32, (3,)), ("depth", np.float32), ("direct", np.float32),
+                      ("tri_id", np.int32), ("hits", np.uint32), ("lit", np.uint32)])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TMPT_LIB_PATH: another in-tree build of the library (compiler-flag A/B in tools/)
@@ -142,6 +149,8 @@ _scene_hit_ranged = _sig("tmpt_scene_hit_ranged", ctypes.c_int, [ctypes.c_void_p
                                                                  ctypes.c_int32, _f32p, _i32p])
 _render = _sig("tmpt_render", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
                                              ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
+_render_aov = _sig("tmpt_render_aov", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
+                                                     ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
 _build_octree = _sig("tmpt_scene_build_octree", ctypes.c_int, [ctypes.c_void_p, _f32p, _f32p])
 _octree_bounds = _sig("tmpt_octree_bounds", ctypes.c_int, [_f32p, _f32p, _f32p])
 _octree_digest = _sig("tmpt_octree_digest", ctypes.c_int, [_f32p, ctypes.c_int32, _f32p, _f32p, _u64p])
@@ -167,7 +176,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_render", "tmpt_render_multi", "tmpt_tile_rows", "tmpt_tile_row_to_y", "tmpt_get_stats",
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
-           "tmpt_octree_flags")
+           "tmpt_octree_flags", "tmpt_render_aov")
 
 
 def _check(rc: int, what: str) -> None:
@@ -534,6 +543,37 @@ class Scene:
                                          num_shards=num_shards, spp_begin=done, spp_count=n)
             done += n
             yield done, img, rays
+
+    def trace_aov(self, camera: Camera, width: int, height: int, spp: int, band_rows: int = 0,
+                  shard: int = 0, num_shards: int = 1, out=None, wait_stream="current"):
+        """The AOV pass of one shard (tmpt_render_aov): returns (records[tile_rows,
+        width] of :data:`AOV_DTYPE`, rays) -- per pixel the summed hit normal,
+        depth and first-bounce light scalar (each times 1/spp), sample 0's
+        triangle id and the hit / lit sample counts, from the camera rays a
+        ``SEED_SAMPLE`` :meth:`trace_image` of the same size and spp traces.
+        rays = one closest-hit query per sample + one shadow query per hit.
+        ``out`` (a device pointer with tile_rows*width*32 bytes, 16-byte aligned;
+        then records is None) and ``wait_stream`` as in :meth:`trace_image`.
+        Render option ``aov_group`` sets the lanes that share a pixel."""
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        rows = int(_tile_rows(ctypes.byref(d)))
+        rays = ctypes.c_uint64()
+        cam = camera._to_c()
+        if out is not None:
+            _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.c_void_p(int(out)),
+                               ctypes.byref(rays)), "trace_aov")
+            return None, int(rays.value)
+        rec = np.zeros((rows, width), AOV_DTYPE)
+        _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), rec.ctypes.data_as(ctypes.c_void_p),
+                           ctypes.byref(rays)), "trace_aov")
+        return rec, int(rays.value)
 
     def stats(self) -> RenderStats:
         s = _Stats()

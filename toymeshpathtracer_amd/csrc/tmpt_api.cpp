@@ -15,6 +15,7 @@
 #include "tmpt.h"
 #include "tmpt_internal.h"
 #include "tmpt_traverse.h"
+#include "tmpt_render.h"
 
 namespace tmpt {
 
@@ -141,6 +142,7 @@ const OptionDef kOptions[] = {
     {"wf_bins", false, 1, 8, &Options::wf_bins, nullptr, nullptr},
     {"rowstream_test_abort", false, 0, 1, &Options::rowstream_test_abort, nullptr, nullptr},
     {"tie_rule", false, 0, 1, &Options::tie_rule, nullptr, nullptr},
+    {"aov_group", false, 0, 16, &Options::aov_group, nullptr, nullptr},
 };
 
 const OptionDef* find_option(const char* key)
@@ -174,6 +176,10 @@ int options_set(Options& o, const char* key, double v, bool allow_build)
         }
         if ((strcmp(key, "row_occ") == 0 || strcmp(key, "path_waves") == 0) && v != 0 && v != 4 && v != 5) {
             set_error(std::string("option '") + key + "' takes 0 (auto), 4 or 5");  // waves per SIMD
+            return -22;
+        }
+        if (strcmp(key, "aov_group") == 0 && v > 0 && ((long long)v & ((long long)v - 1)) != 0) {
+            set_error(std::string("option '") + key + "' out of range: 0 (auto), 1, 2, 4, 8 or 16");  // lanes per pixel
             return -22;
         }
         if ((strcmp(key, "sample_block") == 0 || strcmp(key, "wf_bins") == 0) && v > 0 &&
@@ -706,6 +712,43 @@ int tmpt_render(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d
     if (!rc && !dev_out && bytes) {
         if (hipMemcpy(rgba_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
             rc = (set_error("tmpt_render: readback failed"), -1);
+    }
+    if (!dev_out && d_out) (void)hipFree(d_out);
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_render_aov(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt_aov_pixel* out,
+                    uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    if (!h || !cam || !d || !out) return bad("tmpt_render_aov: null argument");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_aov: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_aov: invalid height");
+    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_aov: invalid samplesPerPixel");
+    if (d->seed_mode != TMPT_SEED_SAMPLE)
+        return bad("tmpt_render_aov: seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a camera ray is a "
+                   "function of pixel and sample)");
+    if (d->spp_begin != 0 || d->spp_count != 0)
+        return bad("tmpt_render_aov: spp_begin / spp_count must be 0 (the pass is not progressive)");
+    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_aov: TMPT_FLAG_COUNT_VISITS is not supported");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
+        return bad("tmpt_render_aov: invalid shard");
+    const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev_out && (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
+        return bad("tmpt_render_aov: a device output must be 16-byte aligned");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * sizeof(tmpt_aov_pixel);
+    tmpt_aov_pixel* d_out = nullptr;
+    if (dev_out) d_out = out;
+    else if (bytes && hipMalloc(&d_out, bytes) != hipSuccess) return bad("tmpt_render_aov: out of device memory");
+    int rc = render_aov(s, cam, d, d_out, ray_count);
+    if (!rc) rc = check_report(s, "tmpt_render_aov");
+    if (!rc && !dev_out && bytes) {
+        if (hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = (set_error("tmpt_render_aov: readback failed"), -1);
     }
     if (!dev_out && d_out) (void)hipFree(d_out);
     return rc;

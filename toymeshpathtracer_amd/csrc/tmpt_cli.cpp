@@ -1,6 +1,6 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
-//        [--gpus N] [--device D] [--out output.png]
+//        [--gpus N] [--device D] [--out output.png] [--aov PREFIX]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -8,6 +8,10 @@
 // work.  With --gpus N (tmpt_render_multi) the rows
 // are dealt round-robin one at a time (row y to device y % N), one host thread
 // per device, and the tiles are assembled into the frame.
+// --aov PREFIX (one device only): after the frame, the AOV pass (tmpt_render_aov) at the same
+// size and spp on the same device, written as PREFIX_normal.png, PREFIX_direct.png and
+// PREFIX_depth.png.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,11 +27,70 @@ static double now_s()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+static float saturate(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+// The AOV pass on `device` (its own scene, the octree built as for the frame) and its three
+// images, all float32 maps, alpha 255:
+//   PREFIX_normal.png  uint8(saturate(n * 0.5 + 0.5) * 255) per channel
+//   PREFIX_direct.png  grey uint8(saturate(sqrtf(direct)) * 255)
+//   PREFIX_depth.png   grey over the pixels with hits > 0 of d = depth * spp / hits:
+//                      uint8((1 - (d - dmin) / (dmax - dmin)) * 255), dmin / dmax over those
+//                      pixels (dmax == dmin: 255); a pixel without a hit is 0
+static int write_aovs(const char* prefix, const float* tris, int32_t n, const float box[6], const tmpt_camera* cam,
+                      int w, int h, int spp, int device)
+{
+    tmpt_scene* scene = nullptr;
+    if (tmpt_scene_create(tris, n, device, &scene)) return 1;
+    std::vector<tmpt_aov_pixel> rec((size_t)w * h);
+    tmpt_render_desc desc;
+    memset(&desc, 0, sizeof(desc));
+    desc.width = w; desc.height = h; desc.spp = spp; desc.seed_mode = TMPT_SEED_SAMPLE;
+    uint64_t rays = 0;
+    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    if (!rc) rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &rays);
+    tmpt_stats st;
+    if (!rc) rc = tmpt_get_stats(scene, &st);
+    // (a failed call's message survives the destroy: only failures set it)
+    if (tmpt_scene_destroy(scene) && !rc) rc = 1;
+    if (rc) return rc;
+    printf("AOV pass: %.1f K Rays in %.3f ms\n", rays / 1000.0, st.render_ms);
+    const size_t P = rec.size();
+    std::vector<float> depth(P, 0.0f);
+    float dmin = INFINITY, dmax = -INFINITY;
+    for (size_t i = 0; i < P; ++i) {
+        if (rec[i].hits == 0) continue;
+        const float d = rec[i].depth * (float)spp / (float)rec[i].hits;
+        depth[i] = d;
+        dmin = d < dmin ? d : dmin;
+        dmax = d > dmax ? d : dmax;
+    }
+    std::vector<uint8_t> img[3];
+    for (auto& v : img) v.assign(P * 4, 255);
+    for (size_t i = 0; i < P; ++i) {
+        for (int c = 0; c < 3; ++c) {
+            const float m = rec[i].normal[c] * 0.5f;
+            img[0][4 * i + c] = (uint8_t)(saturate(m + 0.5f) * 255.0f);
+        }
+        const uint8_t g = (uint8_t)(saturate(sqrtf(rec[i].direct)) * 255.0f);
+        uint8_t z = 0;
+        if (rec[i].hits != 0) {
+            const float num = depth[i] - dmin, den = dmax - dmin;
+            const float q = num / den;
+            z = dmax == dmin ? (uint8_t)255 : (uint8_t)((1.0f - q) * 255.0f);
+        }
+        for (int c = 0; c < 3; ++c) img[1][4 * i + c] = g, img[2][4 * i + c] = z;
+    }
+    const char* names[3] = {"_normal.png", "_direct.png", "_depth.png"};
+    for (int k = 0; k < 3; ++k)
+        if (tmpt_write_png((std::string(prefix) + names[k]).c_str(), img[k].data(), w, h)) return 1;
+    return 0;
+}
+
 int main(int argc, const char** argv)
 {
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
-               "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png]\n");
+               "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix]\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -39,6 +102,7 @@ int main(int argc, const char** argv)
     const char* obj = argv[4];
     int seed = TMPT_SEED_ROW, engine = TMPT_ENGINE_PERSISTENT, gpus = 1, device = 0;
     const char* out = "output.png";
+    const char* aov = nullptr;
     for (int i = 5; i < argc; ++i) {
         if (!strcmp(argv[i], "--seed") && i + 1 < argc) {
             ++i;
@@ -53,6 +117,7 @@ int main(int argc, const char** argv)
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
+        else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -62,8 +127,9 @@ int main(int argc, const char** argv)
         printf("ERROR: failed to load .obj file\n");
         return 1;
     }
-    int ndev = tmpt_device_count();
     if (gpus < 1) gpus = 1;
+    if (aov && gpus > 1) { printf("ERROR: --aov runs on one device (--gpus 1)\n"); return 1; }
+    int ndev = tmpt_device_count();
     if (device + gpus > ndev) {
         printf("ERROR: %d GPU(s) requested from device %d, %d present\n", gpus, device, ndev);
         return 1;
@@ -92,6 +158,10 @@ int main(int argc, const char** argv)
     printf("Rendered scene at %ix%i,%ispp in %.3f s\n", w, h, spp, dt);
     printf("- %.1f K Rays, %.1f K Rays/s\n", total / 1000.0, total / 1000.0 / dt);
     if (tmpt_write_png(out, image.data(), w, h)) { printf("ERROR: %s\n", tmpt_last_error()); return 1; }
+    if (aov && write_aovs(aov, tris, n, box, &cam, w, h, spp, device)) {
+        printf("ERROR: %s\n", tmpt_last_error());
+        return 1;
+    }
     tmpt_free(tris);
     return 0;
 }

@@ -227,6 +227,7 @@ struct Options {
                               // from 3 pixels per 4-wave lane; 4 or 5)
     int redo_inline = 1;      // test hook: 0 = the deferring kernel's waves leave every dropped sample
                               // to the k_redo launch (its fallback) instead of tracing them in their tail
+    int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
 };
 int options_parse(Options& o, const char* text, bool allow_build);
 int options_set(Options& o, const char* key, double value, bool allow_build);

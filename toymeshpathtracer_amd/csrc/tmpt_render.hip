@@ -23,42 +23,9 @@
 #include <cmath>
 #include <vector>
 
-#include "tmpt.h"
-#include "tmpt_internal.h"
-#include "tmpt_traverse.h"
+#include "tmpt_render.h"
 
 namespace tmpt {
-
-struct RenderArgs {
-    Camera cam;
-    int32_t W, H, spp, seed_mode, band_rows, shard, nshards, tile_rows;
-    float invW, invH, spp_recip;
-    int64_t slots;  // tile_rows * W
-    // progressive spp: samples [smp_begin, smp_end) this call; prog = per-pixel
-    // {colour sum, rng} carried between calls (null: one full pass)
-    int32_t smp_begin, smp_end;
-    float out_recip;  // 1/spp for the final pass, 1/smp_end for a preview
-    float4* prog;
-    // sample seeding (TMPT_SEED_SAMPLE): jump tables of sample_seed (null in the
-    // other modes); a lane's run of samples ends where smp & bmask == 0 (its
-    // block of the persistent engine; 2047 = never inside 1..1024)
-    const uint32_t* jt;
-    uint32_t bmask;
-    // row seeding in the megakernel: rows per wave (lanes 0..row_lanes-1 each
-    // run one row's chain; the rest of the wave idles)
-    int32_t row_lanes;
-    // camera rays take the reference's root box test first (SceneView::oct
-    // set and the lens may lie outside the root box: render() decides)
-    int32_t root_check;
-};
-
-__device__ __forceinline__ int tile_row_to_y(const RenderArgs& a, int lr)
-{
-    int lb = lr / a.band_rows, r = lr - lb * a.band_rows;
-    return (lb * a.nshards + a.shard) * a.band_rows + r;
-}
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // wave64 ballot straight from the predicate (HIP's __ballot widens the bool to
 // an int and compares it again: two extra VALU per call in the hot loops)
@@ -73,13 +40,6 @@ __device__ __forceinline__ uint64_t stamp()
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     __builtin_amdgcn_sched_barrier(0);
     return t;
-}
-
-// wave64 sum of a 32-bit value (all lanes must call)
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
-    return v;
 }
 
 // Compacted append: every lane of the wave calls; lanes with pred get
@@ -2433,13 +2393,12 @@ __global__ void __launch_bounds__(256) k_rs_count(RowSpec rs, unsigned long long
 }
 
 // ============================================================ host side
+// (kBlk, kSL and the helpers up to make_args: shared with tmpt_aov.hip, tmpt_render.h)
 namespace {
-
-constexpr int kBlk = 256;
-constexpr int kSL = 16;  // LDS stack entries per lane
 // the 5-wave path kernels (OCC 5): 30 KB of LDS per block -- a 12-entry LDS
 // stack, the scattered ray's direction only, kTopNodes5 top nodes
 constexpr int kPathSL5 = 12;
+}  // namespace
 
 int occupancy_grid(const void* fn, int block, size_t dyn_lds, int device)
 {
@@ -2483,6 +2442,8 @@ SceneView view(const Scene& s)
     }
     return v;
 }
+
+namespace {
 
 // Columns of M^n, M the xorshift32 step as a GF(2) 32x32 matrix (maths.cpp:5-13):
 // column j = image of bit j.
@@ -2533,8 +2494,6 @@ void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& ta
 // sample_seed's byte tables for samples [0, spp): J_s = M^(s * kSampleStride)
 void sample_jump_tables(int32_t spp, std::vector<uint32_t>& tab) { jump_tables(kSampleStride, spp, tab); }
 
-namespace {
-
 RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d)
 {
     RenderArgs a;
@@ -2569,6 +2528,7 @@ RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d)
     return a;
 }
 
+namespace {
 
 template <bool ROW, bool COUNT>
 int launch_mega(Scene& s, const RenderArgs& a, uint32_t* out, unsigned long long* counters)
@@ -3981,6 +3941,71 @@ int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float 
     return 0;
 }
 
+int ensure_sample_tables(Scene& s, int32_t spp, const char* what)
+{
+    if (s.jt_spp >= spp) return 0;
+    std::vector<uint32_t> tab;
+    sample_jump_tables(spp, tab);
+    uint32_t* nt = nullptr;
+    TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
+    if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(nt);
+        set_error(std::string(what) + ": jump table upload failed");
+        return -1;
+    }
+    if (s.jt) (void)hipFree(s.jt);
+    s.jt = nt;
+    s.jt_spp = spp;
+    return 0;
+}
+
+int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what)
+{
+    if (!(d->flags & TMPT_FLAG_WAIT_STREAM)) return 0;  // order after the caller's stream (tmpt.h)
+    if (!s.wait_ev) TMPT_HIP(hipEventCreateWithFlags(&s.wait_ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(s.wait_ev, reinterpret_cast<hipStream_t>(static_cast<uintptr_t>(d->wait_stream)));
+    if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, s.wait_ev, 0);
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": wait_stream: " + hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+// camera rays take the reference's root box test unless the whole lens
+// (origin +- lens_radius along u and v) lies inside the root box by more
+// than tMin and a rounding margin: a ray from inside always passes it
+int32_t camera_root_check(const Scene& s, const Camera& cam)
+{
+    if (!(s.oct && s.opt.tie_rule == 0)) return 0;
+    const float o[3] = {cam.origin.x, cam.origin.y, cam.origin.z};
+    const float uu[3] = {cam.u.x, cam.u.y, cam.u.z}, vv[3] = {cam.v.x, cam.v.y, cam.v.z};
+    bool inside = true;
+    for (int c = 0; c < 3; ++c) {
+        const double r = (double)cam.lens_radius * (std::fabs((double)uu[c]) + std::fabs((double)vv[c]));
+        const double m = 2.0 * kMinT + 1e-4 * ((double)s.oct_hi[c] - (double)s.oct_lo[c]);
+        inside = inside && (double)o[c] - r > (double)s.oct_lo[c] + m && (double)o[c] + r < (double)s.oct_hi[c] - m;
+    }
+    return inside ? 0 : 1;
+}
+
+void reset_render_stats(Scene& s)
+{
+    s.extend_ms = s.shadow_ms = 0;
+    s.extend_rays = s.shadow_rays = s.node_visits = s.tri_tests = 0;
+    s.shadow_node_visits = s.shadow_tri_tests = 0;
+    s.extend_launches = s.shadow_launches = s.iterations = 0;
+    s.row_engine = 0;
+    s.stream_fallbacks = 0;
+    s.chain_pixels = 0;
+    s.redo_samples = 0;
+    s.redo_late = 0;
+    s.redo_launches = 0;
+    s.redo_ms = 0.0;
+    s.redo_rays = 0;
+    s.tie_path = 0;
+}
+
 int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* d_out,
            uint64_t* ray_count)
 {
@@ -4015,46 +4040,12 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
         s.prog_key[6] = -1;  // valid again only once this pass completes
     }
     if (a.seed_mode == TMPT_SEED_SAMPLE) {  // jump tables of sample_seed, grown to spp
-        if (s.jt_spp < a.spp) {
-            std::vector<uint32_t> tab;
-            sample_jump_tables(a.spp, tab);
-            uint32_t* nt = nullptr;
-            TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-            if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(nt);
-                set_error("tmpt_render: jump table upload failed");
-                return -1;
-            }
-            if (s.jt) (void)hipFree(s.jt);
-            s.jt = nt;
-            s.jt_spp = a.spp;
-        }
+        if (int rc = ensure_sample_tables(s, a.spp, "tmpt_render")) return rc;
         a.jt = s.jt;
     }
-    if (d->flags & TMPT_FLAG_WAIT_STREAM) {  // order after the caller's stream (tmpt.h)
-        if (!s.wait_ev) TMPT_HIP(hipEventCreateWithFlags(&s.wait_ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(s.wait_ev, reinterpret_cast<hipStream_t>(static_cast<uintptr_t>(d->wait_stream)));
-        if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, s.wait_ev, 0);
-        if (e != hipSuccess) {
-            set_error(std::string("tmpt_render: wait_stream: ") + hipGetErrorString(e));
-            return -1;
-        }
-    }
+    if (int rc = wait_caller_stream(s, d, "tmpt_render")) return rc;
     if (ensure_counters(s)) return -1;
-    // camera rays take the reference's root box test unless the whole lens
-    // (origin +- lens_radius along u and v) lies inside the root box by more
-    // than tMin and a rounding margin: a ray from inside always passes it
-    if (s.oct && s.opt.tie_rule == 0) {
-        const float o[3] = {a.cam.origin.x, a.cam.origin.y, a.cam.origin.z};
-        const float uu[3] = {a.cam.u.x, a.cam.u.y, a.cam.u.z}, vv[3] = {a.cam.v.x, a.cam.v.y, a.cam.v.z};
-        bool inside = true;
-        for (int c = 0; c < 3; ++c) {
-            const double r = (double)a.cam.lens_radius * (std::fabs((double)uu[c]) + std::fabs((double)vv[c]));
-            const double m = 2.0 * kMinT + 1e-4 * ((double)s.oct_hi[c] - (double)s.oct_lo[c]);
-            inside = inside && (double)o[c] - r > (double)s.oct_lo[c] + m && (double)o[c] + r < (double)s.oct_hi[c] - m;
-        }
-        a.root_check = inside ? 0 : 1;
-    }
+    a.root_check = camera_root_check(s, a.cam);
     unsigned long long* d_counters = s.counters;
     TMPT_HIP(hipMemsetAsync(d_counters, 0, kRenderCounters * sizeof(unsigned long long), s.stream));
     hipEvent_t e0 = s.render_ev[0], e1 = s.render_ev[1];
@@ -4071,19 +4062,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
         set_error("tmpt_render: progressive spp needs the persistent engine");
         return -22;
     }
-    s.extend_ms = s.shadow_ms = 0;
-    s.extend_rays = s.shadow_rays = s.node_visits = s.tri_tests = 0;
-    s.shadow_node_visits = s.shadow_tri_tests = 0;
-    s.extend_launches = s.shadow_launches = s.iterations = 0;
-    s.row_engine = 0;
-    s.stream_fallbacks = 0;
-    s.chain_pixels = 0;
-    s.redo_samples = 0;
-    s.redo_late = 0;
-    s.redo_launches = 0;
-    s.redo_ms = 0.0;
-    s.redo_rays = 0;
-    s.tie_path = 0;
+    reset_render_stats(s);
     if (a.slots > 0) {
         if (wave) rc = render_wavefront(s, a, d_out, count);
         else if (persistent) rc = render_persistent(s, a, d_out, count, d_counters);
