@@ -284,6 +284,11 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    stack and 80 LDS top nodes, 30 KB of LDS per block and 96 VGPRs per lane).  Auto:
  *                    5 in sample seeding and the row engine's re-trace, 5 in pixel seeding from 3 pixels
  *                    per 4-wave lane
+ *   top_walk         persistent path kernels: at the end of a shading round, up to top_walk node
+ *                    rounds for the lanes standing on a BVH node of the block's LDS copy of the top
+ *                    levels (every query starts there), with no global load in them (-1 = the
+ *                    seeding's measured default, 0 = off, 1..8 = the round cap); each lane's
+ *                    traversal order, and so the image and every count, is the same for every value
  *   redo_cap         test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown
  *   redo_inline      test hook (1): 0 leaves every dropped sample to the second launch

@@ -172,7 +172,9 @@ constexpr float kTfarSlack = 1.00001f;
 constexpr int kStackTotal = 128;
 
 constexpr int kRowSpecMaxGroups = 8;  // speculative row engine: row groups (streams)
-constexpr int kRenderCounters = 32;   // ray / visit / round counters of one render
+constexpr int kRenderCounters = 48;   // ray / visit / round counters of one render
+constexpr int kTopCounter = 32;       // [32..41] k_path's top-level visit and top-walk round statistics
+                                      // (instrumented instantiations only)
 constexpr int kTieCounter = 24;       // [24] tied queries re-answered over the octree, [25] root-box misses,
                                       // [30] crack / flat-triangle queries re-answered over it (ties[6])
 constexpr int kCrackCounter = 30;
@@ -227,6 +229,8 @@ struct Options {
                               // from 3 pixels per 4-wave lane; 4 or 5)
     int redo_inline = 1;      // test hook: 0 = the deferring kernel's waves leave every dropped sample
                               // to the k_redo launch (its fallback) instead of tracing them in their tail
+    int top_walk = -1;        // path kernels: node rounds over the LDS-cached top levels at the end of a
+                              // shading round, with no global load in them (-1 = per seeding, 0 off, 1..8)
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
 };
 int options_parse(Options& o, const char* text, bool allow_build);

@@ -960,6 +960,11 @@ struct PathCtl {
     // decides) -- the finished shadow queries are checked as closest hits are
     // (octree_flag), so HELP and DEFER are off then.
     uint32_t oct_shadow;
+    // Top-walk rounds (option top_walk): at the end of a shading round, up to
+    // this many wave-uniform node rounds for the lanes standing on a node of
+    // the block's LDS copy of the top levels -- every query starts at node 0
+    // -- with no global load in them (trav_step4q2_mixed TOPONLY).  0 = off.
+    uint32_t top_walk;
 };
 
 constexpr uint32_t kSimdKeys = 8u * 8u * 2u * 16u * 4u;  // XCC x SE x SH x CU x SIMD (HW_ID fields)
@@ -1277,6 +1282,16 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     uint64_t pt_shade = 0, pt_node = 0, pt_leaf = 0, pt_t = PROF ? stamp() : 0;
     // PROF >= 2: the shading round split (pixel fetch, hit/finish shading, camera, query set-up)
     uint64_t ps_fetch = 0, ps_shade = 0, ps_cam = 0, ps_start = 0;
+    // Top-walk rounds (pc.top_walk) and the top levels' share of the node
+    // rounds, wave-uniform.  COUNT: node lane-steps on an LDS-resident node
+    // (tv_n), those of them before the query's first other step (tv_lead,
+    // `lead` per lane), voted node rounds with lanes on both sides of ntop /
+    // on the LDS side only (tv_mix, tv_only).  COUNT or PROF: top-walk rounds
+    // and their lanes (tw_r, tw_l).  PROF: cycles in top-walk rounds (pt_top),
+    // voted node rounds and their cycles with a global-side lane (pn_g, pt_node_g)
+    uint64_t tv_n = 0, tv_lead = 0, tv_mix = 0, tv_only = 0, tw_r = 0, tw_l = 0;
+    uint64_t pt_top = 0, pt_node_g = 0, pn_g = 0, pn_all = 0;
+    bool lead = false;
     f3 col = mk(0.0f, 0.0f, 0.0f);
     TravRay r;
     TravState ts;
@@ -1769,6 +1784,55 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 }
             }
             if (PROF >= 2) ps_start += stamp() - ps_t;
+            if (COUNT && start) lead = true;
+            // Top-walk rounds (pc.top_walk): every query starts at node 0 and
+            // its first visits are nodes of the LDS copy, but in a voted node
+            // round some other lane nearly always stands on a global node, so
+            // those visits wait out the global loads' latency with it.  Here
+            // the lanes on an LDS-resident node -- the queries just started
+            // and any lane already traversing that stands on one -- take up to
+            // top_walk node rounds that hold no global load at all.  The same
+            // step on the same state in the same order per lane: every answer,
+            // tie flag and count is what the voted rounds alone give.  No
+            // vote: every stepping lane is at a node.
+            if (pc.top_walk) {
+                uint64_t tw_t = 0;
+                if (PROF) {
+                    tw_t = stamp();
+                    pt_shade += tw_t - pt_t;
+                }
+                for (uint32_t k = 0; k < pc.top_walk; ++k) {
+                    const bool top = in_query && ts.node >= 0 && (uint32_t)ts.node < st.ntop;
+                    const uint64_t tm = wballot(top);
+                    if (tm == 0) break;
+                    if (COUNT || PROF) {
+                        ++tw_r;
+                        tw_l += (uint64_t)__popcll(tm);
+                    }
+                    if (COUNT) {
+                        tv_n += (uint64_t)__popcll(tm);
+                        tv_lead += (uint64_t)__popcll(wballot(top && lead));
+                    }
+                    if (top) {
+                        bool done;
+                        if (!COUNT) {
+                            done = trav_step4q2_mixed<false, BLOCK, SL, true, 1, SOA, false, FLAG, true>(sv, r, qany, ts, st,
+                                                                                                        cnt);
+                        } else {
+                            TravCount c1;
+                            done = trav_step4q2_mixed<COUNT, BLOCK, SL, true, 1, SOA, false, FLAG, true>(sv, r, qany, ts, st,
+                                                                                                        c1);
+                            (qany ? cnt_s : cnt).nodes += c1.nodes;
+                        }
+                        if (done) in_query = false;
+                        if ((kFull && pc.cost_out) || dp0 > 0.0f) ++psteps;
+                    }
+                }
+                if (PROF) {
+                    pt_t = stamp();
+                    pt_top += pt_t - tw_t;
+                }
+            }
         }
         if (dp0 > 0.0f) {  // longest remaining traversal work first (wave-uniform)
             float rem = 0.0f;
@@ -1825,6 +1889,15 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 if (!leaf_round) { ++rs_nr; rs_nl += (uint64_t)__popcll(at_node); }
                 if (leaf_round) { ++rs_lr; rs_ll += (uint64_t)__popcll(at_leaf); }
             }
+            uint64_t top_m = 0;  // COUNT / PROF: this node round's lanes on an LDS-resident node
+            if ((COUNT || PROF) && !leaf_round) top_m = at_node & wballot(ts.node >= 0 && (uint32_t)ts.node < st.ntop);
+            if (COUNT) {
+                tv_n += (uint64_t)__popcll(top_m);
+                tv_lead += (uint64_t)__popcll(top_m & wballot(lead));
+                if (top_m != 0) ++((at_node & ~top_m) != 0 ? tv_mix : tv_only);
+                // the lane's first step that is not on an LDS-resident node ends its leading run
+                if (in_query && (ts.node < 0) == leaf_round && !((top_m >> lane_id()) & 1ull)) lead = false;
+            }
             if (!COUNT) {
                 // voted round: the kind is wave-uniform, so only its code runs
                 // (a scalar branch instead of exec-mask splits around both)
@@ -1848,6 +1921,13 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
             if (PROF) {
                 const uint64_t t = stamp();
                 (leaf_round ? pt_leaf : pt_node) += t - pt_t;
+                if (!leaf_round) {
+                    ++pn_all;
+                    if ((at_node & ~top_m) != 0) {
+                        ++pn_g;
+                        pt_node_g += t - pt_t;
+                    }
+                }
                 pt_t = t;
             }
         }
@@ -1965,6 +2045,22 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
             atomicAdd(&counters[17], (unsigned long long)ps_shade);
             atomicAdd(&counters[18], (unsigned long long)ps_cam);
             atomicAdd(&counters[19], (unsigned long long)ps_start);
+        }
+        if (COUNT) {
+            atomicAdd(&counters[kTopCounter], (unsigned long long)tv_n);
+            atomicAdd(&counters[kTopCounter + 1], (unsigned long long)tv_lead);
+            atomicAdd(&counters[kTopCounter + 2], (unsigned long long)tv_mix);
+            atomicAdd(&counters[kTopCounter + 3], (unsigned long long)tv_only);
+        }
+        if (COUNT || PROF) {
+            atomicAdd(&counters[kTopCounter + 4], (unsigned long long)tw_r);
+            atomicAdd(&counters[kTopCounter + 5], (unsigned long long)tw_l);
+        }
+        if (PROF) {
+            atomicAdd(&counters[kTopCounter + 6], (unsigned long long)pt_top);
+            atomicAdd(&counters[kTopCounter + 7], (unsigned long long)pt_node_g);
+            atomicAdd(&counters[kTopCounter + 8], (unsigned long long)pn_g);
+            atomicAdd(&counters[kTopCounter + 9], (unsigned long long)pn_all);
         }
     }
 }
@@ -2737,6 +2833,24 @@ __global__ void __launch_bounds__(256) k_resolve_chains(PixelChains ch, const fl
     out[p] = pack_pixel(col, spp_recip);
 }
 
+// PathCtl::top_walk from option top_walk: the round cap, or (-1, auto) the
+// seeding's measured default.  seeding: 0 sample, 1 pixel, 2 row (both row
+// engines and the pixel chains).  Bench frame, same box, parent / cap 0 / 2 /
+// 3 / 4 / 5 / 6 / 8 (profiles/r07_top_walk/): sample
+// seeding, k_path ms, N=1 171.9 / 172.3 / 170.5 / 169.3 / 168.7 / 171.3 /
+// 174.3 / 178.3, 1/8 shard 24.2 / 24.0 / 23.9 / 23.7 / 23.6 / 24.0 / 24.4 /
+// 24.8 -- the queries of a shading round leave the LDS copy after 3.7 visits,
+// and past the fourth round a few lanes hold the whole wave; row seeding,
+// whole render, 1814 / 1830 / 1815 / - / 1803 / - / - / 1886 ms; pixel
+// seeding, k_path ms, cap 0 / 2 / 4 / 8: N=1 192.6 / 193.9 / 194.8 / 204.8,
+// 1/8 35.3 / 35.6 / 35.0 / 36.7 -- no cap gains there, so off.
+constexpr int kTopWalkSample = 4, kTopWalkPixel = 0, kTopWalkRow = 4;
+static uint32_t top_walk_cap(const Options& o, int seeding)
+{
+    if (o.top_walk >= 0) return (uint32_t)o.top_walk;
+    return (uint32_t)(seeding == 0 ? kTopWalkSample : seeding == 1 ? kTopWalkPixel : kTopWalkRow);
+}
+
 // PathCtl::oct_shadow: whether a shadow query's answer can need the octree --
 // a triangle lying flat on one of its planes, or a light direction that can
 // drift along a crack (octree_crack's test at the smallest t a hit can have,
@@ -2981,6 +3095,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     memset(&pc, 0, sizeof(pc));
     pc.heads = heads;
     pc.oct_shadow = oct_shadow;
+    pc.top_walk = top_walk_cap(o, a.jt ? 0 : 1);
     pc.P = P;
     pc.nblk = nblk;
     pc.blk = blk;
@@ -3024,9 +3139,9 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     }
     pc.chunk = std::min<uint32_t>(kChunk, pc.lane_cap);
     pc.nchunks = (uint32_t)((P + pc.chunk - 1) / pc.chunk);
-    auto final_launch = [&](const RenderArgs& af) -> int {
+    auto final_launch = [&](const RenderArgs& af, int grid_final) -> int {
         TMPT_HIP(hipEventRecord(s.path_ev[2], s.stream));
-        fn<<<grid, kBlk, 0, s.stream>>>(view(s), af, pc, d_out, (uint32_t*)s.ws, d_counters);
+        fn<<<grid_final, kBlk, 0, s.stream>>>(view(s), af, pc, d_out, (uint32_t*)s.ws, d_counters);
         TMPT_HIP(hipGetLastError());
         TMPT_HIP(hipEventRecord(s.path_ev[3], s.stream));
         return 0;
@@ -3137,6 +3252,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         return 0;
     }
     s.tie_path = s.oct_view && o.tie_rule == 0 ? 1 : 0;  // pixel seeding answers in the main loop
+    // both pixel launches run `fn`: their grid is its own co-resident block
+    // count (`grid` above came from the instantiations the choice started from)
+    const int grid_px = occupancy_grid((const void*)fn, kBlk, 0, s.device);
+    if ((size_t)grid_px * kBlk * (kStackTotal - (waves5p ? kPathSL5 : kPathSL)) > ovf_words) {
+        set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
+        return -1;
+    }
     uint32_t* base = heads + head_words;
     float4* state = reinterpret_cast<float4*>(base);  // P x {colour sum, rng}
     uint32_t* cost = base + 4 * (size_t)P;
@@ -3152,7 +3274,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     a1.prog = state;
     pc.cost_out = cost;
     TMPT_HIP(hipEventRecord(s.path_ev[0], s.stream));
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a1, pc, d_out, (uint32_t*)s.ws, d_counters);
+    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a1, pc, d_out, (uint32_t*)s.ws, d_counters);
     TMPT_HIP(hipGetLastError());
     TMPT_HIP(hipEventRecord(s.path_ev[1], s.stream));
     k_order_keys<<<(unsigned)((P + 255) / 256), 256, 0, s.stream>>>(cost, a.W, a.tile_rows, keys, vals);
@@ -3203,7 +3325,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, s.device) != hipSuccess ||
             dev_cus < 1)
             dev_cus = 256;
-        const uint32_t per_cu = (uint32_t)std::max(1, grid / dev_cus);  // blocks per CU
+        const uint32_t per_cu = (uint32_t)std::max(1, grid_px / dev_cus);  // blocks per CU
         pc.simd_reg = simd_reg;
         pc.nsimd = (uint32_t)dev_cus * 4u;
         pc.wps = per_cu * (uint32_t)(kBlk / 64) / 4u;
@@ -3230,7 +3352,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         pc.dprio[2] = 0.105f;
         pc.dprio_cost = cost;
     }
-    if (final_launch(a2)) return -1;
+    if (final_launch(a2, grid_px)) return -1;
     s.path_launches = 2;
     return 0;
 }
@@ -3438,6 +3560,7 @@ int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned lo
     pc.chunk = kChunk;
     pc.rs_noshadow = 1;
     pc.oct_shadow = oct_shadow_check(s);
+    pc.top_walk = top_walk_cap(o, 2);
     pc.rss = S;
     fn4<<<grid, kBlk, 0, s.stream>>>(view(s), as, pc, d_out, ovf, spec_ctr);
     TMPT_HIP(hipGetLastError());
@@ -3733,6 +3856,7 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
         q.pc.p_dev = q.rs.total;
         q.pc.rs_noshadow = noshadow ? 1 : 0;
         q.pc.oct_shadow = oct_shadow_check(s);
+        q.pc.top_walk = top_walk_cap(o, 2);
         q.rs.lpix = lpix;
         q.rs.lstate = lstate;
         q.rs.lslot = lslot;
@@ -4195,6 +4319,26 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
                     "(%.1f wanting, %.1f traversing)\n",
                     c[6], c[6] ? (double)c[7] / c[6] : 0.0, c[8], c[8] ? (double)c[9] / c[8] : 0.0,
                     c[10], c[10] ? (double)c[11] / c[10] : 0.0, c[10] ? (double)c[12] / c[10] : 0.0);
+        {  // the top levels' share (k_path tv_*, tw_*, pt_top, pt_node_g)
+            const unsigned long long* t = c + kTopCounter;
+            const unsigned long long nv = c[1] + c[4];
+            if (count && getenv("TMPT_ROUND_LOG") && nv)
+                fprintf(stderr,
+                        "k_path top levels: %.4f of node lane-steps on an LDS node, %.4f of those before the query's "
+                        "first other step (%.2f per query); voted node rounds with LDS lanes %.4f, of them mixed "
+                        "with global lanes %.4f; top-walk rounds %llu (%.1f lanes)\n",
+                        (double)t[0] / nv, t[0] ? (double)t[1] / t[0] : 0.0, (double)t[1] / (double)c[0],
+                        c[6] ? (double)(t[2] + t[3]) / c[6] : 0.0, t[2] + t[3] ? (double)t[2] / (t[2] + t[3]) : 0.0,
+                        t[4], t[4] ? (double)t[5] / t[4] : 0.0);
+            if (t[9])
+                fprintf(stderr,
+                        "  node rounds with a global-side lane: %llu of %llu, %.0f cycles each; without: %.0f cycles "
+                        "each; top-walk rounds %llu (%.1f lanes), %.0f cycles each, %.2f%% of wave time\n",
+                        t[8], t[9], t[8] ? (double)t[7] / t[8] : 0.0,
+                        t[9] > t[8] ? (double)(c[14] - t[7]) / (t[9] - t[8]) : 0.0, t[4],
+                        t[4] ? (double)t[5] / t[4] : 0.0, t[4] ? (double)t[6] / t[4] : 0.0,
+                        100.0 * t[6] / (double)(c[13] + c[14] + c[15] + t[6]));
+        }
 #endif
     } else if (rowspec) {
         s.extend_ms = ms;

@@ -214,8 +214,10 @@ __device__ __forceinline__ void trav_init(TravState& ts, float tmax)
 // per-ray ranges): the far-distance slack is applied by magnitude, so it
 // widens a box's interval for negative distances too (kTfarSlack alone would
 // shrink it there); the path engines' range kMinT..kMaxT never needs it.
+// TOPONLY (with KIND 1): the caller guarantees ts.node < st.ntop, so only the
+// LDS read of the node is emitted, no global load (k_path's top-walk rounds).
 template <bool COUNT, int BLOCK, int SL, bool TOPC = false, int KIND = 0, bool SOA = false, bool NEG = false,
-          bool FLAG = false>
+          bool FLAG = false, bool TOPONLY = false>
 __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const TravRay& r, bool any,
                                                    TravState& ts, TravStack<BLOCK, SL>& st,
                                                    TravCount& cnt, float tlo = 0.0f, float tmin = kMinT,
@@ -228,12 +230,12 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
         // 32-bit byte offset off an SGPR base: one VALU for the address
         uint4 A, B, C;
         int4 L;
-        if (SOA && (!TOPC || (uint32_t)ts.node >= st.ntop)) {  // four planes: 16 + 16 + 8 + 16 B
+        if (!TOPONLY && SOA && (!TOPC || (uint32_t)ts.node >= st.ntop)) {  // four planes: 16 + 16 + 8 + 16 B
             const uint32_t k = (uint32_t)ts.node;
             A = sv.soa.na[k], B = sv.soa.nb[k], L = sv.soa.nd[k];
             const uint2 c2 = sv.soa.nc[k];
             C = make_uint4(c2.x, c2.y, 0u, 0u);
-        } else if (!TOPC || (uint32_t)ts.node >= st.ntop) {
+        } else if (!TOPONLY && (!TOPC || (uint32_t)ts.node >= st.ntop)) {
             const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(sv.nodes4) +
                                                             ((uint32_t)ts.node << 6));
             A = p[0], B = p[1], C = p[2];
