@@ -289,6 +289,12 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    levels (every query starts there), with no global load in them (-1 = the
  *                    seeding's measured default, 0 = off, 1..8 = the round cap); each lane's
  *                    traversal order, and so the image and every count, is the same for every value
+ *   shadow_order     any-hit (shadow) queries, every engine: the order in which a BVH node's children
+ *                    that the ray meets are visited (-1 = the measured default: 2, in row seeding 0; 0 = nearest entry
+ *                    first, as closest-hit queries always go; 1 = longest overlap tf - tn first;
+ *                    2 = largest exit distance first, by the key tn - 1024 tf); only the hit / miss
+ *                    bit of such a query is used, so the image and the ray counts are the same for
+ *                    every value, and closest-hit queries do not change at all
  *   redo_cap         test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown
  *   redo_inline      test hook (1): 0 leaves every dropped sample to the second launch

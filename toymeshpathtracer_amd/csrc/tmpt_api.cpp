@@ -129,6 +129,7 @@ const OptionDef kOptions[] = {
     {"redo_lanes", false, 1, 64, &Options::redo_lanes, nullptr, nullptr},
     {"path_waves", false, 0, 5, &Options::path_waves, nullptr, nullptr},
     {"top_walk", false, -1, 8, &Options::top_walk, nullptr, nullptr},
+    {"shadow_order", false, -1, 2, &Options::shadow_order, nullptr, nullptr},
     {"rowspec", false, 0, 1, &Options::rowspec, nullptr, nullptr},
     {"rowspec_wmax", false, 0, 16384, &Options::rowspec_wmax, nullptr, nullptr},
     {"rowspec_windows", false, 0, 32, &Options::rowspec_windows, nullptr, nullptr},

@@ -171,6 +171,11 @@ constexpr float kTfarSlack = 1.00001f;
 // exceed kStackTotal (DESIGN.md "Traversal").
 constexpr int kStackTotal = 128;
 
+// Option shadow_order's default (-1) in sample and pixel seeding and for the
+// batched queries: largest exit first ("The walk over
+// the same tree"); row seeding keeps nearest first (tmpt_render.hip view()).
+constexpr int kShadowOrderDefault = 2;
+
 constexpr int kRowSpecMaxGroups = 8;  // speculative row engine: row groups (streams)
 constexpr int kRenderCounters = 48;   // ray / visit / round counters of one render
 constexpr int kTopCounter = 32;       // [32..41] k_path's top-level visit and top-walk round statistics
@@ -231,6 +236,8 @@ struct Options {
                               // to the k_redo launch (its fallback) instead of tracing them in their tail
     int top_walk = -1;        // path kernels: node rounds over the LDS-cached top levels at the end of a
                               // shading round, with no global load in them (-1 = per seeding, 0 off, 1..8)
+    int shadow_order = -1;    // any-hit queries: the order a node's children are visited in (-1 = default,
+                              // 0 nearest entry first, 1 longest overlap tf - tn first, 2 largest exit tf first)
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
 };
 int options_parse(Options& o, const char* text, bool allow_build);
@@ -299,6 +306,7 @@ struct Scene {
     int64_t redo_late = 0;   // of them, left by the launch's tail to the k_redo launch
     int32_t redo_launches = 0;  // k_redo launches of the last render
     int32_t tie_path = 0;       // tmpt_stats.tie_path of the last render
+    bool row_render = false;    // the render in progress is row-seeded (view(): shadow_order's default)
     double redo_ms = 0.0;       // and their time (not in extend_ms)
     uint64_t redo_rays = 0;     // and their rays (in the render's count)
     // speculative row seeding (tmpt_render.hip render_rowspec): jump tables

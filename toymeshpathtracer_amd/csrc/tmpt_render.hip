@@ -2519,10 +2519,25 @@ int ensure_ws(Scene& s, size_t bytes)
     return 0;
 }
 
+// SceneView::any_w from option shadow_order: the weight of a child's exit
+// distance tf in an any-hit lane's sort key tn + w * tf.  0: nearest first;
+// -1: tn - tf, the longest overlap first; -1024: the exit distance decides and
+// the entry distance only breaks near-ties.
+// Default (-1), from the same-box A/B per seeding mode:
+// largest exit first in sample and pixel seeding and the batched queries; in
+// row seeding, where no order moves the whole render by more than its noise,
+// the old walk.
+static float shadow_order_weight(const Options& o, bool row)
+{
+    const int order = o.shadow_order >= 0 ? o.shadow_order : row ? 0 : kShadowOrderDefault;
+    return order == 0 ? 0.0f : order == 1 ? -1.0f : -1024.0f;
+}
+
 SceneView view(const Scene& s)
 {
     SceneView v{s.nodes4, s.tri_pre, s.tri_orig, s.n, s.n_nodes4};
     v.soa = s.soa;
+    v.any_w = shadow_order_weight(s.opt, s.row_render);
 #ifdef TMPT_CHECK
     v.chk = s.chk;
     // TMPT_CHECK_SELFTEST=1 (the report's own test, tests/test_gpu_check.py):
@@ -4038,6 +4053,7 @@ int check_report(Scene& s, const char* what)
 int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
                     float* d_hits, int32_t* d_ids)
 {
+    s.row_render = false;
     if (ensure_counters(s)) return -1;
     TMPT_HIP(hipMemsetAsync(s.ties, 0, 2 * sizeof(unsigned long long), s.stream));
     TMPT_HIP(hipMemsetAsync(s.counters + kCrackCounter, 0, sizeof(unsigned long long), s.stream));
@@ -4135,6 +4151,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
 {
     RenderArgs a = make_args(cam, d);
     bool count = (d->flags & TMPT_FLAG_COUNT_VISITS) != 0;
+    s.row_render = d->seed_mode == TMPT_SEED_ROW;  // view(): shadow_order's default
     // progressive spp: keep per-pixel state for the shard between calls
     const bool progressive = a.smp_begin > 0 || a.smp_end < a.spp;
     if (progressive) {

@@ -145,6 +145,10 @@ struct SceneView {
     // build option layout=soa (tmpt_internal.h SoaScene): the same nodes and
     // triangle records as planes, read by the SOA instantiations
     SoaScene soa;
+    // any-hit child order (option shadow_order, shadow_order_weight): an
+    // any-hit lane sorts a node's children by tn + any_w * tf instead of tn
+    // (0: nearest first, as closest-hit lanes always do)
+    float any_w = 0.0f;
 #ifdef TMPT_CHECK
     uint32_t* chk = nullptr;  // Scene::chk (tmpt_internal.h kChk*)
 #endif
@@ -198,7 +202,9 @@ __device__ __forceinline__ void trav_init(TravState& ts, float tmax)
 // v_cndmask per plane dword), t = q * (2^e/d) + fma(origin, 1/d, -o/d) by
 // packed fma over child pairs, no per-child min/max and no mask test (empty
 // slots carry an inverted box and link to the null leaf); the nearest hit
-// child is next, the others are pushed pairwise-ordered.  Leaf: its triangles'
+// child is next, the others are pushed pairwise-ordered ("nearest" by the sort
+// key: the entry distance, or for an any-hit lane SceneView::any_w's mix of
+// entry and exit distance).  Leaf: its triangles'
 // Moller-Trumbore tests (bit-exact, maths.cpp:339-380) with t in [tmin, tmax];
 // ties on t keep the lowest triangle index and set bit 0 (the caller settles
 // them, settle_closest).  `any` (run time): stop at the
@@ -279,12 +285,19 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
         const float tfz[4] = {fz01.x, fz01.y, fz23.x, fz23.y};
         float key[4];
         int ch[4] = {L.x, L.y, L.z, L.w};
+        // The sort key of a child that passes: tn for a closest-hit lane (w =
+        // 0: 0 * tf + tn orders as tn does, tf is finite where the child
+        // passes), tn + any_w * tf for an any-hit lane -- with any_w = -1 the
+        // child the ray stays in longest goes first, with a large negative
+        // any_w the child it leaves last.  Only the order of the visits
+        // depends on it; which children pass does not.
+        const float w = any ? sv.any_w : 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float tn = fmaxf(fmaxf(tnx[k], tny[k]), fmaxf(tnz[k], tlo));
             float tf = fminf(fminf(tfx[k], tfy[k]), fminf(tfz[k], ts.bt));
             const float tf_slack = NEG ? tf + fabsf(tf) * (kTfarSlack - 1.0f) : tf * kTfarSlack;
-            key[k] = tn <= tf_slack ? tn : INFINITY;
+            key[k] = tn <= tf_slack ? __builtin_fmaf(w, tf, tn) : INFINITY;
         }
         {  // nearest child next; the others pushed pairwise-ordered only
             const bool s01 = key[1] < key[0], s23 = key[3] < key[2];
