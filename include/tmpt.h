@@ -43,7 +43,10 @@ extern "C" {
                               octree's queries, and whether the deferred form fell back);
                               still 9, additive: tmpt_render_aov and tmpt_aov_pixel (the AOV pass) and
                               the render option aov_group -- no struct above changed, so the version
-                              did not: callers detect the entry point by its symbol */
+                              did not: callers detect the entry point by its symbol;
+                              still 9, additive: tmpt_render_radiance (the float frame of a render),
+                              tmpt_denoise and tmpt_denoise_desc (the AOV-guided a-trous filter) and the
+                              render option denoise_lds -- again no struct above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -182,6 +185,54 @@ typedef struct {
     uint32_t lit;       /* of them, those that added to `direct` */
 } tmpt_aov_pixel;
 
+/* tmpt_denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010)
+ * over a float radiance frame (tmpt_render_radiance), guided by the frame's AOV
+ * records (tmpt_render_aov): `direct` stops it at the hard shadow edges, `normal`
+ * and `depth` at the geometry's.  The arithmetic below IS the contract, as the
+ * renders' is: every operation is float32 and rounds once (no contraction into
+ * fused multiply-adds, `/` and sqrtf correctly rounded), in the order written;
+ * there is no exp or pow in it.  dot(a, b) = (ax*bx + ay*by) + az*bz.
+ *
+ * Guides, per pixel, once per call:
+ *   cov = hits > 0
+ *   nh  = normal * (1.0f / sqrtf(fmaxf(dot(normal, normal), 1e-30f)))   (each component times the scalar)
+ *   zb  = depth * ((float)spp / (float)hits)      the mean hit t; formed and read only where cov
+ *   dl  = direct
+ * Level L = 0 .. levels-1, stride s = 1 << L; level 0 reads rgba32f_in, level L > 0
+ * the output of level L-1.  For pixel p = (x, y), with h = {1/16, 1/4, 3/8, 1/4, 1/16}:
+ *   wsum = 0, csum = {0, 0, 0}
+ *   for j = -2 .. 2 (outer), for i = -2 .. 2 (inner): the tap q = p + s * (i, j)
+ *     q outside the frame: skipped;  cov_q != cov_p: skipped
+ *     i == 0 and j == 0:  w = h[2] * h[2]
+ *     else                w = h[i+2] * h[j+2], and if cov_p then, in this order,
+ *       w = w * wn   c = fmaxf(0.0f, dot(nh_p, nh_q)), then normal_exp times c = c * c;  wn = c
+ *       w = w * wz   wz = 1.0f / (1.0f + rz*rz),
+ *                    rz = (zb_p - zb_q) / ((sigma_depth * fminf(zb_p, zb_q)) * (float)(s * max(|i|, |j|)))
+ *       w = w * wd   wd = 1.0f / (1.0f + rd*rd),  rd = (dl_p - dl_q) / sigma_direct
+ *     csum.k = csum.k + in_q.k * w   for k = r, g, b;   wsum = wsum + w
+ *   out_p.k = csum.k / wsum,  out_p.w = in_p.w        (wsum >= 9/64: the centre tap always counts)
+ * rgba32f_out = the last level's output; rgba8_out = its pixels packed as the renders
+ * pack theirs (main.cpp:224-233): uint8(saturate(sqrtf(k)) * 255) per channel, alpha 255.
+ * fmaxf / fminf return the other operand for a NaN; which NaN comes out of NaN inputs is
+ * not specified.  Nothing screens the input: a radiance value that is not finite reaches
+ * every pixel whose taps reach it, level after level.
+ * The two sigma defaults were tuned by RMSE against 512-spp frames (DESIGN.md "Denoiser").
+ *
+ * The filter works on a WHOLE frame, width x height pixels with contiguous rows, row 0 at
+ * the bottom: a caller who rendered banded shards assembles the frame (radiance and AOV
+ * records alike, tmpt_tile_row_to_y) before the call. */
+typedef struct {
+    int32_t width, height, spp;   /* spp of the AOV records (for the mean depth) */
+    int32_t levels;               /* 1..6, 0 = 5 */
+    int32_t normal_exp;           /* squarings of the normal cosine, 0..8, -1 = 5 (c^32) */
+    int32_t flags;                /* TMPT_FLAG_OUT_DEVICE: all four pointers are device pointers;
+                                     TMPT_FLAG_WAIT_STREAM + wait_stream as in tmpt_render */
+    float sigma_depth;            /* 0 = auto: 1.0f / (float)height */
+    float sigma_direct;           /* 0 = 0.05f */
+    uint64_t wait_stream;
+    int32_t reserved[4];
+} tmpt_denoise_desc;
+
 /* ---- host side: scene ingest and camera (not kernels) ------------------- */
 
 /* LoadScene (main.cpp:122-170) over objParseFile (objparser.cpp:304-355):
@@ -301,7 +352,11 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    that otherwise takes only those the main launch's tail did not
  *   aov_group        tmpt_render_aov: lanes that share a pixel, each tracing every aov_group-th
  *                    sample (0 = auto: the largest of them that spp fills; or 1, 2, 4, 8, 16); the
- *                    records are the same for every value */
+ *                    records are the same for every value
+ *   denoise_lds      tmpt_denoise: how a level reads its taps -- 1: the levels of stride 1 and 2 stage
+ *                    their block's tile and halo (colour and guides) in LDS, the wider strides read
+ *                    global memory directly; 0: every level reads directly; -1 (default): the measured
+ *                    choice per stride; the output is the same for every value */
 int tmpt_scene_create_ex(const float* tris, int32_t n, int32_t device, const char* options, tmpt_scene** out);
 int tmpt_scene_set_option(tmpt_scene* scene, const char* key, double value);
 int tmpt_scene_get_option(const tmpt_scene* scene, const char* key, double* value);
@@ -381,6 +436,37 @@ int tmpt_render(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_des
  * of a progressive render.  Render option aov_group sets the lanes per pixel. */
 int tmpt_render_aov(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
                     tmpt_aov_pixel* out, uint64_t* ray_count);
+/* The float frame of a render: tmpt_render of the same desc, which also hands
+ * out the linear radiance.  rgba32f_out (tmpt_tile_rows(desc) * width * 4
+ * floats, the compact tile layout of tmpt_render): per pixel {r, g, b} = the
+ * colour sum taken in sample order times spp_recip = 1.0f / (float)spp -- the
+ * value of main.cpp:221, before the sqrtf of :224 -- and .w = 1.0f.
+ * rgba8_out (may be NULL): exactly the bytes tmpt_render writes; they are also
+ * what packing the float tile gives: uint8(saturate(sqrtf(k)) * 255), alpha 255.
+ * The call traces the paths tmpt_render traces, with the same kernels but for
+ * the stores of the float sums, so *ray_count and tmpt_get_stats are
+ * tmpt_render's.  Persistent engine, TMPT_SEED_PIXEL or TMPT_SEED_SAMPLE, whole
+ * renders only: -22 for TMPT_SEED_ROW, another engine, TMPT_FLAG_COUNT_VISITS or
+ * spp_begin / spp_count other than 0.  TMPT_FLAG_OUT_DEVICE: both outputs are
+ * device pointers (rgba32f_out 16-byte aligned); TMPT_FLAG_WAIT_STREAM as in
+ * tmpt_render.  The call leaves the scene's progressive state alone, as
+ * tmpt_render_aov does: it may run between two passes of a progressive render. */
+int tmpt_render_radiance(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
+                         float* rgba32f_out, uint8_t* rgba8_out, uint64_t* ray_count);
+/* The filter of tmpt_denoise_desc above, `levels` a-trous levels over the
+ * whole frame: rgba32f_in and aov hold width * height pixels / records (the AOV
+ * pass at desc->spp); rgba32f_out (may be NULL; may be rgba32f_in itself, else
+ * must not overlap it) takes the filtered frame, rgba8_out (may be NULL) its
+ * packed pixels; at least one of the two is given.  The scene supplies the
+ * device, the stream, the workspace and the error channel -- no geometry is
+ * read, and the progressive state is left alone.  Device pointers
+ * (TMPT_FLAG_OUT_DEVICE) are 16-byte aligned (rgba8_out: 4).  -22 for a size
+ * outside tmpt_render's limits, levels outside 0..6, normal_exp outside -1..8,
+ * a negative or non-finite sigma, other flags, or a missing pointer.
+ * tmpt_get_stats afterwards: render_ms is the filter's time on the device
+ * (guide preparation and the levels); the other fields keep the last render's. */
+int tmpt_denoise(tmpt_scene* scene, const tmpt_denoise_desc* desc, const float* rgba32f_in,
+                 const tmpt_aov_pixel* aov, float* rgba32f_out, uint8_t* rgba8_out);
 /* main.cpp:312-331 over several devices in ONE process (SURVEY.md §8e's
  * single-process form): a scene per entry of devices[] (created here, freed on
  * return), the frame's rows dealt round-robin to them (1-row bands), one host

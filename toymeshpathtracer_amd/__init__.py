@@ -14,6 +14,8 @@ reference                   here
 ``TraceImageBody`` :180     :meth:`Scene.trace_image` (parallel_for, main.cpp:329)
 (none: guide buffers)       :meth:`Scene.trace_aov` (:data:`AOV_DTYPE` records: normal, depth, direct
                             light, triangle id, coverage of a sample-seeded frame's camera rays)
+(none: float frame)         :meth:`Scene.trace_radiance` (the render's linear radiance beside its bytes)
+(none: denoiser)            :meth:`Scene.denoise` (edge-avoiding a-trous filter guided by the AOV records)
 ``stbi_write_png`` :342     :func:`write_png`
 ==========================  ==============================================
 
@@ -96,6 +98,13 @@ class _Desc(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 2)]
 
 
+class _DenoiseDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("spp", ctypes.c_int32),
+                ("levels", ctypes.c_int32), ("normal_exp", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("sigma_depth", ctypes.c_float), ("sigma_direct", ctypes.c_float),
+                ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
+
+
 class _Stats(ctypes.Structure):
     _fields_ = [("render_ms", ctypes.c_double), ("extend_ms", ctypes.c_double),
                 ("shadow_ms", ctypes.c_double), ("extend_rays", ctypes.c_uint64),
@@ -151,6 +160,11 @@ _render = _sig("tmpt_render", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Ca
                                              ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
 _render_aov = _sig("tmpt_render_aov", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
                                                      ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
+_render_radiance = _sig("tmpt_render_radiance", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
+                                                               ctypes.POINTER(_Desc), ctypes.c_void_p,
+                                                               ctypes.c_void_p, _u64p])
+_denoise = _sig("tmpt_denoise", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_DenoiseDesc), ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
 _build_octree = _sig("tmpt_scene_build_octree", ctypes.c_int, [ctypes.c_void_p, _f32p, _f32p])
 _octree_bounds = _sig("tmpt_octree_bounds", ctypes.c_int, [_f32p, _f32p, _f32p])
 _octree_digest = _sig("tmpt_octree_digest", ctypes.c_int, [_f32p, ctypes.c_int32, _f32p, _f32p, _u64p])
@@ -176,7 +190,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_render", "tmpt_render_multi", "tmpt_tile_rows", "tmpt_tile_row_to_y", "tmpt_get_stats",
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
-           "tmpt_octree_flags", "tmpt_render_aov")
+           "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise")
 
 
 def _check(rc: int, what: str) -> None:
@@ -574,6 +588,89 @@ class Scene:
         _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), rec.ctypes.data_as(ctypes.c_void_p),
                            ctypes.byref(rays)), "trace_aov")
         return rec, int(rays.value)
+
+    def trace_radiance(self, camera: Camera, width: int, height: int, spp: int, seed_mode: int = SEED_SAMPLE,
+                       band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None, wait_stream="current"):
+        """:meth:`trace_image` of one shard on the persistent engine (pixel or
+        sample seeding) that also hands out the linear radiance
+        (tmpt_render_radiance): returns (float32[tile_rows, width, 4], rgba8[tile_rows,
+        width, 4], rays) -- per pixel the colour sum in sample order times 1/spp
+        (before the square root of the 8-bit image) with alpha 1.0, the very
+        bytes and ray count of :meth:`trace_image`.  ``out``: a device pointer
+        for the float tile (16-byte aligned), or a pair (float tile, rgba8 tile
+        or None); the arrays returned are then None.  ``wait_stream`` as in
+        :meth:`trace_image`."""
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, spp, seed_mode, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        rows = int(_tile_rows(ctypes.byref(d)))
+        rays = ctypes.c_uint64()
+        cam = camera._to_c()
+        if out is not None:
+            f32, u8 = out if isinstance(out, (tuple, list)) else (out, None)
+            _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.c_void_p(int(f32)),
+                                    None if u8 is None else ctypes.c_void_p(int(u8)), ctypes.byref(rays)),
+                   "trace_radiance")
+            return None, None, int(rays.value)
+        rad = np.zeros((rows, width, 4), np.float32)
+        img = np.zeros((rows, width, 4), np.uint8)
+        _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), rad.ctypes.data_as(ctypes.c_void_p),
+                                img.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)), "trace_radiance")
+        return rad, img, int(rays.value)
+
+    def denoise(self, radiance, aov, spp: int, levels: int = 0, normal_exp: int = -1, sigma_depth: float = 0.0,
+                sigma_direct: float = 0.0, out=None, width: Optional[int] = None, height: Optional[int] = None,
+                wait_stream="current"):
+        """The AOV-guided a-trous filter (tmpt_denoise; include/tmpt.h states its
+        arithmetic) over a whole frame: ``radiance`` float32[h, w, 4]
+        (:meth:`trace_radiance`; shards assembled first), ``aov`` the frame's
+        :data:`AOV_DTYPE` records [h, w] at ``spp`` (:meth:`trace_aov`).
+        Returns (float32[h, w, 4], rgba8[h, w, 4]).  0 / -1 / 0.0 select the
+        defaults: 5 levels, the normal cosine to the 32nd power, sigma_depth =
+        1 / h, sigma_direct = 0.05.  ``out``: a float32 array [h, w, 4] that takes
+        the filtered frame (it may be ``radiance`` itself).  Device form: ``radiance`` and ``aov`` are
+        device pointers (ints, 16-byte aligned), ``width`` and ``height`` give
+        the size and ``out`` = (float frame pointer or None, rgba8 pointer or
+        None) -- the float output may be the input itself; returns (None, None)."""
+        dev = isinstance(radiance, int)
+        d = _DenoiseDesc()
+        if dev:
+            if width is None or height is None or out is None:
+                raise ValueError("denoise: device pointers need width, height and out")
+            h, w = int(height), int(width)
+        else:
+            radiance = np.ascontiguousarray(radiance, np.float32)
+            aov = np.ascontiguousarray(aov, AOV_DTYPE)
+            h, w = radiance.shape[:2]
+            if radiance.shape != (h, w, 4) or aov.shape != (h, w):
+                raise ValueError("denoise: radiance [h, w, 4] and aov [h, w] of one whole frame")
+        d.width, d.height, d.spp, d.levels, d.normal_exp = w, h, spp, levels, normal_exp
+        d.sigma_depth, d.sigma_direct = sigma_depth, sigma_direct
+        if dev:
+            d.flags = FLAG_OUT_DEVICE
+            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+            if ws is not None:
+                d.flags |= FLAG_WAIT_STREAM
+                d.wait_stream = int(ws)
+            f32, u8 = out
+            _check(_denoise(self._h, ctypes.byref(d), ctypes.c_void_p(radiance), ctypes.c_void_p(int(aov)),
+                            None if f32 is None else ctypes.c_void_p(int(f32)),
+                            None if u8 is None else ctypes.c_void_p(int(u8))), "denoise")
+            return None, None
+        res = np.zeros((h, w, 4), np.float32) if out is None else out
+        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+                and res.flags.c_contiguous):
+            raise ValueError("denoise: out must be a contiguous float32 array [h, w, 4] (it may be radiance itself)")
+        img = np.zeros((h, w, 4), np.uint8)
+        _check(_denoise(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
+                        aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
+                        img.ctypes.data_as(ctypes.c_void_p)), "denoise")
+        return res, img
 
     def stats(self) -> RenderStats:
         s = _Stats()

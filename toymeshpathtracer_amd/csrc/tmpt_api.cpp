@@ -29,7 +29,7 @@ void camera_init(tmpt_camera* cam, f3 lookFrom, f3 lookAt, f3 vup, float vfov, f
 void camera_for_scene(tmpt_camera* cam, f3 sceneMin, f3 sceneMax, int w, int h, bool sponza);
 int write_png(const char* path, const uint8_t* rgba, int w, int h);
 int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* d_out,
-           uint64_t* ray_count);
+           uint64_t* ray_count, float4* d_sums = nullptr);
 int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
                     float* d_hits, int32_t* d_ids);
 
@@ -145,6 +145,7 @@ const OptionDef kOptions[] = {
     {"rowstream_test_abort", false, 0, 1, &Options::rowstream_test_abort, nullptr, nullptr},
     {"tie_rule", false, 0, 1, &Options::tie_rule, nullptr, nullptr},
     {"aov_group", false, 0, 16, &Options::aov_group, nullptr, nullptr},
+    {"denoise_lds", false, -1, 1, &Options::denoise_lds, nullptr, nullptr},
 };
 
 const OptionDef* find_option(const char* key)
@@ -753,6 +754,130 @@ int tmpt_render_aov(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_des
             rc = (set_error("tmpt_render_aov: readback failed"), -1);
     }
     if (!dev_out && d_out) (void)hipFree(d_out);
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d, float* rgba32f_out,
+                         uint8_t* rgba8_out, uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    if (!h || !cam || !d || !rgba32f_out) return bad("tmpt_render_radiance: null argument");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_radiance: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_radiance: invalid height");
+    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_radiance: invalid samplesPerPixel");
+    if (d->seed_mode != TMPT_SEED_PIXEL && d->seed_mode != TMPT_SEED_SAMPLE)
+        return bad("tmpt_render_radiance: seed_mode must be TMPT_SEED_PIXEL or TMPT_SEED_SAMPLE (row seeding keeps no "
+                   "float sum per pixel)");
+    if (d->engine != TMPT_ENGINE_PERSISTENT)
+        return bad("tmpt_render_radiance: engine must be TMPT_ENGINE_PERSISTENT");
+    if (d->spp_begin != 0 || d->spp_count != 0)
+        return bad("tmpt_render_radiance: spp_begin / spp_count must be 0 (whole renders only)");
+    if (d->flags & TMPT_FLAG_COUNT_VISITS)
+        return bad("tmpt_render_radiance: TMPT_FLAG_COUNT_VISITS is not supported");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
+        return bad("tmpt_render_radiance: invalid shard");
+    const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev_out && (reinterpret_cast<uintptr_t>(rgba32f_out) & 15u) != 0)
+        return bad("tmpt_render_radiance: a device rgba32f_out must be 16-byte aligned");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width;
+    // the kernels write both tiles: device buffers of the library's own stand in
+    // for host outputs and for an rgba8_out the caller does not want
+    float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
+    uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
+    void *own_f = nullptr, *own_8 = nullptr;
+    auto cleanup = [&]() {
+        if (own_f) (void)hipFree(own_f);
+        if (own_8) (void)hipFree(own_8);
+    };
+    if (px && ((!d_f && hipMalloc(&own_f, px * sizeof(float4)) != hipSuccess) ||
+               (!d_8 && hipMalloc(&own_8, px * 4) != hipSuccess))) {
+        cleanup();
+        return bad("tmpt_render_radiance: out of device memory");
+    }
+    if (own_f) d_f = static_cast<float4*>(own_f);
+    if (own_8) d_8 = static_cast<uint32_t*>(own_8);
+    int rc = render(s, cam, d, d_8, ray_count, d_f);
+    if (!rc) rc = check_report(s, "tmpt_render_radiance");
+    if (!rc && !dev_out && px) {
+        if (hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
+            (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = (set_error("tmpt_render_radiance: readback failed"), -1);
+    }
+    cleanup();
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f_in, const tmpt_aov_pixel* aov,
+                 float* rgba32f_out, uint8_t* rgba8_out)
+{
+    TMPT_GUARD_BEGIN
+    // the descriptor first, before anything that needs a scene or a device
+    if (!d) return bad("tmpt_denoise: null descriptor");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_denoise: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_denoise: invalid height");
+    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_denoise: invalid samplesPerPixel");
+    if (d->levels < 0 || d->levels > 6) return bad("tmpt_denoise: levels out of range (1..6, 0 = 5)");
+    if (d->normal_exp < -1 || d->normal_exp > 8) return bad("tmpt_denoise: normal_exp out of range (0..8, -1 = 5)");
+    if (!(d->sigma_depth >= 0.0f) || !(d->sigma_depth <= 3.0e38f))
+        return bad("tmpt_denoise: sigma_depth must be finite and not negative (0 = auto)");
+    if (!(d->sigma_direct >= 0.0f) || !(d->sigma_direct <= 3.0e38f))
+        return bad("tmpt_denoise: sigma_direct must be finite and not negative (0 = default)");
+    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return bad("tmpt_denoise: unknown flag");
+    if (!rgba32f_out && !rgba8_out) return bad("tmpt_denoise: no output (rgba32f_out and rgba8_out are both null)");
+    if (!h || !rgba32f_in || !aov) return bad("tmpt_denoise: null argument");
+    const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev && (((reinterpret_cast<uintptr_t>(rgba32f_in) | reinterpret_cast<uintptr_t>(aov) |
+                  reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
+                (reinterpret_cast<uintptr_t>(rgba8_out) & 3u) != 0))
+        return bad("tmpt_denoise: device pointers must be 16-byte aligned (rgba8_out: 4)");
+    tmpt_denoise_desc r = *d;  // the defaults, in one place
+    if (r.levels == 0) r.levels = 5;
+    if (r.normal_exp < 0) r.normal_exp = 5;
+    if (r.sigma_depth == 0.0f) r.sigma_depth = 1.0f / (float)r.height;
+    if (r.sigma_direct == 0.0f) r.sigma_direct = 0.05f;
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const size_t n = (size_t)r.width * (size_t)r.height;
+    const float4* d_in = reinterpret_cast<const float4*>(rgba32f_in);
+    const tmpt_aov_pixel* d_aov = aov;
+    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
+    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
+    void *own_in = nullptr, *own_aov = nullptr, *own_8 = nullptr;
+    auto cleanup = [&]() {
+        if (own_in) (void)hipFree(own_in);
+        if (own_aov) (void)hipFree(own_aov);
+        if (own_8) (void)hipFree(own_8);
+    };
+    if (!dev) {  // host pointers: staged on the device; the float result is filtered in place there
+        if (hipMalloc(&own_in, n * sizeof(float4)) != hipSuccess ||
+            hipMalloc(&own_aov, n * sizeof(tmpt_aov_pixel)) != hipSuccess ||
+            (rgba8_out && hipMalloc(&own_8, n * 4) != hipSuccess)) {
+            cleanup();
+            return bad("tmpt_denoise: out of device memory");
+        }
+        if (hipMemcpy(own_in, rgba32f_in, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess) {
+            cleanup();
+            return (set_error("tmpt_denoise: upload failed"), -1);
+        }
+        d_in = static_cast<const float4*>(own_in);
+        d_aov = static_cast<const tmpt_aov_pixel*>(own_aov);
+        d_o32 = rgba32f_out ? static_cast<float4*>(own_in) : nullptr;
+        d_o8 = static_cast<uint32_t*>(own_8);
+    }
+    int rc = denoise(s, &r, d_in, d_aov, d_o32, d_o8);
+    if (!rc && !dev) {
+        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
+            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = (set_error("tmpt_denoise: readback failed"), -1);
+    }
+    cleanup();
     return rc;
     TMPT_GUARD_END
 }

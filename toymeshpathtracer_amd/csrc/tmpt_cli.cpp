@@ -1,6 +1,6 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
-//        [--gpus N] [--device D] [--out output.png] [--aov PREFIX]
+//        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -11,6 +11,8 @@
 // --aov PREFIX (one device only): after the frame, the AOV pass (tmpt_render_aov) at the same
 // size and spp on the same device, written as PREFIX_normal.png, PREFIX_direct.png and
 // PREFIX_depth.png.
+// --denoise OUT.png (one device, --seed sample): beside the usual output, the frame's float
+// radiance (tmpt_render_radiance) filtered by tmpt_denoise with the AOV records as guides.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,11 +88,46 @@ static int write_aovs(const char* prefix, const float* tris, int32_t n, const fl
     return 0;
 }
 
+// --denoise OUT.png on `device` (its own scene, the octree built as for the frame): the
+// sample-seeded radiance render (tmpt_render_radiance), the AOV pass at the same size and spp
+// (tmpt_render_aov) and the filter with its defaults (tmpt_denoise); the filtered frame's
+// packed pixels are written to `path`.
+static int write_denoised(const char* path, const float* tris, int32_t n, const float box[6], const tmpt_camera* cam,
+                          int w, int h, int spp, int device)
+{
+    tmpt_scene* scene = nullptr;
+    if (tmpt_scene_create(tris, n, device, &scene)) return 1;
+    const size_t P = (size_t)w * h;
+    std::vector<float> rad(P * 4);
+    std::vector<tmpt_aov_pixel> rec(P);
+    std::vector<uint8_t> img(P * 4);
+    tmpt_render_desc desc;
+    memset(&desc, 0, sizeof(desc));
+    desc.width = w; desc.height = h; desc.spp = spp; desc.seed_mode = TMPT_SEED_SAMPLE;
+    desc.engine = TMPT_ENGINE_PERSISTENT;
+    tmpt_denoise_desc dn;
+    memset(&dn, 0, sizeof(dn));
+    dn.width = w; dn.height = h; dn.spp = spp; dn.normal_exp = -1;
+    uint64_t rays = 0, aov_rays = 0;
+    tmpt_stats st;
+    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    if (!rc) rc = tmpt_render_radiance(scene, cam, &desc, rad.data(), nullptr, &rays);
+    if (!rc) rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &aov_rays);
+    if (!rc) rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
+    if (!rc) rc = tmpt_get_stats(scene, &st);
+    if (tmpt_scene_destroy(scene) && !rc) rc = 1;
+    if (rc) return rc;
+    printf("Denoised frame: %.1f K Rays + %.1f K AOV Rays, filter %.3f ms\n", rays / 1000.0, aov_rays / 1000.0,
+           st.render_ms);
+    return tmpt_write_png(path, img.data(), w, h);
+}
+
 int main(int argc, const char** argv)
 {
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
-               "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix]\n");
+               "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
+               "[--denoise file.png]\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -103,6 +140,7 @@ int main(int argc, const char** argv)
     int seed = TMPT_SEED_ROW, engine = TMPT_ENGINE_PERSISTENT, gpus = 1, device = 0;
     const char* out = "output.png";
     const char* aov = nullptr;
+    const char* denoised = nullptr;
     for (int i = 5; i < argc; ++i) {
         if (!strcmp(argv[i], "--seed") && i + 1 < argc) {
             ++i;
@@ -118,6 +156,7 @@ int main(int argc, const char** argv)
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
+        else if (!strcmp(argv[i], "--denoise") && i + 1 < argc) denoised = argv[++i];
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -129,6 +168,11 @@ int main(int argc, const char** argv)
     }
     if (gpus < 1) gpus = 1;
     if (aov && gpus > 1) { printf("ERROR: --aov runs on one device (--gpus 1)\n"); return 1; }
+    if (denoised && gpus > 1) { printf("ERROR: --denoise runs on one device (--gpus 1)\n"); return 1; }
+    if (denoised && seed != TMPT_SEED_SAMPLE) {
+        printf("ERROR: --denoise needs --seed sample (the AOV records are a sample-seeded frame's)\n");
+        return 1;
+    }
     int ndev = tmpt_device_count();
     if (device + gpus > ndev) {
         printf("ERROR: %d GPU(s) requested from device %d, %d present\n", gpus, device, ndev);
@@ -159,6 +203,10 @@ int main(int argc, const char** argv)
     printf("- %.1f K Rays, %.1f K Rays/s\n", total / 1000.0, total / 1000.0 / dt);
     if (tmpt_write_png(out, image.data(), w, h)) { printf("ERROR: %s\n", tmpt_last_error()); return 1; }
     if (aov && write_aovs(aov, tris, n, box, &cam, w, h, spp, device)) {
+        printf("ERROR: %s\n", tmpt_last_error());
+        return 1;
+    }
+    if (denoised && write_denoised(denoised, tris, n, box, &cam, w, h, spp, device)) {
         printf("ERROR: %s\n", tmpt_last_error());
         return 1;
     }

@@ -239,6 +239,8 @@ struct Options {
     int shadow_order = -1;    // any-hit queries: the order a node's children are visited in (-1 = default,
                               // 0 nearest entry first, 1 longest overlap tf - tn first, 2 largest exit tf first)
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
+    int denoise_lds = -1;     // tmpt_denoise: levels of stride 1 and 2 read an LDS tile + halo (1), every level
+                              // reads global memory directly (0), or the measured choice per stride (-1)
 };
 int options_parse(Options& o, const char* text, bool allow_build);
 int options_set(Options& o, const char* key, double value, bool allow_build);

@@ -1,5 +1,6 @@
 // tmpt_render.h -- what the render translation units share (tmpt_render.hip:
-// the path tracer's engines; tmpt_aov.hip: the AOV pass): the kernel argument
+// the path tracer's engines; tmpt_aov.hip: the AOV pass; tmpt_denoise.hip: the
+// filter over a finished frame): the kernel argument
 // block of one render call, the wave helpers, and the host helpers of a render
 // call (defined in tmpt_render.hip).
 #pragma once
@@ -71,5 +72,11 @@ void reset_render_stats(Scene& s);
 // tmpt_aov.hip: the AOV pass of one shard (tmpt_render_aov), d_out on the device
 int render_aov(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt_aov_pixel* d_out,
                uint64_t* ray_count);
+
+// tmpt_denoise.hip: the a-trous filter (tmpt_denoise) over a whole frame, every
+// pointer on the device; d (checked by the caller) holds the resolved levels,
+// normal_exp and sigmas.  d_out32 or d_out8 may be null; d_out32 may be d_in.
+int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt_aov_pixel* d_aov, float4* d_out32,
+            uint32_t* d_out8);
 
 }  // namespace tmpt

@@ -1147,7 +1147,7 @@ __device__ void rss_chaser(const RenderArgs& a, const RsStream& S, int wave)
 
 
 template <bool COUNT, int BLOCK, int SL, int STEPS, int SHADE_MIN, int OCC = 1, int TAIL = 0, int PROF = 0,
-          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0>
+          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false>
 __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a, PathCtl pc,
                                                 uint32_t* __restrict__ out,
                                                 uint32_t* __restrict__ ovf,
@@ -1161,6 +1161,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // sample seeding): as 2, but a flagged sample is dropped and traced again
     // in the redo phase -- the main loop carries no octree walk.
     constexpr bool DEFER = TIES == 1, FLAG = TIES != 0;
+    // SUMS (tmpt_render_radiance, sample seeding with a pixel as one unit, no
+    // colour buffer): the pixel's colour sum goes to a.prog beside the packed
+    // pixel, as pixel mode's does; the instantiations tmpt_render launches have
+    // SUMS false and no such store.
+    static_assert(!SUMS || SAMP == 1, "SUMS: the sample kernel's float sums");
     __shared__ uint32_t s_stack[SL * BLOCK];
     // SAMP 3, 4 (shadow-free speculation): no light terms, no pending next ray
     __shared__ float s_light[SAMP >= 3 ? 1 : kMaxDepth * BLOCK];
@@ -1729,7 +1734,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     if (smp < (uint32_t)a.smp_end && (!SAMP || ((smp & a.bmask) != 0u && !single))) {
                         cam = true;
                     } else {
-                        if (kFull && a.prog) a.prog[pix] = make_float4(col.x, col.y, col.z, __uint_as_float(rng));
+                        if ((kFull || (SUMS && !pc.sbuf)) && a.prog)
+                            a.prog[pix] = make_float4(col.x, col.y, col.z, __uint_as_float(rng));
                         if (kFull && pc.cost_out) pc.cost_out[pix] = psteps;
                         if (SAMP < 2 && (!SAMP || !pc.sbuf)) out[pix] = pack_pixel(col, a.out_recip);
                         has_pix = false;
@@ -2110,7 +2116,8 @@ __global__ void __launch_bounds__(256) k_order_keys(const uint32_t* __restrict__
 // A progressive pass (prog != null) sums its samples [s_begin, s_end) onto the
 // sum the previous pass left in prog (none when s_begin = 0), keeps the new sum
 // there, and writes the preview with out_recip = 1/s_end (the full render's
-// 1/spp on the last pass).
+// 1/spp on the last pass).  tmpt_render_radiance hands in its float tile as
+// prog with s_begin = 0: the whole render's sums, kept beside the pixels.
 __global__ void __launch_bounds__(64) k_resolve_px(const float4* __restrict__ sbuf, int64_t P, int32_t spp,
                                                     float spp_recip, uint32_t* __restrict__ out,
                                                     int32_t s_begin = 0, int32_t s_end = -1,
@@ -2833,8 +2840,12 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
 
 // The chains' pixels: the pilot's colour sum, then samples smp0 .. spp-1 from
 // the colour buffer, in sample order (main.cpp:218), packed (main.cpp:221-233).
+// sums (tmpt_render_radiance; null otherwise): the pixel's float sum is kept
+// there too, as pass 2 keeps the other pixels' (it may be cinit itself: each
+// thread reads its own pixel's entry before it writes it).
 __global__ void __launch_bounds__(256) k_resolve_chains(PixelChains ch, const float4* __restrict__ sbuf, int32_t spp,
-                                                        float spp_recip, uint32_t* __restrict__ out)
+                                                        float spp_recip, uint32_t* __restrict__ out,
+                                                        float4* sums = nullptr)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= ch.n) return;
@@ -2845,6 +2856,7 @@ __global__ void __launch_bounds__(256) k_resolve_chains(PixelChains ch, const fl
         const float4 c = sbuf[(size_t)p * (size_t)spp + (size_t)k];
         col = col + mk(c.x, c.y, c.z);
     }
+    if (sums) sums[p] = make_float4(col.x, col.y, col.z, c0.w);
     out[p] = pack_pixel(col, spp_recip);
 }
 
@@ -3203,6 +3215,23 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                              : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 2>;
         else if (waves5 && fn == fn_default)
             fn_main = k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1>;
+        // tmpt_render_radiance in sample seeding without the colour buffer (a
+        // pixel is one unit): the kernel chosen above with SUMS, which stores
+        // the pixel's float sum in a.prog beside the packed pixel.  With the
+        // buffer k_resolve_px stores it, in pixel seeding k_path<SAMP 0> does.
+        if (a.jt && a.prog && !pc.sbuf) {
+            if (count || prof) {
+                set_error("tmpt_render_radiance: no instrumented kernel stores the float sums");
+                return -22;
+            }
+            const bool oct = s.oct_view && o.tie_rule == 0;
+            fn_main =
+                soa      ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, true, 0, true>
+                : oct    ? (waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 2, true>
+                                   : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 2, true>)
+                : waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 0, true>
+                         : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 0, true>;
+        }
         // the launch's grid is the launched kernel's co-resident block count
         // (the deferred re-traces' completion count relies on it)
         int grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
@@ -3260,8 +3289,10 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             break;
         }
         if (pc.sbuf) {
+            // (a.prog: a progressive pass's carried sums, or tmpt_render_radiance's
+            // float sums of a whole render; null for a plain tmpt_render)
             k_resolve_px<<<(unsigned)((a.slots + 63) / 64), 64, 0, s.stream>>>(
-                pc.sbuf, a.slots, a.spp, a.out_recip, d_out, a.smp_begin, a.smp_end, pass ? a.prog : nullptr);
+                pc.sbuf, a.slots, a.spp, a.out_recip, d_out, a.smp_begin, a.smp_end, a.prog);
             TMPT_HIP(hipGetLastError());
         }
         return 0;
@@ -3369,6 +3400,10 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     }
     if (final_launch(a2, grid_px)) return -1;
     s.path_launches = 2;
+    // tmpt_render_radiance: pass 2 (and k_resolve_chains) left every pixel's
+    // float sum in the pilot's state array
+    if (a.prog)
+        TMPT_HIP(hipMemcpyAsync(a.prog, state, sizeof(float4) * (size_t)P, hipMemcpyDeviceToDevice, s.stream));
     return 0;
 }
 
@@ -3955,8 +3990,10 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
         TMPT_HIP(hipMemsetAsync(gs[0].heads, 0, head_words * 4, s.stream));
         fn<<<pgrid, kBlk, 0, s.stream>>>(view(s), as, pc2, d_out, gs[0].ovf, spec_ctr + 16);
         if (ch)
-            k_resolve_chains<<<(unsigned)((ch->n + 255) / 256), 256, 0, s.stream>>>(*ch, s.sbuf, a.spp, a.spp_recip,
-                                                                                   d_out);
+            // (a radiance render, a.prog set: the chains' sums go back into the pilot's
+            // state array, from which render_persistent copies every pixel's)
+            k_resolve_chains<<<(unsigned)((ch->n + 255) / 256), 256, 0, s.stream>>>(
+                *ch, s.sbuf, a.spp, a.spp_recip, d_out, a.prog ? const_cast<float4*>(ch->cinit) : nullptr);
         else
             k_resolve_px<<<(unsigned)((a.slots + 63) / 64), 64, 0, s.stream>>>(s.sbuf, a.slots, a.spp, a.spp_recip,
                                                                                 d_out);
@@ -4146,8 +4183,28 @@ void reset_render_stats(Scene& s)
     s.tie_path = 0;
 }
 
+// tmpt_render_radiance's last step: the float sums {r, g, b, -} the render left
+// per pixel become the float frame {sum * spp_recip, 1.0f}, in place
+// (main.cpp:221: col *= spp_recip, before the sqrtf of :224)
+__global__ void __launch_bounds__(256) k_radiance_scale(float4* __restrict__ px, int64_t n, float spp_recip)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 c = px[i];
+    const f3 col = mk(c.x, c.y, c.z) * spp_recip;
+    px[i] = make_float4(col.x, col.y, col.z, 1.0f);
+}
+
+// d_sums (tmpt_render_radiance: a whole render on the persistent engine in
+// pixel or sample seeding, checked by the caller; null for tmpt_render): one
+// float4 per pixel of the tile, which the render's own stores of the float
+// colour sum fill (RenderArgs::prog: k_path in pixel seeding, k_resolve_px or
+// k_path<SUMS> in sample seeding) and k_radiance_scale then scales.  The
+// launch plan (units, blocks, grids, passes) does not depend on it, and the
+// scene's progressive state is not touched: the sums are this buffer's, not
+// Scene::prog's.
 int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* d_out,
-           uint64_t* ray_count)
+           uint64_t* ray_count, float4* d_sums)
 {
     RenderArgs a = make_args(cam, d);
     bool count = (d->flags & TMPT_FLAG_COUNT_VISITS) != 0;
@@ -4179,6 +4236,8 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
         a.prog = s.prog;
         memcpy(s.prog_key, key, sizeof(key));
         s.prog_key[6] = -1;  // valid again only once this pass completes
+    } else if (d_sums) {
+        a.prog = d_sums;
     }
     if (a.seed_mode == TMPT_SEED_SAMPLE) {  // jump tables of sample_seed, grown to spp
         if (int rc = ensure_sample_tables(s, a.spp, "tmpt_render")) return rc;
@@ -4220,6 +4279,10 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
         } else {
             rc = render_megakernel(s, a, d_out, count, d_counters);
             if (a.seed_mode == TMPT_SEED_ROW) s.row_engine = 1;
+        }
+        if (rc == 0 && d_sums) {
+            k_radiance_scale<<<(unsigned)((a.slots + 255) / 256), 256, 0, s.stream>>>(d_sums, a.slots, a.spp_recip);
+            if (hipGetLastError() != hipSuccess) rc = (set_error("tmpt_render_radiance: scale launch failed"), -1);
         }
     }
     (void)hipEventRecord(e1, s.stream);
