@@ -346,7 +346,17 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    2 = largest exit distance first, by the key tn - 1024 tf); only the hit / miss
  *                    bit of such a query is used, so the image and the ray counts are the same for
  *                    every value, and closest-hit queries do not change at all
- *   redo_cap         test hook (0 = auto): the capacity of tie_defer's sample list; a
+ *   pop_cull         closest-hit queries, every engine: a traversal stack entry carries, in the bits its
+ *                    child link leaves free, the top bits of its child's entry distance (a lower bound);
+ *                    an entry popped once the best hit is already nearer than that is discarded
+ *                    unvisited and one more entry popped (-1 = the seeding's measured default: on in
+ *                    every seeding mode and for the batched queries; 0 = off; 1 = on); the child's own box test would reject it, so every answer, tie flag, image
+ *                    and ray count is the same for every value; only node_visits and tri_tests fall
+ *   pop_key_bits     read-only (tmpt_scene_get_option): the width K of that key on this scene, 31 less
+ *                    the bits of a child link (the record count's and leaf_max's widths), at most 16 and
+ *                    at most pop_key_cap; 0, and nothing culled, where fewer than 9 would be left
+ *   pop_key_cap      test hook (-1 = no cap): at most this many key bits (0..16; 0..8 give no key)
+ *   redo_cap        test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown
  *   redo_inline      test hook (1): 0 leaves every dropped sample to the second launch
  *                    that otherwise takes only those the main launch's tail did not

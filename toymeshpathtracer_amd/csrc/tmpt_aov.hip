@@ -178,7 +178,7 @@ int render_aov(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt
                uint64_t* ray_count)
 {
     RenderArgs a = make_args(cam, d);
-    s.row_render = false;  // the AOV pass traces the sample-seeded frame's camera rays
+    s.row_render = s.pixel_render = false;  // the AOV pass traces the sample-seeded frame's camera rays
     if (int rc = ensure_sample_tables(s, a.spp, "tmpt_render_aov")) return rc;
     a.jt = s.jt;
     if (int rc = wait_caller_stream(s, d, "tmpt_render_aov")) return rc;

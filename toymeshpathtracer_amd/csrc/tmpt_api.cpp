@@ -130,6 +130,8 @@ const OptionDef kOptions[] = {
     {"path_waves", false, 0, 5, &Options::path_waves, nullptr, nullptr},
     {"top_walk", false, -1, 8, &Options::top_walk, nullptr, nullptr},
     {"shadow_order", false, -1, 2, &Options::shadow_order, nullptr, nullptr},
+    {"pop_cull", false, -1, 1, &Options::pop_cull, nullptr, nullptr},
+    {"pop_key_cap", false, -1, kPopKeyMax, &Options::pop_key_cap, nullptr, nullptr},
     {"rowspec", false, 0, 1, &Options::rowspec, nullptr, nullptr},
     {"rowspec_wmax", false, 0, 16384, &Options::rowspec_wmax, nullptr, nullptr},
     {"rowspec_windows", false, 0, 32, &Options::rowspec_windows, nullptr, nullptr},
@@ -596,6 +598,10 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
 {
     TMPT_GUARD_BEGIN
     if (!h || !value) return bad("tmpt_scene_get_option: null argument");
+    if (key && strcmp(key, "pop_key_bits") == 0) {  // read-only: the scene's layout under pop_key_cap
+        *value = (double)pop_key_bits(h->s.link_bits, h->s.opt.pop_key_cap);
+        return 0;
+    }
     return options_get(h->s.opt, key, value);
     TMPT_GUARD_END
 }

@@ -568,7 +568,8 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
                                                        int2* __restrict__ next,
                                                        uint32_t* __restrict__ counters,
                                                        Bvh4Node* __restrict__ out, int leaf_max,
-                                                       int n_tris, const uint32_t* __restrict__ dec)
+                                                       int n_tris, const uint32_t* __restrict__ dec,
+                                                       int count_shift)
 {
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nf) return;
@@ -629,7 +630,7 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
     }
     // empty slots: inverted quantised box (lo 255 > hi 0) and a link to the null
     // leaf, so a step that does not consult the mask still finds nothing there
-    const int null_leaf = (int)(0x80000000u | (uint32_t)n_tris);
+    const int null_leaf = (int)leaf_link(1u, (uint32_t)n_tris, count_shift);
     int4 links = make_int4(null_leaf, null_leaf, null_leaf, null_leaf);
     int* lk = &links.x;
     for (int k = nc; k < 4; ++k)
@@ -646,10 +647,9 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
         mask |= 1u << k;
         int c = cand[k];
         if (c < 0) {  // BVH2 leaf: one triangle at sorted slot ~c
-            lk[k] = (int)(0x80000000u | (uint32_t)(~c));
+            lk[k] = (int)leaf_link(1u, (uint32_t)(~c), count_shift);
         } else if (is_leaf(c)) {
-            lk[k] = (int)(0x80000000u | ((uint32_t)(count_of(c) - 1) << kLeafCountShift) |
-                          (uint32_t)range[c].x);
+            lk[k] = (int)leaf_link((uint32_t)count_of(c), (uint32_t)range[c].x, count_shift);
         } else {
             uint32_t slot = atomicAdd(&counters[0], 1u);
             uint32_t qi = atomicAdd(&counters[1], 1u);
@@ -805,6 +805,15 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
     k_tri_pre<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, tvals, s.tri_pre);
     const int leaf_max = s.opt.leaf_max;
     s.leaf_max = leaf_max;
+    // the links' layout (tmpt_internal.h link_layout): the leaf fields as wide as
+    // this scene needs; a node index never needs more (n_nodes4 <= m < n)
+    const LinkLayout ll = link_layout((uint32_t)n, leaf_max, (uint32_t)m);
+    if (ll.count_shift > 27 || ll.link_bits > 31) {
+        set_error("build_lbvh: too many triangles for a 32-bit child link");
+        return -1;
+    }
+    s.count_shift = ll.count_shift;
+    s.link_bits = ll.link_bits;
     // collapse=1: SAH-optimal collapse (fewer, fuller nodes: 13.2k vs 16.7k
     // on the sponza stand-in, but measured ~2% slower there); default greedy
     // largest-area opening
@@ -839,7 +848,8 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
     int2 *fa = fr0, *fb = fr1;
     while (nf > 0) {
         k_bvh4_level<<<blocks_for(nf, kBlock), kBlock, 0, st>>>(tchild, trange, leaf, tvals, tib, fa, nf,
-                                                                fb, c4, s.nodes4, leaf_max, n, dec);
+                                                                fb, c4, s.nodes4, leaf_max, n, dec,
+                                                                ll.count_shift);
         ++levels;
         if (hipMemcpyAsync(hc, c4, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) return -1;

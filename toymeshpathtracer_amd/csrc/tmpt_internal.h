@@ -26,7 +26,8 @@ namespace tmpt {
 //      signed: scale = 2^e) | child-valid mask (byte 3)
 //   b: qlo.x[4], qhi.x[4], qlo.y[4], qhi.y[4]   (uint8 per child, child k in byte k)
 //   c: qlo.z[4], qhi.z[4], 0, 0
-//   d: child links: >=0 node index; <0 leaf = 0x80000000 | (count-1)<<27 | first slot
+//   d: child links: >=0 node index; <0 leaf = 0x80000000 | (count-1)<<count_shift | first slot
+//      (count_shift per scene: link_layout below)
 // A child box decodes as origin + q*scale (q*scale exact), quantised outward
 // from the padded boxes, so culling stays conservative.
 struct alignas(16) Bvh4Node {
@@ -37,9 +38,93 @@ struct alignas(16) Bvh4Node {
 };
 static_assert(sizeof(Bvh4Node) == 64, "BVH4Q node is one half cache line");
 
-constexpr int kLeafCountShift = 27;
-constexpr uint32_t kLeafFirstMask = (1u << kLeafCountShift) - 1u;
 constexpr int kLeafMaxTris = 16;
+
+// Child links and stack entries ("Link layout").  A link
+// is 32 bits: an internal child is its node index; a leaf is
+//   bit 31 | (count - 1) << count_shift | first record
+// with the fields only as wide as the scene needs: count_shift = bits(n), n
+// the highest record a leaf can name (the null leaf's), and a count field of
+// bits(leaf_max - 1) bits.  Bits 30..link_bits of every link are therefore 0,
+// and a traversal stack entry carries there the top K bits of the f32 pattern
+// of its child's entry distance tn >= 0 (sign bit 0: it coincides with the leaf
+// flag): 8 exponent bits and K - 8 of the mantissa, truncated, so a lower bound
+// of tn.  Pop culling compares it with the best hit (tmpt_traverse.h trav_pop).
+constexpr int kPopKeyMin = 9;   // fewer bits than the exponent and one more: no key, culling off
+constexpr int kPopKeyMax = 16;
+TMPT_HD constexpr int bits_for(uint32_t v)
+{
+    int b = 0;
+    for (; v; v >>= 1) ++b;
+    return b;
+}
+struct LinkLayout {
+    int count_shift;  // of a leaf link's count - 1; the first-record field lies below it
+    int link_bits;    // bits 0..link_bits-1 (and bit 31) are all a link uses
+};
+TMPT_HD constexpr LinkLayout link_layout(uint32_t n_tris, int leaf_max, uint32_t n_nodes4)
+{
+    const int cs = bits_for(n_tris), leaf = cs + bits_for((uint32_t)leaf_max - 1u);
+    const int node = bits_for(n_nodes4 ? n_nodes4 - 1u : 0u);
+    return LinkLayout{cs, leaf > node ? leaf : node};
+}
+// K, the key's width: what the link leaves free below bit 31, at most
+// kPopKeyMax and at most `cap` (option pop_key_cap, < 0 = none); 0 below kPopKeyMin
+TMPT_HD constexpr int pop_key_bits(int link_bits, int cap)
+{
+    int k = 31 - link_bits;
+    k = k > kPopKeyMax ? kPopKeyMax : k;
+    k = cap >= 0 && k > cap ? cap : k;
+    return k < kPopKeyMin ? 0 : k;
+}
+TMPT_HD constexpr uint32_t pop_key_mask(int k) { return k ? ((1u << k) - 1u) << (31 - k) : 0u; }
+TMPT_HD constexpr uint32_t leaf_link(uint32_t count, uint32_t first, int count_shift)
+{
+    return 0x80000000u | ((count - 1u) << count_shift) | first;
+}
+TMPT_HD constexpr uint32_t leaf_first(uint32_t link, int count_shift) { return link & ((1u << count_shift) - 1u); }
+TMPT_HD constexpr uint32_t leaf_count(uint32_t link, int count_shift)
+{
+    return ((link >> count_shift) & (uint32_t)(kLeafMaxTris - 1)) + 1u;
+}
+// a stack entry from a clean link and the f32 bits of its key; and back
+TMPT_HD constexpr uint32_t entry_pack(uint32_t link, uint32_t key_f32, uint32_t key_mask)
+{
+    return (key_f32 & key_mask) | link;
+}
+TMPT_HD constexpr uint32_t entry_key(uint32_t e, uint32_t key_mask) { return e & key_mask; }
+TMPT_HD constexpr uint32_t entry_link(uint32_t e, uint32_t key_mask) { return e ^ (e & key_mask); }
+
+namespace link_checks {
+// the bench scene (stand-in sponza: 66,453 records, leaves of <= 2, 16.7 k nodes): 13 key bits
+constexpr LinkLayout kBench = link_layout(66453u, 2, 16700u);
+static_assert(kBench.count_shift == 17 && kBench.link_bits == 18, "bench scene: 18-bit links");
+static_assert(pop_key_bits(kBench.link_bits, -1) == 13 && pop_key_mask(13) == 0x7FFC0000u, "bench scene: bits 30..18");
+static_assert(pop_key_bits(kBench.link_bits, 9) == 9 && pop_key_mask(9) == 0x7FC00000u, "capped key");
+static_assert(pop_key_bits(kBench.link_bits, 0) == 0 && pop_key_bits(kBench.link_bits, 8) == 0 &&
+                  pop_key_mask(0) == 0u, "no key below 9 bits");
+// the same scene with leaves of <= 16: four count bits, 10 key bits
+static_assert(link_layout(66453u, 16, 9000u).link_bits == 21 && pop_key_bits(21, -1) == 10, "leaf_max 16");
+// 2^21 triangles: the null leaf's record needs 22 bits; with leaves of <= 2 only 8 bits stay, so no key
+static_assert(link_layout(1u << 21, 2, 1u << 20).link_bits == 23 && pop_key_bits(23, -1) == 0, "2^21 triangles");
+static_assert(link_layout(1u << 21, 1, 1u << 21).link_bits == 22 && pop_key_bits(22, -1) == 9, "2^21, leaf_max 1");
+// tiny scenes: the key is capped at 16 bits; a tree of many nodes and few records is sized by its nodes
+static_assert(pop_key_bits(link_layout(12u, 2, 5u).link_bits, -1) == 16 && pop_key_mask(16) == 0x7FFF8000u, "cap 16");
+static_assert(link_layout(3u, 1, 1000u).link_bits == 10, "node index decides");
+// the widest layout is the old fixed one: count at bit 27, all of bits 30..0 used
+static_assert(link_layout((1u << 27) - 1u, 16, 1u << 26).link_bits == 31, "2^27 - 1 triangles still fit");
+// pack / unpack: the link comes back clean, the key is the f32 pattern truncated (a lower bound for tn >= 0)
+constexpr uint32_t kLeaf = leaf_link(2u, 66452u, kBench.count_shift), kMask = pop_key_mask(13);
+constexpr uint32_t kTn = 0x4129999Au;  // 10.6f
+static_assert(leaf_first(kLeaf, kBench.count_shift) == 66452u && leaf_count(kLeaf, kBench.count_shift) == 2u,
+              "leaf decode");
+static_assert(entry_link(entry_pack(kLeaf, kTn, kMask), kMask) == kLeaf, "leaf link survives its key");
+static_assert(entry_link(entry_pack(16699u, kTn, kMask), kMask) == 16699u, "node link survives its key");
+static_assert(entry_key(entry_pack(kLeaf, kTn, kMask), kMask) == 0x41280000u, "key = tn truncated (10.5 <= 10.6)");
+static_assert(entry_key(entry_pack(kLeaf, 0x7F800000u, kMask), kMask) == 0x7F800000u, "+inf stays +inf");
+static_assert(entry_pack(kLeaf, kTn, 0u) == kLeaf && entry_key(kLeaf, 0u) == 0u, "no key field: plain links");
+}  // namespace link_checks
+
 constexpr int kTopNodes = 120;  // BVH4 nodes held in LDS per path block (7.5 KB)
 // The same in the 5-wave path kernels (OCC 5): 5 KB, so a block's LDS is 30 KB
 // (12-entry stack 12 KB, light terms 10 KB, pending ray 3 KB, top nodes 5 KB).
@@ -175,10 +260,19 @@ constexpr int kStackTotal = 128;
 // batched queries: largest exit first ("The walk over
 // the same tree"); row seeding keeps nearest first (tmpt_render.hip view()).
 constexpr int kShadowOrderDefault = 2;
+// Option pop_cull's default (-1) per seeding mode, from the same-box A/B
+// ("A key in the entry's spare bits"): on everywhere.
+// Sample and row seeding gain on the parent by more than three times the A/A
+// spread; pixel seeding only draws level with it, but with the pop's extra
+// instructions in the kernel either way, off would cost it 7 %.  The batched
+// queries and the AOV pass go by sample seeding's.
+constexpr int kPopCullSample = 1, kPopCullPixel = 1, kPopCullRow = 1;
 
 constexpr int kRowSpecMaxGroups = 8;  // speculative row engine: row groups (streams)
 constexpr int kRenderCounters = 48;   // ray / visit / round counters of one render
-constexpr int kTopCounter = 32;       // [32..41] k_path's top-level visit and top-walk round statistics
+constexpr int kWalkCounter = 42;      // [42] stack entries pop culling discarded, [43] of them followed by
+                                      // another stale entry (counting instantiations only)
+constexpr int kTopCounter = 32;      // [32..41] k_path's top-level visit and top-walk round statistics
                                       // (instrumented instantiations only)
 constexpr int kTieCounter = 24;       // [24] tied queries re-answered over the octree, [25] root-box misses,
                                       // [30] crack / flat-triangle queries re-answered over it (ties[6])
@@ -238,6 +332,11 @@ struct Options {
                               // shading round, with no global load in them (-1 = per seeding, 0 off, 1..8)
     int shadow_order = -1;    // any-hit queries: the order a node's children are visited in (-1 = default,
                               // 0 nearest entry first, 1 longest overlap tf - tn first, 2 largest exit tf first)
+    int pop_cull = -1;        // closest-hit queries: a popped stack entry whose key (a lower bound of its child's
+                              // entry distance) already exceeds the best hit is discarded unvisited, and one
+                              // more entry popped (-1 = the seeding's measured default, 0 off, 1 on)
+    int pop_key_cap = -1;     // test hook: at most this many key bits in a stack entry (-1 = no cap; below
+                              // kPopKeyMin there is no key and nothing is culled)
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
     int denoise_lds = -1;     // tmpt_denoise: levels of stride 1 and 2 read an LDS tile + halo (1), every level
                               // reads global memory directly (0), or the measured choice per stride (-1)
@@ -253,6 +352,7 @@ struct Scene {
     int32_t max_depth = 0;  // of the LBVH (Karras builder)
     Bvh4Node* nodes4 = nullptr;
     int32_t n_nodes4 = 0, depth4 = 0, leaf_max = 0, ploc_iters = 0;
+    int32_t count_shift = 0, link_bits = 31;  // the links' layout (link_layout), fixed by the build
     TriPre* tri_pre = nullptr;
     TriOrig* tri_orig = nullptr;
     void* soa_buf = nullptr;  // layout=soa: the planes of SoaScene, one allocation
@@ -309,6 +409,7 @@ struct Scene {
     int32_t redo_launches = 0;  // k_redo launches of the last render
     int32_t tie_path = 0;       // tmpt_stats.tie_path of the last render
     bool row_render = false;    // the render in progress is row-seeded (view(): shadow_order's default)
+    bool pixel_render = false;  // ... is pixel-seeded (view(): pop_cull's default)
     double redo_ms = 0.0;       // and their time (not in extend_ms)
     uint64_t redo_rays = 0;     // and their rays (in the render's count)
     // speculative row seeding (tmpt_render.hip render_rowspec): jump tables

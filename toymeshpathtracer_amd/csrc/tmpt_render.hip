@@ -1829,6 +1829,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                             done = trav_step4q2_mixed<COUNT, BLOCK, SL, true, 1, SOA, false, FLAG, true>(sv, r, qany, ts, st,
                                                                                                         c1);
                             (qany ? cnt_s : cnt).nodes += c1.nodes;
+                            cnt.stale += c1.stale;  // (closest-hit lanes only: an any-hit lane discards nothing)
+                            cnt.stale2 += c1.stale2;
                         }
                         if (done) in_query = false;
                         if ((kFull && pc.cost_out) || dp0 > 0.0f) ++psteps;
@@ -1922,6 +1924,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 TravCount& dst = qany ? cnt_s : cnt;
                 dst.nodes += c1.nodes;
                 dst.tris += c1.tris;
+                dst.stale += c1.stale;
+                dst.stale2 += c1.stale2;
                 if ((kFull && pc.cost_out) || dp0 > 0.0f) ++psteps;
             }
             if (PROF) {
@@ -2023,10 +2027,14 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     uint32_t nt = COUNT ? wave_sum(cnt.tris) : 0u;
     uint32_t nvs = COUNT ? wave_sum(cnt_s.nodes) : 0u;
     uint32_t nts = COUNT ? wave_sum(cnt_s.tris) : 0u;
+    uint32_t nst = COUNT ? wave_sum(cnt.stale) : 0u;
+    uint32_t nst2 = COUNT ? wave_sum(cnt.stale2) : 0u;
     if (lane_id() == 0) {
         atomicAdd(&counters[0], (unsigned long long)(re + rs));
         atomicAdd(&counters[3], (unsigned long long)re);
         if (COUNT) {
+            atomicAdd(&counters[kWalkCounter], (unsigned long long)nst);
+            atomicAdd(&counters[kWalkCounter + 1], (unsigned long long)nst2);
             atomicAdd(&counters[1], (unsigned long long)nv);
             atomicAdd(&counters[2], (unsigned long long)nt);
             atomicAdd(&counters[4], (unsigned long long)nvs);
@@ -2540,11 +2548,21 @@ static float shadow_order_weight(const Options& o, bool row)
     return order == 0 ? 0.0f : order == 1 ? -1.0f : -1024.0f;
 }
 
+// Option pop_cull; its default (-1) from the same-box A/B per seeding mode
+// ("A key in the entry's spare bits").
+static bool pop_cull_on(const Scene& s)
+{
+    if (s.opt.pop_cull >= 0) return s.opt.pop_cull != 0;
+    return (s.row_render ? kPopCullRow : s.pixel_render ? kPopCullPixel : kPopCullSample) != 0;
+}
+
 SceneView view(const Scene& s)
 {
     SceneView v{s.nodes4, s.tri_pre, s.tri_orig, s.n, s.n_nodes4};
     v.soa = s.soa;
     v.any_w = shadow_order_weight(s.opt, s.row_render);
+    v.count_shift = (uint32_t)s.count_shift;
+    v.key_mask = pop_cull_on(s) ? pop_key_mask(pop_key_bits(s.link_bits, s.opt.pop_key_cap)) : 0u;
 #ifdef TMPT_CHECK
     v.chk = s.chk;
     // TMPT_CHECK_SELFTEST=1 (the report's own test, tests/test_gpu_check.py):
@@ -4090,7 +4108,7 @@ int check_report(Scene& s, const char* what)
 int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
                     float* d_hits, int32_t* d_ids)
 {
-    s.row_render = false;
+    s.row_render = s.pixel_render = false;
     if (ensure_counters(s)) return -1;
     TMPT_HIP(hipMemsetAsync(s.ties, 0, 2 * sizeof(unsigned long long), s.stream));
     TMPT_HIP(hipMemsetAsync(s.counters + kCrackCounter, 0, sizeof(unsigned long long), s.stream));
@@ -4209,6 +4227,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
     RenderArgs a = make_args(cam, d);
     bool count = (d->flags & TMPT_FLAG_COUNT_VISITS) != 0;
     s.row_render = d->seed_mode == TMPT_SEED_ROW;  // view(): shadow_order's default
+    s.pixel_render = d->seed_mode == TMPT_SEED_PIXEL;  // view(): pop_cull's default
     // progressive spp: keep per-pixel state for the shard between calls
     const bool progressive = a.smp_begin > 0 || a.smp_end < a.spp;
     if (progressive) {
@@ -4399,6 +4418,18 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
                     "(%.1f wanting, %.1f traversing)\n",
                     c[6], c[6] ? (double)c[7] / c[6] : 0.0, c[8], c[8] ? (double)c[9] / c[8] : 0.0,
                     c[10], c[10] ? (double)c[11] / c[10] : 0.0, c[10] ? (double)c[12] / c[10] : 0.0);
+        if (count && getenv("TMPT_ROUND_LOG")) {  // pop culling (kWalkCounter) and the work per closest-hit query
+            const unsigned long long* w = c + kWalkCounter;
+            const SceneView sv = view(s);
+            fprintf(stderr,
+                    "k_path walk: %d key bits, culling %s; per closest-hit query %.3f node visits, %.3f triangle "
+                    "tests; stale pops discarded %llu (%.4f of closest-hit node visits and discards), followed by another "
+                    "stale entry %.4f\n",
+                    pop_key_bits(s.link_bits, s.opt.pop_key_cap), sv.key_mask ? "on" : "off",
+                    c[3] ? (double)c[1] / c[3] : 0.0, c[3] ? (double)c[2] / c[3] : 0.0, w[0],
+                    c[1] + w[0] ? (double)w[0] / (double)(c[1] + w[0]) : 0.0,
+                    w[0] ? (double)w[1] / w[0] : 0.0);
+        }
         {  // the top levels' share (k_path tv_*, tw_*, pt_top, pt_node_g)
             const unsigned long long* t = c + kTopCounter;
             const unsigned long long nv = c[1] + c[4];

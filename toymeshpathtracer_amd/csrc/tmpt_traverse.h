@@ -86,6 +86,12 @@ typedef __attribute__((address_space(3))) u32x4 lds_u4;
 // ds_write; a generic pointer let it merge the two pop paths into one FLAT
 // load, which goes through the vector-memory address unit (TA) like a global
 // load -- one extra TA slot per traversal step.
+//
+// An entry is a child link with a key in the bits the scene's links leave
+// free (tmpt_internal.h entry_pack): the top bits of the f32 pattern of the
+// child's entry distance, a lower bound of it, which trav_pop compares with
+// the best hit.  The key costs one v_and_or_b32 per pushed child and no LDS
+// or global traffic of its own; LDS and overflow entries are the same words.
 template <int BLOCK, int SL>
 struct TravStack {
     lds_u32* lds;    // &s_stack[threadIdx.x]; entry k at lds[k * BLOCK]
@@ -93,38 +99,44 @@ struct TravStack {
     const lds_u4* top = nullptr;  // LDS copy of BVH4 nodes [0, ntop) (TOPC steps), 4 uint4 each
     uint32_t ntop = 0;
     __device__ __forceinline__ TravStack(uint32_t* l, uint32_t* g) : lds((lds_u32*)l), glob(g) {}
-    __device__ __forceinline__ void push(int& sp, int v)
+    __device__ __forceinline__ void push(int& sp, uint32_t e)
     {
-        if (SL >= kStackTotal || sp < SL) lds[sp * BLOCK] = (uint32_t)v;
-        else glob[sp - SL] = (uint32_t)v;
+        if (SL >= kStackTotal || sp < SL) lds[sp * BLOCK] = e;
+        else glob[sp - SL] = e;
         ++sp;
     }
     // Up to three pushes (c0 first, c2 last = popped first), branch-free while
     // the LDS part has room for three: the valid ones are compacted into
     // consecutive slots by selects and all three slots are written (slots
     // above the new depth are free, so the extra writes are harmless).
-    __device__ __forceinline__ void push3(int& sp, bool v0, int c0, bool v1, int c1, bool v2, int c2)
+    // k0..k2: the children's keys (f32 bits are taken under key_mask; 0: none).
+    __device__ __forceinline__ void push3(int& sp, uint32_t key_mask, bool v0, int c0, float k0, bool v1, int c1,
+                                          float k1, bool v2, int c2, float k2)
     {
+        const uint32_t e0 = entry_pack((uint32_t)c0, __float_as_uint(k0), key_mask);
+        const uint32_t e1 = entry_pack((uint32_t)c1, __float_as_uint(k1), key_mask);
+        const uint32_t e2 = entry_pack((uint32_t)c2, __float_as_uint(k2), key_mask);
         if (sp + 3 <= SL) {
-            const int s0 = v0 ? c0 : (v1 ? c1 : c2);
-            const int s1 = (v0 && v1) ? c1 : c2;
-            lds[sp * BLOCK] = (uint32_t)s0;
-            lds[(sp + 1) * BLOCK] = (uint32_t)s1;
-            lds[(sp + 2) * BLOCK] = (uint32_t)c2;
+            const uint32_t s0 = v0 ? e0 : (v1 ? e1 : e2);
+            const uint32_t s1 = (v0 && v1) ? e1 : e2;
+            lds[sp * BLOCK] = s0;
+            lds[(sp + 1) * BLOCK] = s1;
+            lds[(sp + 2) * BLOCK] = e2;
             sp += (int)v0 + (int)v1 + (int)v2;
         } else {
-            if (v0) push(sp, c0);
-            if (v1) push(sp, c1);
-            if (v2) push(sp, c2);
+            if (v0) push(sp, e0);
+            if (v1) push(sp, e1);
+            if (v2) push(sp, e2);
         }
     }
-    __device__ __forceinline__ int pop(int& sp)
+    // the top entry, key and all
+    __device__ __forceinline__ uint32_t pop(int& sp)
     {
         --sp;
-        if (SL >= kStackTotal) return (int)lds[sp * BLOCK];
+        if (SL >= kStackTotal) return lds[sp * BLOCK];
         uint32_t v = lds[min(sp, SL - 1) * BLOCK];
         if (sp >= SL) v = glob[sp - SL];
-        return (int)v;
+        return v;
     }
 };
 
@@ -149,6 +161,10 @@ struct SceneView {
     // any-hit lane sorts a node's children by tn + any_w * tf instead of tn
     // (0: nearest first, as closest-hit lanes always do)
     float any_w = 0.0f;
+    // the links' layout (tmpt_internal.h link_layout; a scalar operand of the
+    // leaf decode) and the key field of a stack entry (pop_key_mask); 0: no
+    // key is pushed and no pop is culled (option pop_cull off, or no room)
+    uint32_t count_shift = 27, key_mask = 0u;
 #ifdef TMPT_CHECK
     uint32_t* chk = nullptr;  // Scene::chk (tmpt_internal.h kChk*)
 #endif
@@ -176,6 +192,8 @@ __device__ __noinline__ void chk_fail(uint32_t* chk, uint32_t code, int what)
 
 struct TravCount {
     uint32_t nodes = 0, tris = 0;
+    // pop culling: entries discarded, and those of them whose successor was stale as well
+    uint32_t stale = 0, stale2 = 0;
 };
 
 // Resumable traversal state of one lane (registers).
@@ -195,6 +213,52 @@ __device__ __forceinline__ void trav_init(TravState& ts, float tmax)
     ts.best = -1;
     ts.bt = tmax;
     ts.bu = ts.bv = 0.0f;
+}
+
+// The next entry off the stack into ts.node (a clean link: the key is masked
+// off here, once); true when the stack is empty (the query is finished).
+// Pop culling (option pop_cull, SceneView::key_mask): a closest-hit lane discards
+// the entry when its key, a lower bound of the child's entry distance tn,
+// exceeds ts.bt * kTfarSlack -- the step's own child test with today's,
+// smaller bt, so the child would be culled at its parent now and holds no
+// triangle nearer than, or tied with, the best hit -- and pops once more; that
+// second entry is taken as it is (a run of stale entries costs the visits it
+// always did).  Never on ==.  An any-hit lane's limit is +inf (its key bits
+// are never read as a distance: no pattern exceeds +inf); a NEG query pushes
+// no key and discards nothing.  With culling off key_mask is 0: every key
+// reads as 0, which exceeds no bt >= 0.  KIND 1 / 2 (voted rounds): branch-free
+// while the stack is within its LDS part, both candidate entries read at once.
+template <bool COUNT, int KIND, bool NEG, int BLOCK, int SL>
+__device__ __forceinline__ bool trav_pop(const SceneView& sv, bool any, TravState& ts, TravStack<BLOCK, SL>& st,
+                                         TravCount& cnt)
+{
+    const uint32_t km = NEG ? 0u : sv.key_mask;
+    const float lim = any ? INFINITY : ts.bt * kTfarSlack;
+    auto is_stale = [&](uint32_t e) { return !NEG && __uint_as_float(entry_key(e, km)) > lim; };
+    if (KIND != 0 && ts.sp <= SL) {
+        const uint32_t e1 = st.lds[(uint32_t)max(ts.sp - 1, 0) * BLOCK];
+        const uint32_t e2 = st.lds[(uint32_t)max(ts.sp - 2, 0) * BLOCK];
+        const bool stale = is_stale(e1);
+        const int take = stale ? 2 : 1;
+        const bool done = ts.sp < take;
+        if (COUNT && stale && ts.sp >= 1) {
+            ++cnt.stale;
+            if (ts.sp >= 2 && is_stale(e2)) ++cnt.stale2;
+        }
+        ts.node = (int)entry_link(stale ? e2 : e1, km);
+        ts.sp = max(ts.sp - take, 0);
+        return done;
+    }
+    if (ts.sp == 0) return true;
+    uint32_t e = st.pop(ts.sp);
+    if (is_stale(e)) {
+        if (COUNT) ++cnt.stale;
+        if (ts.sp == 0) return true;
+        e = st.pop(ts.sp);
+        if (COUNT && is_stale(e)) ++cnt.stale2;
+    }
+    ts.node = (int)entry_link(e, km);
+    return false;
 }
 
 // One step over BVH4Q (64-B quantised nodes): one node or one leaf.
@@ -310,7 +374,11 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
             const int cn = sab ? cb : ca, cno = sab ? ca : cb;
             if (kn != INFINITY) {
                 if (TMPT_CHK(sv.chk, ts.sp + 3 <= kStackTotal, kChkStack, ts.sp)) return true;
-                st.push3(ts.sp, kbo != INFINITY, cbo, kao != INFINITY, cao, kno != INFINITY, cno);
+                // the sort keys ride along as the entries' keys: for a closest-hit lane
+                // w = 0 and fma(0, tf, tn) is tn itself, >= 0 (tlo clamps it) unless
+                // NEG, which pushes none; an any-hit lane's are never read
+                st.push3(ts.sp, NEG ? 0u : sv.key_mask, kbo != INFINITY, cbo, kbo, kao != INFINITY, cao, kao,
+                         kno != INFINITY, cno, kno);
                 ts.node = cn;
                 return false;
             }
@@ -318,8 +386,9 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
     }
     if (KIND == 2 || (KIND == 0 && ts.node < 0)) {
         const uint32_t code = (uint32_t)ts.node;
-        const uint32_t first = code & kLeafFirstMask;
-        const uint32_t n = ((code >> kLeafCountShift) & 15u) + 1u;
+        // the scene's layout from a scalar operand: two v_bfe, as many VALU as with immediates
+        const uint32_t first = leaf_first(code, (int)sv.count_shift);
+        const uint32_t n = leaf_count(code, (int)sv.count_shift);
         // records [0, n] (record n: the null leaf's)
         if (TMPT_CHK(sv.chk, first + n <= (uint32_t)sv.n + 1u, kChkLeaf, code)) return true;
         const char* base = reinterpret_cast<const char*>(sv.tri_pre);
@@ -408,17 +477,8 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
                 if (tri(p[0], p[1], p[2])) return true;
             }
         }
-        if (KIND == 2 && ts.sp <= SL) {  // branch-free pop from the LDS part
-            const uint32_t top = st.lds[(uint32_t)max(ts.sp - 1, 0) * BLOCK];
-            const bool done = ts.sp == 0;
-            ts.node = (int)top;
-            ts.sp -= done ? 0 : 1;
-            return done;
-        }
     }
-    if (ts.sp == 0) return true;
-    ts.node = st.pop(ts.sp);
-    return false;
+    return trav_pop<COUNT, KIND, NEG>(sv, any, ts, st, cnt);
 }
 
 // ---------------------------------------------------------------- reference octree
