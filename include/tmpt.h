@@ -412,7 +412,28 @@ int tmpt_scene_destroy(tmpt_scene* scene);
  * normal.xyz, t} written where ids[i] >= 0; ids[i] = index of the closest
  * triangle or -1 (the reference returns 1 instead of the index).  any_hit != 0
  * stops at the first accepted triangle (the shadow query's semantics: only
- * ids[i] >= 0 is meaningful).  Host pointers. */
+ * ids[i] >= 0 is meaningful).  Host pointers.
+ *
+ * Domain.  "The closest triangle" is the linear scan over all triangles with
+ * RayIntersectTriangleImproved (maths.cpp:339-380), lowest index on a tie.  The
+ * answers equal it for ray origins within 100 scene diagonals of the scene's
+ * box.  This does not hold for a scene one of whose extents is thousands of
+ * times smaller than another (tests/geometry_cases.py `anisotropic`: 1e3 x 1
+ * x 1e-3).  Cause: Moller-Trumbore's acceptance region widens with distance
+ * (the error of u and v grows with |orig - v0|), the padded leaf box
+ * (kBoxPadRel) does not, so from afar the scan accepts rays that miss the box.
+ * Beyond the domain an answer is still sound: a returned triangle is one the
+ * scan accepts, with its t bits, never nearer than the scan's; only hits can be
+ * lost.  Rays of 40,000 (20,000 from a sphere, 20,000 from an axis, at that many
+ * diagonals) whose answer differs from the scan's, oracle BVH / GPU:
+ *                        10     100      1000         10000
+ *   12 cases (below)    0 / 0   0 / 0   <= 2 / <= 5   <= 73 / <= 88
+ *   anisotropic         0 / 0  95 / 87  2490 / 2438   6333 / 6307
+ * (below: the other ten cases of tests/test_ray_cases.py, suzanne and teapot,
+ * no octree; oracle BVH counts printed by
+ * tests/test_ray_cases.py::test_domain_*, GPU counts by
+ * tests/test_gpu_ray_cases.py::test_beyond_the_domain_is_sound and
+ * ::test_obj_scenes_from_afar, seed 5; DESIGN.md section 2 has every row.) */
 int tmpt_scene_hit(const tmpt_scene* scene, const float* rays, int64_t n, float tmin, float tmax,
                    int32_t any_hit, float* hits, int32_t* ids);
 /* The same with the range per ray, as each HitScene call takes it

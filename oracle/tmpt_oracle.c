@@ -509,7 +509,23 @@ static void oct_hit(const orc_scene* s, int64_t node, v3 ro, v3 rd, v3 inv, floa
 /* ---- exact-semantics BVH (own structure; DESIGN.md "scene query contract") ----
  * Same answer as a linear scan with strict '<' (lowest index among equal t):
  * boxes are inflated and the slab test is slackened so culling is
- * conservative, and ties are broken on the triangle index. */
+ * conservative, and ties are broken on the triangle index.
+ *
+ * Domain of "same answer": ray origins within 100 scene diagonals of the
+ * scene's box.  It does not hold for a scene one of whose extents is thousands
+ * of times smaller than another (geometry_cases.py `anisotropic`).  Cause:
+ * Moller-Trumbore's acceptance region widens with distance (the error of u
+ * and v grows with |orig - v0|), the box padded by BVH_PAD_REL does not, so from
+ * afar the scan accepts rays that miss the padded leaf box.  The device build
+ * (tmpt_bvh.hip) pads by the same rule and constants, so the GPU leaves the
+ * scan where this BVH does.  Rays of 40,000 per cell (far_sphere_M and
+ * far_axis_M of tests/ray_cases.py, seed 5) whose answer differs from the
+ * scan's at M diagonals, this BVH / the GPU:
+ *                        10     100      1000         10000
+ *   12 cases            0 / 0   0 / 0   <= 2 / <= 5   <= 73 / <= 88
+ *   anisotropic         0 / 0  95 / 87  2490 / 2438   6333 / 6307
+ * (this BVH: printed by tests/test_ray_cases.py::test_domain_*; the GPU: by
+ * tests/test_gpu_ray_cases.py; DESIGN.md section 2 has every row.) */
 #define BVH_PAD_REL 1e-5f
 #define BVH_TFAR_SLACK 1.00001f
 

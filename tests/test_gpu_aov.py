@@ -17,28 +17,12 @@ import pytest
 import oracle
 import toymeshpathtracer_amd as tm
 from conftest import ROOT, data
+from render_restate import aov_expect, same_records as _same
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 CHECK_LIB = os.path.join(ROOT, "toymeshpathtracer_amd", "_lib_check", "libtmpt.so")
-
-
-def _dot(a, b):  # glm: (x*x' + y*y') + z*z', one rounding per operation
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
-def _normalize(v):  # v * (1 / sqrt(dot(v, v)))
-    return v * (f32(1) / np.sqrt(_dot(v, v)))
-
-
-LIGHT = _normalize(np.array([-0.7, 1.0, 0.5], f32))
-
-
-def _light_cosine(n, d):
-    nl = np.where((_dot(n, d) < 0)[:, None], n, -n)
-    c = _dot(np.broadcast_to(LIGHT, nl.shape), nl)
-    return np.where(c > 0, c, f32(0)).astype(f32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -53,42 +37,7 @@ def _expect(name, w, h, spp, index=False):
     cam = tm.Camera.for_scene(bmin, bmax, w, h).as_array()
     osc = (oracle.Scene(tris, accel=oracle.ACCEL_BVH, tie=oracle.TIE_INDEX, bmin=bmin, bmax=bmax) if index else
            oracle.Scene(tris, accel=oracle.ACCEL_OCTREE, tie=oracle.TIE_VISIT, bmin=bmin, bmax=bmax))
-    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
-    rays = np.zeros((h, w, spp, 6), f32)
-    for y in range(h):
-        for x in range(w):
-            seed = oracle.pixel_seed(x, y, w)
-            for s in range(spp):
-                st = oracle.sample_seed(seed, s)
-                r = oracle.float01_seq(st, 2)
-                state = int(oracle.xorshift_seq(st, 2)[1])
-                o, d, _ = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
-                rays[y, x, s, :3], rays[y, x, s, 3:] = o, d
-    flat = rays.reshape(-1, 6)
-    ids, hits = osc.hit_batch(flat, 0.001, 1.0e7)
-    hit = ids >= 0
-    lc = _light_cosine(hits[:, 3:6], flat[:, 3:6])
-    want_shadow = hit & (lc > 0)
-    sids, _ = osc.hit_batch(np.concatenate([hits[:, 0:3], np.broadcast_to(LIGHT, (len(flat), 3))], 1), 0.001, 1.0e7)
-    lit = want_shadow & (sids < 0)
-    shape = (h, w, spp)
-    hit, lit, lc, ids = hit.reshape(shape), lit.reshape(shape), lc.reshape(shape), ids.reshape(shape)
-    nrm, t = hits[:, 3:6].reshape(shape + (3,)), hits[:, 6].reshape(shape)
-    rec = np.zeros((h, w), tm.AOV_DTYPE)
-    nsum, dsum, lsum = np.zeros((h, w, 3), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
-    for s in range(spp):  # float32 sums in sample order; a miss adds nothing
-        nsum = np.where(hit[..., s, None], nsum + nrm[..., s, :], nsum)
-        dsum = np.where(hit[..., s], dsum + t[..., s], dsum)
-        lsum = np.where(lit[..., s], lsum + lc[..., s], lsum)
-    recip = f32(1) / f32(spp)
-    rec["normal"], rec["depth"], rec["direct"] = nsum * recip, dsum * recip, lsum * recip
-    rec["tri_id"] = np.where(hit[..., 0], ids[..., 0], -1)
-    rec["hits"], rec["lit"] = hit.sum(-1), lit.sum(-1)
-    per_pixel = hit.sum(-1)
-    counts = dict(hits=int(hit.sum()), misses=int((~hit).sum()),
-                  shadowed=int((want_shadow.reshape(shape) & ~lit).sum()),
-                  partial=int(((per_pixel > 0) & (per_pixel < spp)).sum()))
-    return rec, counts
+    return aov_expect(osc, cam, w, h, spp)
 
 
 def _scene(name, index=False):
@@ -99,15 +48,6 @@ def _scene(name, index=False):
 def _cam(name, w, h):
     _, bmin, bmax = _load(name)
     return tm.Camera.for_scene(bmin, bmax, w, h)
-
-
-def _same(got, want):
-    """Every field of every record, floats as bits."""
-    for f in tm.AOV_DTYPE.names:
-        a, b = np.ascontiguousarray(got[f]), np.ascontiguousarray(want[f])
-        bad = np.argwhere((a.view(np.uint32) != b.view(np.uint32)).reshape(a.shape))
-        assert len(bad) == 0, f"{f}: {len(bad)} differ, first at {bad[0]}: {a[tuple(bad[0])]} vs {b[tuple(bad[0])]}"
-    assert got.tobytes() == want.tobytes()
 
 
 @pytest.mark.parametrize("name,w,h,spp,index", [("suzanne.obj", 32, 18, 4, False), ("teapot.obj", 24, 14, 2, False),

@@ -719,6 +719,21 @@ def test_tiny_scenes(gpu, ntris, engine):
         assert (ids == -1).all()
 
 
+@pytest.mark.parametrize("ntris", [0, 1, 2])
+@pytest.mark.parametrize("engine", [tm.ENGINE_PERSISTENT, tm.ENGINE_MEGAKERNEL])
+def test_tiny_scenes_row_seeding(gpu, ntris, engine):
+    """test_tiny_scenes in the reference's own row seeding: one lane per row
+    (megakernel) and the speculative row engine (persistent)."""
+    tris, bmin, bmax = tm.load_scene(data("cube.obj"))
+    sub = np.ascontiguousarray(tris[:ntris])
+    cam = tm.Camera.for_scene(bmin, bmax, 48, 27)
+    with tm.Scene(sub) as sc:
+        img, rays = sc.trace_image(cam, 48, 27, 3, seed_mode=tm.SEED_ROW, engine=engine)
+    ref, rrays = oracle.Scene(sub, accel=oracle.ACCEL_LINEAR, tie=oracle.TIE_INDEX).render(
+        cam.as_array(), 48, 27, 3, seed_mode=oracle.SEED_ROW)
+    assert rays == rrays and np.array_equal(img, ref)
+
+
 def test_max_spp_and_sample_count_edges(gpu):
     """spp at the reference's maximum (1024, main.cpp:258-280) on a tiny image."""
     tris, bmin, bmax, sc = _scene("cube.obj")

@@ -16,6 +16,7 @@ import pytest
 import oracle
 import toymeshpathtracer_amd as tm
 from conftest import ROOT, data
+from render_restate import pack, radiance_expect, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +39,6 @@ def _cam(name, w, h):
     return tm.Camera.for_scene(bmin, bmax, w, h)
 
 
-def pack(rad):
-    """pack_pixel(col, 1.0f) of a float tile (main.cpp:224-233) in numpy float32."""
-    out = np.full(rad.shape[:-1] + (4,), 255, np.uint8)
-    v = np.minimum(np.maximum(np.sqrt(rad[..., :3]), f32(0)), f32(1)) * f32(255)
-    out[..., :3] = v.astype(np.uint8)
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def _expect(name, w, h, spp, seed_mode, index=False):
     """(float32[h, w, 3] colour sum in sample order times 1/spp, rays) from the
@@ -54,32 +47,7 @@ def _expect(name, w, h, spp, seed_mode, index=False):
     cam = tm.Camera.for_scene(bmin, bmax, w, h).as_array()
     osc = (oracle.Scene(tris, accel=oracle.ACCEL_BVH, tie=oracle.TIE_INDEX, bmin=bmin, bmax=bmax) if index else
            oracle.Scene(tris, accel=oracle.ACCEL_OCTREE, tie=oracle.TIE_VISIT, bmin=bmin, bmax=bmax))
-    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
-    out = np.zeros((h, w, 3), f32)
-    rays = 0
-    for y in range(h):
-        for x in range(w):
-            seed = oracle.pixel_seed(x, y, w)
-            state = seed  # pixel seeding: one stream per pixel, threaded through the samples
-            col = np.zeros(3, f32)
-            for s in range(spp):
-                if seed_mode == tm.SEED_SAMPLE:
-                    state = oracle.sample_seed(seed, s)
-                r = oracle.float01_seq(state, 2)
-                state = int(oracle.xorshift_seq(state, 2)[1])
-                o, d, state = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
-                c, state, n = osc.trace(o, d, state)
-                col = col + c  # float32, sample order
-                rays += n
-            out[y, x] = col * (f32(1) / f32(spp))
-    return out, rays
-
-
-def _same_bits(got, want, what=""):
-    a, b = np.ascontiguousarray(got, f32).view(np.uint32), np.ascontiguousarray(want, f32).view(np.uint32)
-    bad = np.argwhere(a != b)
-    assert len(bad) == 0, f"{what}: {len(bad)} floats differ, first at {bad[0]}: " \
-                          f"{got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}"
+    return radiance_expect(osc, cam, w, h, spp, seed_mode)
 
 
 @pytest.mark.parametrize("seed", [tm.SEED_SAMPLE, tm.SEED_PIXEL], ids=["sample", "pixel"])

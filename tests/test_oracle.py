@@ -102,6 +102,16 @@ def test_bvh_equals_linear_scan(name):
     assert np.array_equal(a[0], b[0])
     h = a[0] >= 0
     assert h.sum() > 100 and np.array_equal(a[1][h].view(np.uint32), b[1][h].view(np.uint32))
+    if name == "suzanne":
+        # origins 100 scene diagonals away (ray_cases.py): still inside the domain on
+        # which the padded leaf boxes cover Moller-Trumbore's acceptance region
+        import ray_cases
+        far = ray_cases.families(tris, 20000, 5)["far_sphere_100"]
+        a = oracle.Scene(tris, accel=oracle.ACCEL_BVH, tie=oracle.TIE_INDEX).hit_batch(far, 0.001, 1e7)
+        b = oracle.Scene(tris, accel=oracle.ACCEL_LINEAR).hit_batch(far, 0.001, 1e7)
+        assert np.array_equal(a[0], b[0])
+        h = a[0] >= 0
+        assert h.sum() > 2000 and np.array_equal(a[1][h].view(np.uint32), b[1][h].view(np.uint32))
 
 
 # ---------------------------------------------------------------- golden fixtures
