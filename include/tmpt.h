@@ -534,6 +534,14 @@ int tmpt_write_png(const char* path, const uint8_t* rgba, int32_t width, int32_t
  * reference has no counterpart; tests compare it with the host libm. */
 int tmpt_unit_sincos(int32_t device, uint32_t key0, uint32_t n, float* out);
 
+/* The multiply-shift divider the path kernel divides by the frame's width and
+ * a unit's block counts with (exact for dividends below 2^31): out[i] = x[i] /
+ * divisor for the n dividends x (host memory), by the host's statement of the
+ * device's expression; mul_shift (may be null) receives the pair.  A check
+ * hook like the one above: tests compare it with integer division.  Additive,
+ * the ABI version stays. */
+int tmpt_fastdiv(uint32_t divisor, const uint32_t* x, uint64_t n, uint32_t* out, uint32_t mul_shift[2]);
+
 const char* tmpt_last_error(void);
 int tmpt_abi_version(void);
 

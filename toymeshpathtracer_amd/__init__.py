@@ -182,7 +182,6 @@ _last_error = _sig("tmpt_last_error", ctypes.c_char_p, [])
 _abi = _sig("tmpt_abi_version", ctypes.c_int, [])
 _unit_sincos = _sig("tmpt_unit_sincos", ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
                                                        ctypes.c_void_p])
-
 #: every symbol include/tmpt.h declares (checked by tests/test_abi.py)
 EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_scene",
            "tmpt_device_count", "tmpt_scene_create", "tmpt_scene_create_ex", "tmpt_scene_set_option",
@@ -190,7 +189,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_render", "tmpt_render_multi", "tmpt_tile_rows", "tmpt_tile_row_to_y", "tmpt_get_stats",
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
-           "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise")
+           "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv")
 
 
 def _check(rc: int, what: str) -> None:
@@ -208,6 +207,19 @@ def unit_sincos(key0: int, n: int, device: int = 0) -> np.ndarray:
     out = np.empty((n, 2), dtype=np.float32)
     _check(_unit_sincos(device, key0, n, out.ctypes.data), "tmpt_unit_sincos")
     return out
+
+
+def fastdiv(divisor: int, x: np.ndarray):
+    """x // divisor by the path kernel's multiply-shift divider (tmpt_internal.h
+    FastDiv; dividends below 2^31), evaluated on the host: (quotients, (mul, shift))."""
+    # bound on first use: an earlier build of the library (TMPT_LIB_PATH, the A/B tools) has no such symbol
+    fn = _sig("tmpt_fastdiv", ctypes.c_int, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p])
+    x = np.ascontiguousarray(x, dtype=np.uint32)
+    out = np.empty_like(x)
+    ms = np.zeros(2, dtype=np.uint32)
+    _check(fn(divisor, x.ctypes.data, x.size, out.ctypes.data, ms.ctypes.data), "tmpt_fastdiv")
+    return out, (int(ms[0]), int(ms[1]))
 
 
 def device_count() -> int:

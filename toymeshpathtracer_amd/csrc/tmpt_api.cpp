@@ -312,6 +312,24 @@ int tmpt_unit_sincos(int32_t device, uint32_t key0, uint32_t n, float* out)
     TMPT_GUARD_END
 }
 
+int tmpt_fastdiv(uint32_t divisor, const uint32_t* x, uint64_t n, uint32_t* out, uint32_t mul_shift[2])
+{
+    TMPT_GUARD_BEGIN
+    if (divisor == 0u || divisor >= (1u << 31)) return bad("tmpt_fastdiv: divisor out of range (1 .. 2^31 - 1)");
+    if ((!x || !out) && n) return bad("tmpt_fastdiv: null argument");
+    const FastDiv f = fastdiv_make(divisor);
+    if (mul_shift) {
+        mul_shift[0] = f.mul;
+        mul_shift[1] = f.shift;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        if (x[i] >= (1u << 31)) return bad("tmpt_fastdiv: dividend out of range (below 2^31)");
+        out[i] = fastdiv(x[i], f);
+    }
+    return 0;
+    TMPT_GUARD_END
+}
+
 int tmpt_load_obj(const char* path, float** out_tris, int32_t* out_n, float out_bmin[3],
                   float out_bmax[3])
 {

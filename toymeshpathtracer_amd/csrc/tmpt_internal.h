@@ -125,6 +125,35 @@ static_assert(entry_key(entry_pack(kLeaf, 0x7F800000u, kMask), kMask) == 0x7F800
 static_assert(entry_pack(kLeaf, kTn, 0u) == kLeaf && entry_key(kLeaf, 0u) == 0u, "no key field: plain links");
 }  // namespace link_checks
 
+// Division by a divisor the host knows (the frame's width, a unit's block
+// counts: wave-uniform, fixed per launch) as a multiply and a shift, in place
+// of the ~25-instruction u32 division sequence the compiler emits for a
+// run-time divisor.  For d >= 1 with l = ceil(log2 d):
+//   mul = ceil(2^(31 + l) / d)  (< 2^32: d > 2^(l-1)),  shift = l,
+//   x / d = (x * mul) >> (31 + l) = mulhi(2x, mul) >> l     for every x < 2^31
+// (Granlund & Montgomery 1994, N = 31: mul * d = 2^(31+l) + e with 0 <= e < d
+// <= 2^l, so x * mul / 2^(31+l) exceeds x / d by x * e / (d * 2^(31+l)) < 1/d,
+// too little to reach the next integer).  2x fits 32 bits, so the device needs
+// no 64-bit product.  Every dividend here is a pixel, row or unit index, and
+// the host keeps those below 2^31 (render_persistent).
+struct FastDiv {
+    uint32_t mul, shift;
+};
+inline FastDiv fastdiv_make(uint32_t d)
+{
+    const uint32_t l = (uint32_t)bits_for(d > 1u ? d - 1u : 0u);
+    const uint64_t p = 1ull << (31u + l);
+    return FastDiv{(uint32_t)((p + d - 1u) / d), l};
+}
+TMPT_HD uint32_t fastdiv(uint32_t x, FastDiv f)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(x << 1, f.mul) >> f.shift;
+#else
+    return (uint32_t)(((uint64_t)(x << 1) * f.mul) >> 32) >> f.shift;
+#endif
+}
+
 constexpr int kTopNodes = 120;  // BVH4 nodes held in LDS per path block (7.5 KB)
 // The same in the 5-wave path kernels (OCC 5): 5 KB, so a block's LDS is 30 KB
 // (12-entry stack 12 KB, light terms 10 KB, pending ray 3 KB, top nodes 5 KB).
@@ -272,6 +301,8 @@ constexpr int kRowSpecMaxGroups = 8;  // speculative row engine: row groups (str
 constexpr int kRenderCounters = 48;   // ray / visit / round counters of one render
 constexpr int kWalkCounter = 42;      // [42] stack entries pop culling discarded, [43] of them followed by
                                       // another stale entry (counting instantiations only)
+constexpr int kCamCounter = 44;       // [44..46] k_path PROF >= 2: shading rounds, those whose camera block runs,
+                                      // the lanes in it
 constexpr int kTopCounter = 32;      // [32..41] k_path's top-level visit and top-walk round statistics
                                       // (instrumented instantiations only)
 constexpr int kTieCounter = 24;       // [24] tied queries re-answered over the octree, [25] root-box misses,

@@ -32,11 +32,21 @@ struct RenderArgs {
     // camera rays take the reference's root box test first (SceneView::oct
     // set and the lens may lie outside the root box: camera_root_check decides)
     int32_t root_check;
+    // the dividers of W and band_rows (k_path's shading round divides by
+    // neither at run time: tmpt_internal.h FastDiv)
+    FastDiv div_w, div_band;
 };
 
 __device__ __forceinline__ int tile_row_to_y(const RenderArgs& a, int lr)
 {
     int lb = lr / a.band_rows, r = lr - lb * a.band_rows;
+    return (lb * a.nshards + a.shard) * a.band_rows + r;
+}
+
+// the same for lr >= 0, by the launch's divider of band_rows
+__device__ __forceinline__ int tile_row_to_y_fd(const RenderArgs& a, int lr)
+{
+    int lb = (int)fastdiv((uint32_t)lr, a.div_band), r = lr - lb * a.band_rows;
     return (lb * a.nshards + a.shard) * a.band_rows + r;
 }
 

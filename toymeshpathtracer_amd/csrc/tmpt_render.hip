@@ -920,6 +920,7 @@ struct PathCtl {
     // units).  With nblk > 1 each sample's colour goes to sbuf[s * slots + pixel]
     // and k_resolve sums them in sample order (main.cpp:218's col += Trace).
     uint32_t nblk, blk;
+    FastDiv div_nblk, div_blk;  // their dividers (the unit decode)
     uint32_t blk0;  // progressive pass: the block of its first sample (units = the pass's blocks)
     // the frame's tail (option sample_tail): units >= ua are single samples,
     // unit ua + v = sample v % blk of block ua + v / blk, so the last units
@@ -1287,6 +1288,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     uint64_t pt_shade = 0, pt_node = 0, pt_leaf = 0, pt_t = PROF ? stamp() : 0;
     // PROF >= 2: the shading round split (pixel fetch, hit/finish shading, camera, query set-up)
     uint64_t ps_fetch = 0, ps_shade = 0, ps_cam = 0, ps_start = 0;
+    // PROF >= 2: shading rounds, those whose camera block runs, the lanes in it
+    uint64_t pc_sr = 0, pc_cr = 0, pc_cl = 0;
     // Top-walk rounds (pc.top_walk) and the top levels' share of the node
     // rounds, wave-uniform.  COUNT: node lane-steps on an LDS-resident node
     // (tv_n), those of them before the query's first other step (tv_lead,
@@ -1446,25 +1449,25 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                         uint32_t q = unit, sub = 0u;  // block, sample within it (tail units)
                         single = unit >= pc.ua;
                         if (single) {
-                            const uint32_t v = unit - pc.ua, qv = v / pc.blk;
+                            const uint32_t v = unit - pc.ua, qv = fastdiv(v, pc.div_blk);
                             q = pc.ua + qv;
                             sub = v - qv * pc.blk;
                         }
-                        pix = q / pc.nblk;
+                        pix = fastdiv(q, pc.div_nblk);
                         smp0 = (q - pix * pc.nblk + pc.blk0) * pc.blk + sub;  // blk0: a progressive pass's first block
                     } else {
                         pix = (kFull && pc.order) ? pc.order[res + k] : res + k;
                     }
                     psteps = 0;
                     has_pix = true;
-                    const int lr = (int)(pix / (uint32_t)a.W);
+                    const int lr = (int)fastdiv(pix, a.div_w);
                     const int x = (int)(pix - (uint32_t)lr * (uint32_t)a.W);
                     if (SAMP == 4) {
                         rng = rss_state(pc.rss, (int)srow, cur_unit);
                     } else if (SAMP >= 2) {
                         rng = pc.ustate[cur_unit];
                     } else if (!kFull || a.smp_begin == 0) {
-                        rng = pixel_seed((uint32_t)x, (uint32_t)tile_row_to_y(a, lr), (uint32_t)a.W);
+                        rng = pixel_seed((uint32_t)x, (uint32_t)tile_row_to_y_fd(a, lr), (uint32_t)a.W);
                         col = mk(0.0f, 0.0f, 0.0f);
                     } else {  // progressive: continue the previous pass's stream and sum
                         const float4 pv = a.prog[pix];
@@ -1747,10 +1750,18 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 ps_shade += t - ps_t;
                 ps_t = t;
             }
+            if (PROF >= 2) {
+                const uint64_t cm = wballot(cam);
+                ++pc_sr;
+                if (cm != 0) {
+                    ++pc_cr;
+                    pc_cl += (uint64_t)__popcll(cm);
+                }
+            }
             if (cam) {  // next camera sample of this lane's pixel (main.cpp:212-216)
-                const int lr = (int)(pix / (uint32_t)a.W);
+                const int lr = (int)fastdiv(pix, a.div_w);
                 const int x = (int)(pix - (uint32_t)lr * (uint32_t)a.W);
-                const uint32_t y = (uint32_t)tile_row_to_y(a, lr);
+                const uint32_t y = (uint32_t)tile_row_to_y_fd(a, lr);
                 if (SAMP == 1) {
                     const uint32_t ps = pixel_seed((uint32_t)x, y, (uint32_t)a.W);
                     rng = (pf_smp == smp && pf_pix == pix) ? (pf0 ^ pf1 ^ pf2 ^ pf3) : sample_seed(a.jt, smp, ps);
@@ -2059,6 +2070,9 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
             atomicAdd(&counters[17], (unsigned long long)ps_shade);
             atomicAdd(&counters[18], (unsigned long long)ps_cam);
             atomicAdd(&counters[19], (unsigned long long)ps_start);
+            atomicAdd(&counters[kCamCounter], (unsigned long long)pc_sr);
+            atomicAdd(&counters[kCamCounter + 1], (unsigned long long)pc_cr);
+            atomicAdd(&counters[kCamCounter + 2], (unsigned long long)pc_cl);
         }
         if (COUNT) {
             atomicAdd(&counters[kTopCounter], (unsigned long long)tv_n);
@@ -2661,6 +2675,8 @@ RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d)
     a.bmask = 2047u;
     a.row_lanes = 1;  // one row per wave: measured fastest
     a.root_check = 0;
+    a.div_w = fastdiv_make((uint32_t)a.W);
+    a.div_band = fastdiv_make((uint32_t)a.band_rows);
     return a;
 }
 
@@ -2949,6 +2965,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                               : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse>);
     const PathFn fn_default = fn;
     int prof = 0;
+    bool prof5 = false;
 #ifdef TMPT_DIAG
     // diagnostic build only: TMPT_PROF=1 s_memtime split of wave time (shading /
     // node / leaf rounds); 2: + shading-round split; 3: + per-round cycle counts
@@ -2961,10 +2978,14 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     if (prof && a.jt)
         fn = prof >= 2 ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 1, kSparse, 2, 0, 1>
                        : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 1, kSparse, 1, 0, 1>;
+    // TMPT_PROF=2 in sample seeding: the shading split of the 5-wave kernel the
+    // product runs (its LDS layout and 96 VGPRs), unless path_waves = 4
+    prof5 = prof == 2 && a.jt && !soa && o.path_waves != 4;
+    if (prof5) fn = k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 2, 0, 1>;
 #endif
     // Sample seeding's path kernels run 5 waves per SIMD (OCC 5: the 30-KB LDS
     // layout, 96 VGPRs; option path_waves): the lanes below are theirs
-    const bool waves5 = a.jt && !count && !prof && !soa && o.path_waves != 4;
+    const bool waves5 = a.jt && !count && (!prof || prof5) && !soa && o.path_waves != 4;
     // Pixel seeding's instantiations too, but only with several pixels per
     // lane: at low load a pixel's sample chain is the frame's critical path
     // and a fifth wave on the SIMD slows every chain (whole renders, 4 / 5
@@ -3144,6 +3165,8 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     pc.P = P;
     pc.nblk = nblk;
     pc.blk = blk;
+    pc.div_nblk = fastdiv_make(nblk);
+    pc.div_blk = fastdiv_make(blk);
     pc.blk0 = blk0;
     pc.ua = ua;
     RenderArgs as = a;  // sample seeding: a lane's run of samples is its block
@@ -4411,6 +4434,10 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
                 fprintf(stderr, "  shading split: ballots+pixel fetch %.1f%%, shade/finish %.1f%%, camera %.1f%%, "
                                 "query set-up %.1f%% (of all wave time)\n",
                         100.0 * c[16] / tot, 100.0 * c[17] / tot, 100.0 * c[18] / tot, 100.0 * c[19] / tot);
+            if (c[kCamCounter])
+                fprintf(stderr, "  camera block: runs in %llu of %llu shading rounds (%.3f), %.2f lanes per run\n",
+                        c[kCamCounter + 1], c[kCamCounter], (double)c[kCamCounter + 1] / c[kCamCounter],
+                        c[kCamCounter + 1] ? (double)c[kCamCounter + 2] / c[kCamCounter + 1] : 0.0);
         }
         if (count && getenv("TMPT_ROUND_LOG"))  // wave-round efficiency
             fprintf(stderr,
