@@ -46,7 +46,8 @@ extern "C" {
                               did not: callers detect the entry point by its symbol;
                               still 9, additive: tmpt_render_radiance (the float frame of a render),
                               tmpt_denoise and tmpt_denoise_desc (the AOV-guided a-trous filter) and the
-                              render option denoise_lds -- again no struct above changed */
+                              render option denoise_lds -- again no struct above changed;
+                              still 9, additive: the check hooks tmpt_scene_dump_bvh and tmpt_radix_sort */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -541,6 +542,69 @@ int tmpt_unit_sincos(int32_t device, uint32_t key0, uint32_t n, float* out);
  * hook like the one above: tests compare it with integer division.  Additive,
  * the ABI version stays. */
 int tmpt_fastdiv(uint32_t divisor, const uint32_t* x, uint64_t n, uint32_t* out, uint32_t mul_shift[2]);
+
+/* Check hook: the BVH a scene holds, as its kernels read it, copied to host
+ * memory.  The scene's stream is synchronised first; no kernel is launched and
+ * nothing of the scene changes.
+ *   nodes  n_nodes4 records of 16 uint32 words (64 B):
+ *          [0..2]  origin.xyz, the f32 bits of the node box's minimum
+ *          [3]     bytes 0..2 the signed exponents ex, ey, ez (scale = 2^e per axis), byte 3 the
+ *                  child-valid mask
+ *          [4..9]  qlo.x, qhi.x, qlo.y, qhi.y, qlo.z, qhi.z: child k's 8-bit plane in byte k of each;
+ *                  the child box is origin + q * 2^e, in exact arithmetic
+ *          [10,11] 0
+ *          [12..15] child links: an internal child is its node index; a leaf is
+ *                  bit 31 | (count - 1) << count_shift | first record
+ *   tris   n + 1 records of 12 words (48 B), in leaf order: v0.xyz, e1 = v1 - v0, e2 = v2 - v0 (f32 bits),
+ *          [9] = 2 x the triangle's index | the flat mark (tmpt_scene_build_octree), [10,11] = 0
+ *   info   {n, n_nodes4, depth4, leaf_max, count_shift, link_bits, builder_iters, 1 if the scene has
+ *          the SoA planes (build option layout=soa) else 0}
+ * layout 0 copies the AoS records; layout 1 puts the same two arrays together again from the
+ * SoA planes (words [10,11], which no plane holds, are 0) and is an error on a scene built
+ * without layout=soa.  nodes = tris = NULL: only info is written (the sizes to allocate).
+ * n = 0: no node record (n_nodes4 = depth4 = leaf_max = 0) and the one all-zero triangle record;
+ * n = 1: one node whose only child is the leaf of record 0 (depth4 = 1).
+ * -22 with a message for a null scene or info, a layout other than 0 / 1, one buffer without the
+ * other, layout 1 on an AoS scene, or a buffer shorter than 16 * n_nodes4 / 12 * (n + 1) words:
+ * all checked before any device call.
+ *
+ * What every build keeps (tests/bvh_check.py checks each from this dump, exhaustively and
+ * with no tolerance; DESIGN.md section 4 "Invariants of the built tree"):
+ *   tree    every node in [0, n_nodes4) is reached from node 0 exactly once; nodes are numbered
+ *           level by level -- depth L's nodes fill one contiguous index range straight after depth
+ *           L-1's (the path kernels copy nodes [0, kTopNodes) to LDS on that), so a child's index
+ *           exceeds its parent's; the depth is depth4 = tmpt_stats.bvh4_depth, 3 * depth4 + 1 <= 128
+ *   order   WITHIN a level the indices come from an atomic counter: two builds of one scene have
+ *           equal node arrays only after renumbering breadth-first in child-slot order
+ *           (bvh_check.canonical); raw they differ (observed: 16,247 of the stand-in's 16,662
+ *           node records between two builds), while the triangle records are equal raw
+ *   slots   valid children fill slots 0..nc-1, mask = (1 << nc) - 1, nc >= 2 (the one-triangle tree:
+ *           1); an empty slot has qlo = 255, qhi = 0 on all three axes and the null-leaf link
+ *           bit 31 | n; words [10,11] are 0; bits 30..link_bits of every link are 0 (the
+ *           traversal ORs its pop key in there), (count_shift, link_bits) = (bits(n),
+ *           max(bits(n) + bits(leaf_max - 1), bits(n - 2))), bits(v) = v's bit length
+ *   leaves  the ranges [first, first + count) partition [0, n); 1 <= count <= leaf_max; under
+ *           collapse=greedy no internal child heads a subtree of <= leaf_max triangles
+ *   records [9] >> 1 over records 0..n-1 is a permutation of 0..n-1; v0, e1, e2 are the f32
+ *           differences bit for bit; record n is all zero; bit 0 of [9] is set exactly on the
+ *           triangles flat on a plane of the scene's octree (none without one)
+ *   boxes   a triangle's box is its f32 min / max widened by kBoxPadRel * (max(|lo|, |hi|) +
+ *           (hi - lo)) + 1e-30f, every operation rounded to f32; a child's decoded box contains
+ *           the union U of the boxes beneath it on all six faces and each face lies less than one
+ *           quantum 2^e outside U; origin = the minimum of the children's U per axis, bit for
+ *           bit; e is the least exponent in [-126, 127] with 255 * 2^e >= max(extent, 1e-30)
+ *           (either neighbour where the extent is within 2^-40 relative of 255 * 2^k) */
+int tmpt_scene_dump_bvh(const tmpt_scene* scene, int32_t layout, uint32_t* nodes, uint64_t node_words,
+                        uint32_t* tris, uint64_t tri_words, int32_t info[8]);
+/* Check hook: the device radix sort the build (Morton keys) and the pixel-seeded renders (the
+ * cost-ordered pixel supply) use, run on caller data: the n pairs (keys[i], vals[i]) (host
+ * memory) are uploaded, sorted on the scene's stream and written back in place.  The scene only
+ * lends its device and stream.  The sort is stable and works in whole 8-bit passes from bit 0:
+ * the pairs come back ordered by keys[i] & mask, mask = the low 8 * ceil(bits / 8) bits (all 32
+ * for bits > 24); bits above the mask do not take part.  -22 for bits outside 1..32, n outside
+ * 0..2^22, a null array with n > 0, or a null scene -- checked in that order, before any
+ * device call; n = 0 does nothing. */
+int tmpt_radix_sort(const tmpt_scene* scene, uint32_t* keys, uint32_t* vals, int64_t n, int32_t bits);
 
 const char* tmpt_last_error(void);
 int tmpt_abi_version(void);

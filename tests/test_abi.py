@@ -130,3 +130,25 @@ def test_stats_mirror_matches_the_struct():
     assert list(tm.RenderStats._fields if hasattr(tm.RenderStats, "_fields") else
                 tm.RenderStats.__dataclass_fields__) == fields
     assert "tie_path" in fields
+
+
+def test_check_hook_arguments_are_checked_before_any_device_work():
+    """tmpt_scene_dump_bvh and tmpt_radix_sort test their arguments first: -22 with a
+    message for each bad one, in the documented order, with no scene and no GPU.  (The
+    checks that need a scene -- a short buffer, SoA asked of an AoS scene -- are in
+    test_gpu_bvh_structure.py.)"""
+    lib = ctypes.CDLL(tm.lib_path)
+    dump, sort = lib.tmpt_scene_dump_bvh, lib.tmpt_radix_sort
+    dump.restype = sort.restype = ctypes.c_int
+    dump.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                     ctypes.c_uint64, ctypes.c_void_p]
+    sort.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32]
+    lib.tmpt_last_error.restype = ctypes.c_char_p
+    info = (ctypes.c_int32 * 8)()
+    assert dump(None, 0, None, 0, None, 0, info) == -22 and b"null argument" in lib.tmpt_last_error()
+    k = (ctypes.c_uint32 * 4)()
+    for args, msg in (((None, k, k, 4, 0), b"bits out of range"), ((None, k, k, 4, 33), b"bits out of range"),
+                      ((None, k, k, -1, 32), b"n out of range"), ((None, k, k, (1 << 22) + 1, 32), b"n out of range"),
+                      ((None, None, k, 4, 32), b"null argument"), ((None, k, None, 4, 32), b"null argument"),
+                      ((None, k, k, 4, 32), b"null scene"), ((None, None, None, 0, 8), b"null scene")):
+        assert sort(*args) == -22 and msg in lib.tmpt_last_error(), (args[3:], lib.tmpt_last_error())

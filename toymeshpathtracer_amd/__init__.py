@@ -189,7 +189,8 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_render", "tmpt_render_multi", "tmpt_tile_rows", "tmpt_tile_row_to_y", "tmpt_get_stats",
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
-           "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv")
+           "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
+           "tmpt_scene_dump_bvh", "tmpt_radix_sort")
 
 
 def _check(rc: int, what: str) -> None:
@@ -683,6 +684,41 @@ class Scene:
                         aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
                         img.ctypes.data_as(ctypes.c_void_p)), "denoise")
         return res, img
+
+    def dump_bvh(self, layout: str = "aos") -> dict:
+        """The built BVH as the kernels read it (tmpt_scene_dump_bvh; include/tmpt.h
+        states the encoding and the invariants): ``nodes`` uint32[n_nodes4, 16],
+        ``tris`` uint32[n + 1, 12] and ``info``, a dict of n, n_nodes4, depth4,
+        leaf_max, count_shift, link_bits, builder_iters and soa.  ``layout="soa"``
+        puts the two arrays together again from the SoA planes (an error on a
+        scene built without ``layout=soa``).  Launches no kernel."""
+        if layout not in ("aos", "soa"):
+            raise ValueError("dump_bvh: layout is 'aos' or 'soa'")
+        # bound on first use, as tmpt_fastdiv is
+        fn = _sig("tmpt_scene_dump_bvh", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                                        ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, _i32p])
+        info = np.zeros(8, np.int32)
+        lay = int(layout == "soa")
+        _check(fn(self._h, lay, None, 0, None, 0, info.ctypes.data_as(_i32p)), "dump_bvh")
+        nodes = np.zeros((int(info[1]), 16), np.uint32)
+        tris = np.zeros((int(info[0]) + 1, 12), np.uint32)
+        _check(fn(self._h, lay, nodes.ctypes.data, nodes.size, tris.ctypes.data, tris.size,
+                  info.ctypes.data_as(_i32p)), "dump_bvh")
+        keys = ("n", "n_nodes4", "depth4", "leaf_max", "count_shift", "link_bits", "builder_iters", "soa")
+        return {"nodes": nodes, "tris": tris, "info": dict(zip(keys, (int(v) for v in info)))}
+
+    def radix_sort(self, keys, vals, bits: int = 32):
+        """The device radix sort of the build and the pixel supply on caller data
+        (tmpt_radix_sort): returns (keys, vals) uint32, stably ordered by the low
+        8 * ceil(bits / 8) bits of the key; at most 2^22 pairs."""
+        fn = _sig("tmpt_radix_sort", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_int64, ctypes.c_int32])
+        k = np.array(keys, dtype=np.uint32).reshape(-1)
+        v = np.array(vals, dtype=np.uint32).reshape(-1)
+        if k.shape != v.shape:
+            raise ValueError("radix_sort: keys and vals of one length")
+        _check(fn(self._h, k.ctypes.data, v.ctypes.data, k.size, bits), "radix_sort")
+        return k, v
 
     def stats(self) -> RenderStats:
         s = _Stats()

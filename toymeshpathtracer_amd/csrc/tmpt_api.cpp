@@ -1119,6 +1119,41 @@ int tmpt_get_stats(const tmpt_scene* h, tmpt_stats* o)
     return 0;
 }
 
+int tmpt_scene_dump_bvh(const tmpt_scene* hc, int32_t layout, uint32_t* nodes, uint64_t node_words, uint32_t* tris,
+                        uint64_t tri_words, int32_t info[8])
+{
+    TMPT_GUARD_BEGIN
+    if (!hc || !info) return bad("tmpt_scene_dump_bvh: null argument");
+    if (layout != 0 && layout != 1) return bad("tmpt_scene_dump_bvh: layout is 0 (aos) or 1 (soa)");
+    if ((nodes == nullptr) != (tris == nullptr)) return bad("tmpt_scene_dump_bvh: give both buffers, or neither");
+    Scene& s = const_cast<tmpt_scene*>(hc)->s;
+    const bool has_soa = s.soa_buf != nullptr;
+    if (layout == 1 && !has_soa) return bad("tmpt_scene_dump_bvh: the scene was built without layout=soa");
+    const int32_t out[8] = {s.n, s.n_nodes4, s.depth4, s.leaf_max, s.count_shift, s.link_bits, s.ploc_iters,
+                            has_soa ? 1 : 0};
+    if (nodes && (node_words < 16u * (uint64_t)s.n_nodes4 || tri_words < 12u * ((uint64_t)s.n + 1u)))
+        return bad("tmpt_scene_dump_bvh: short buffer (16 words per node, 12 per triangle record and one more)");
+    memcpy(info, out, sizeof(out));
+    if (!nodes) return 0;
+    TMPT_HIP(hipSetDevice(s.device));
+    return dump_bvh(s, layout == 1, nodes, tris);
+    TMPT_GUARD_END
+}
+
+int tmpt_radix_sort(const tmpt_scene* hc, uint32_t* keys, uint32_t* vals, int64_t n, int32_t bits)
+{
+    TMPT_GUARD_BEGIN
+    if (bits < 1 || bits > 32) return bad("tmpt_radix_sort: bits out of range (1 .. 32)");
+    if (n < 0 || n > (int64_t)kRadixSortHookMax) return bad("tmpt_radix_sort: n out of range (0 .. 2^22)");
+    if (n > 0 && (!keys || !vals)) return bad("tmpt_radix_sort: null argument");
+    if (!hc) return bad("tmpt_radix_sort: null scene");
+    if (n == 0) return 0;
+    Scene& s = const_cast<tmpt_scene*>(hc)->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    return radix_sort_host(s, keys, vals, (int32_t)n, bits);
+    TMPT_GUARD_END
+}
+
 int tmpt_write_png(const char* path, const uint8_t* rgba, int32_t w, int32_t h)
 {
     TMPT_GUARD_BEGIN

@@ -789,6 +789,62 @@ int radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* tkeys, uint32_t* 
 
 size_t radix_sort_hist_words(int32_t n) { return 256 * (size_t)std::max(1, blocks_for(n, kSortTile)); }
 
+// Check hook (tmpt_scene_dump_bvh): the built tree as the kernels read it,
+// copied to host memory -- n_nodes4 nodes of 16 words, n + 1 triangle records
+// of 12 words.  soa: the same two arrays put together again from the SoaScene
+// planes (the padding words, which no plane holds, are 0).  No kernel runs
+// and nothing of the scene changes.
+int dump_bvh(Scene& s, bool soa, uint32_t* nodes, uint32_t* tris)
+{
+    TMPT_HIP(hipStreamSynchronize(s.stream));
+    const size_t n4 = (size_t)s.n_nodes4, n1 = (size_t)s.n + 1;
+    if (!soa) {
+        if (n4) TMPT_HIP(hipMemcpy(nodes, s.nodes4, sizeof(Bvh4Node) * n4, hipMemcpyDeviceToHost));
+        TMPT_HIP(hipMemcpy(tris, s.tri_pre, sizeof(TriPre) * n1, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    std::vector<uint32_t> p4(4 * std::max(n4, n1)), p2(2 * std::max(n4, n1));
+    auto plane = [&](const void* src, size_t count, int w, int at, uint32_t* dst, int stride) -> int {
+        std::vector<uint32_t>& p = w == 4 ? p4 : p2;
+        if (!count) return 0;
+        TMPT_HIP(hipMemcpy(p.data(), src, 4 * (size_t)w * count, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < count; ++k)
+            for (int j = 0; j < w; ++j) dst[(size_t)stride * k + at + j] = p[(size_t)w * k + j];
+        return 0;
+    };
+    for (size_t k = 0; k < n4; ++k) nodes[16 * k + 10] = nodes[16 * k + 11] = 0u;
+    for (size_t k = 0; k < n1; ++k) tris[12 * k + 10] = tris[12 * k + 11] = 0u;
+    if (plane(s.soa.na, n4, 4, 0, nodes, 16) || plane(s.soa.nb, n4, 4, 4, nodes, 16) ||
+        plane(s.soa.nc, n4, 2, 8, nodes, 16) || plane(s.soa.nd, n4, 4, 12, nodes, 16) ||
+        plane(s.soa.ta, n1, 4, 0, tris, 12) || plane(s.soa.tb, n1, 4, 4, tris, 12) ||
+        plane(s.soa.tc, n1, 2, 8, tris, 12))
+        return -1;
+    return 0;
+}
+
+// Check hook (tmpt_radix_sort): radix_sort_pairs over the caller's n pairs, on
+// the scene's device and stream; the result comes back in place.
+int radix_sort_host(Scene& s, uint32_t* keys, uint32_t* vals, int32_t n, int bits)
+{
+    const size_t nb = 4 * (size_t)n, hw = radix_sort_hist_words(n);
+    uint32_t* buf = nullptr;  // keys, vals, tkeys, tvals, hist
+    TMPT_HIP(hipMalloc(&buf, 4 * nb + 4 * hw));
+    uint32_t* d[4] = {buf, buf + n, buf + 2 * (size_t)n, buf + 3 * (size_t)n};
+    hipError_t e = hipMemcpyAsync(d[0], keys, nb, hipMemcpyHostToDevice, s.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d[1], vals, nb, hipMemcpyHostToDevice, s.stream);
+    if (e == hipSuccess) {
+        const int which = radix_sort_pairs(d[0], d[1], d[2], d[3], n, bits, buf + 4 * (size_t)n, s.stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(keys, d[2 * which], nb, hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(vals, d[2 * which + 1], nb, hipMemcpyDeviceToHost, s.stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s.stream);
+    (void)hipFree(buf);
+    TMPT_HIP(e);
+    TMPT_HIP(e2);
+    return 0;
+}
+
 namespace {
 
 // Leaf-ordered triangle records and the top-down collapse of one binary tree

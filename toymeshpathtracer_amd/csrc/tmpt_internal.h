@@ -3,7 +3,11 @@
 // HBM layout of one scene (DESIGN.md "Data layout in HBM"):
 //   nodes4   Bvh4Node[<= n-1]     64 B  4-wide BVH, quantised child boxes,
 //                                        numbered level by level (the top
-//                                        kTopNodes are copied to LDS)
+//                                        kTopNodes are copied to LDS); within
+//                                        a level in the order of an atomic
+//                                        counter, so two builds are equal only
+//                                        renumbered breadth-first, not raw
+//                                        (include/tmpt.h tmpt_scene_dump_bvh)
 //   tri_pre  TriPre[n + 1]        48 B  leaf order: v0, e1 = v1-v0, e2 = v2-v0,
 //                                        original index (the Moller-Trumbore operands)
 //   tri_orig TriOrig[n]           48 B  original order: v0, v1, v2 and the geometric
@@ -501,6 +505,12 @@ void sample_jump_tables(int32_t spp, std::vector<uint32_t>& tab);
 int radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* tkeys, uint32_t* tvals, int32_t n,
                      int bits, uint32_t* hist, hipStream_t st);
 size_t radix_sort_hist_words(int32_t n);
+// check hooks (tmpt_bvh.hip): the built nodes (16 words each) and triangle
+// records (12 words each) copied to the host, from the AoS records or put
+// together again from the SoA planes; and radix_sort_pairs over host data
+constexpr int32_t kRadixSortHookMax = 1 << 22;
+int dump_bvh(Scene& s, bool soa, uint32_t* nodes, uint32_t* tris);
+int radix_sort_host(Scene& s, uint32_t* keys, uint32_t* vals, int32_t n, int bits);
 
 TMPT_HD float4 f4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
 
