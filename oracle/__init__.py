@@ -8,7 +8,9 @@ function).  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 Pinning: the octree restatement reproduces, bit for bit, the raw-RGBA SHA-256
 prefixes and ray counts of the reference binary recorded in SURVEY.md §8c
 (tests/test_oracle.py), and the reference's committed result{1..4}*.png to
-the statistical level those macOS renders allow.
+the statistical level those macOS renders allow.  tests/test_reference_pin.py
+holds it to what the compiled reference answers on adversarial scenes
+(oracle/ref/Makefile builds the reference; tests/golden/ref/ its answers).
 """
 from __future__ import annotations
 

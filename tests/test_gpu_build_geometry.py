@@ -149,6 +149,11 @@ def _config_id(c):
 
 
 def _camera(tris):
+    """The reference's placement (main.cpp:295-307) over the case's vertex box.
+    It leaves most samples as misses: at 48x27x4 the linear scan counts 5,216 ..
+    6,474 rays for the 5,184 camera samples of every case but two, so at most
+    about a fifth of them hit anything.  test_gpu_reference_mode.py renders the
+    same families through cameras that at least 40 % of the samples hit."""
     v = tris.reshape(-1, 3)
     return tm.Camera.for_scene(v.min(0), v.max(0), W, H)
 
