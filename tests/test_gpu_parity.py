@@ -1037,6 +1037,44 @@ def test_path_waves_same_frame_and_rays(gpu, sponza_path, seed):
         sc.set_option("tie_defer", -1)
 
 
+# the k_path variants (tmpt_render.hip kPathVariants) that none of the cases above
+# or in the other single-process GPU files launches: (id, seeding, scene
+# options, set_option calls, count_visits)
+_UNVISITED_VARIANTS = [
+    # the streaming row engine's full re-trace at 4 waves per SIMD, lowest-index leaves
+    ("row-retrace-4waves-unflagged", "row", None, {"path_waves": 4, "row_flag_leaves": 0}, False),
+    # its workers at 5 blocks per CU (a small frame picks 4 on its own), lowest-index leaves
+    ("row-workers-occ5-unflagged", "row", None, {"row_occ": 5, "row_flag_leaves": 0}, False),
+    # the visit counters over the SoA planes, sample seeding
+    ("sample-count-soa", "sample", {"layout": "soa"}, {}, True),
+]
+
+
+@pytest.mark.parametrize("case", _UNVISITED_VARIANTS, ids=[c[0] for c in _UNVISITED_VARIANTS])
+def test_remaining_path_variants_match_oracle(gpu, case):
+    """Suzanne at the smoke shape, 160x90 at 4 spp, with the options that reach
+    each remaining k_path variant: the oracle octree's frame and ray count,
+    byte for byte."""
+    _, seed, scene_opts, opts, count = case
+    tris, bmin, bmax = tm.load_scene(data("suzanne.obj"))
+    w, h, spp = 160, 90, 4
+    cam = tm.Camera.for_scene(bmin, bmax, w, h)
+    sd, osd = {"row": (tm.SEED_ROW, oracle.SEED_ROW), "sample": (tm.SEED_SAMPLE, oracle.SEED_SAMPLE)}[seed]
+    with tm.Scene(tris, options=scene_opts, bounds=(bmin, bmax)) as sc:
+        for k, v in opts.items():
+            sc.set_option(k, v)
+        img, rays = sc.trace_image(cam, w, h, spp, seed_mode=sd, engine=tm.ENGINE_PERSISTENT, count_visits=count)
+        st = sc.stats()
+    if seed == "row":
+        assert st.iterations == 1  # the streaming engine ran, not its fallback to iterations
+    if count:
+        assert st.node_visits > st.extend_rays and st.tri_tests > 0
+    ref, ref_rays = _ref_oracle(tris, bmin, bmax).render(cam.as_array(), w, h, spp, seed_mode=osd)
+    assert rays == ref_rays
+    diff = np.nonzero((img != ref).any(-1))
+    assert diff[0].size == 0, f"{diff[0].size} pixels differ, first at {list(zip(*diff))[:5]}"
+
+
 @pytest.mark.parametrize("shards", [1, 8])
 def test_tie_defer_same_frame_and_rays(gpu, sponza_path, shards):
     """Deferred ties (option tie_defer): the sample kernel's main loop, built

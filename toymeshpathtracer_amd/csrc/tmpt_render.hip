@@ -21,6 +21,8 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "tmpt_render.h"
@@ -835,25 +837,7 @@ __global__ void __launch_bounds__(kSeg) k_wf_advance(WfState s, int parity, int 
 #ifndef TMPT_RSS_T
 #define TMPT_RSS_T 8
 #endif
-constexpr int kRssT = TMPT_RSS_T;
-#ifndef TMPT_PATH_STEPS
-#define TMPT_PATH_STEPS 16
-#endif
-#ifndef TMPT_PIX_STEPS
-#define TMPT_PIX_STEPS 24
-#endif
-#ifndef TMPT_ROW_STEPS
-#define TMPT_ROW_STEPS 16
-#endif
-#ifndef TMPT_ROW_SHADE_MIN
-#define TMPT_ROW_SHADE_MIN 24
-#endif
-#ifndef TMPT_SHADE_MIN
-#define TMPT_SHADE_MIN 16
-#endif
-#ifndef TMPT_SPARSE
-#define TMPT_SPARSE 2
-#endif  // live pixel windows per row at most kRssT - 1 (plus the demand slot)
+constexpr int kRssT = TMPT_RSS_T;  // live pixel windows per row at most kRssT - 1 (plus the demand slot)
 static_assert(kRssT >= 4 && kRssT <= 31, "the worker's pick key holds the slot in 5 bits");
 constexpr uint32_t kRssM24 = 0xFFFFFFu;
 struct RsStream {
@@ -967,6 +951,84 @@ struct PathCtl {
     // -- with no global load in them (trav_step4q2_mixed TOPONLY).  0 = off.
     uint32_t top_walk;
 };
+
+// ---- k_path's variants
+// What varies between k_path's instantiations, by its template parameters'
+// names (BLOCK is kBlk in all of them; TAIL follows samp, path_tail below).
+// The table after k_path (kPathVariants) lists the ones the library instantiates.
+struct PathVariant {
+    bool count;                     // COUNT: the visit counters
+    int sl, steps, shade_min, occ;  // LDS stack entries per lane, rounds per shading check, lanes that trigger one, blocks per CU
+    int prof;                       // PROF (TMPT_DIAG builds): the wave-time split
+    int help;                       // HELP: idle lanes trace other lanes' shadow queries
+    int samp;                       // SAMP: 0 pixel, 1 sample seeding; 2 / 3 / 4 the row engines' units
+    bool soa;                       // the SoA planes (layout=soa)
+    int ties;                       // TIES: 0 lowest index, 2 flag for the octree, 1 flag and defer
+    bool sums;                      // SUMS: the float sums beside the packed pixels
+};
+
+// The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel
+// seeding and the rows' full re-trace (OCC 5): 30 KB of LDS per block -- a
+// 12-entry LDS stack, the scattered ray's direction only, kTopNodes5 top nodes
+constexpr int kPathSL = 16, kPathSL5 = 12;
+
+// The cadences, each with its A/B macro (tools/ab_build.sh, tools/ab_kpath.py).
+#ifndef TMPT_PATH_STEPS
+#define TMPT_PATH_STEPS 16
+#endif
+#ifndef TMPT_PIX_STEPS
+#define TMPT_PIX_STEPS 24
+#endif
+#ifndef TMPT_ROW_STEPS
+#define TMPT_ROW_STEPS 16
+#endif
+#ifndef TMPT_ROW_SHADE_MIN
+#define TMPT_ROW_SHADE_MIN 24
+#endif
+#ifndef TMPT_SHADE_MIN
+#define TMPT_SHADE_MIN 16
+#endif
+#ifndef TMPT_SPARSE
+#define TMPT_SPARSE 2
+#endif
+#ifndef TMPT_RS_OCC
+#define TMPT_RS_OCC 5
+#endif
+// Sample and pixel seeding (render_persistent): traversal rounds between
+// shading checks / lanes waiting that trigger a shading round (A/B on the
+// bench frame at 1 and 8 shards);
+// sparse-wave shading threshold divisor (k_path TAIL): 2 -- bench frame,
+// pixel seeding 235.2 -> 231.9 ms at N=1, 1/8 shard unchanged (41.0 ms);
+// sample seeding 220.4 -> 218.2 ms at N=1, 29.4 -> 29.0 ms at 1/8
+// (TMPT_PATH_STEPS / TMPT_SHADE_MIN / TMPT_SPARSE: A/B builds, tools/ab_build.sh)
+constexpr int kSampleSteps = TMPT_PATH_STEPS, kShadeMin = TMPT_SHADE_MIN, kSparse = TMPT_SPARSE;
+// pixel seeding's kernels: 24 rounds between shading checks -- re-swept at
+// 5 waves per SIMD (whole renders, steps 16 / 24 / 32: 1/8 shard 36.4 /
+// 35.2 / 36.1 ms, 1/4 63.7 / 63.2 / 65.1, N=1 198.0 / 196.0 / 208.9; the
+// sample kernels 172.3 / 172.8 / 182.9 keep 16; 20 and 28 both lose to 24,
+// +1.4 % at 1/8; profiles/r06_experiments/cadence_5waves*.log,
+// cadence_pixel_20_24_28.log)
+constexpr int kPixSteps = TMPT_PIX_STEPS;
+// The streaming row engine (render_rowstream), SAMP 2 and 4:
+// a shading round once 24 lanes wait (16 before round 6): whole row renders,
+// 16 / 24 / 28 / 32, N=1 1835.9 / 1811.4 / 1811.9 / 1833.8 ms, 1/2 1034.8 /
+// 1023.5 / 1023.6, 1/8 432.1 / 430.4 / 427.6 / 428.3; 24 or 32 rounds per
+// check instead of 16: -0.8 / +1.2 % at N=1 (profiles/r06_experiments/row_cadence*.log)
+constexpr int kRowSteps = TMPT_ROW_STEPS, kRowShadeMin = TMPT_ROW_SHADE_MIN;
+// the iterated row engine (render_rowspec), SAMP 2 and 3: no macro
+constexpr int kRowIterSteps = 16, kRowIterShadeMin = 16;
+// blocks per CU of the shadow-free row units, SAMP 3 and 4 (5 waves per SIMD)
+constexpr int kRsOcc3 = TMPT_RS_OCC;
+// TAIL of a variant: kSparse in sample and pixel seeding, 2 in the row engines
+constexpr int path_tail(int samp) { return samp <= 1 ? kSparse : 2; }
+
+using PathFn = void (*)(SceneView, RenderArgs, PathCtl, uint32_t*, uint32_t*, unsigned long long*);
+
+// The kernel of a variant, or null when the table does not hold it.
+PathFn path_kernel(const PathVariant& v);
+// The same for a render call: 0 and the kernel, or -22 with the variant's
+// fields in the error (set_error) -- never a neighbouring kernel.
+int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn);
 
 constexpr uint32_t kSimdKeys = 8u * 8u * 2u * 16u * 4u;  // XCC x SE x SH x CU x SIMD (HW_ID fields)
 
@@ -2093,6 +2155,116 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     }
 }
 
+// ============================================================ k_path's variants
+// Every k_path the library instantiates, one line per kernel, by who launches
+// it ("The path kernel's variants").  A caller describes
+// the kernel it needs (PathVariant, above k_path) and path_kernel() finds it
+// here; a variant without a line has no kernel, and asking for it is the
+// render call's error.  A new kernel is a new line.
+namespace {
+constexpr bool F = false, T = true;
+constexpr PathVariant kPathVariants[] = {
+    // count sl        steps         shade_min  occ prof help samp soa ties sums
+    // ---- sample seeding (render_persistent, SAMP 1): 4 waves per SIMD ...
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F},   // no octree (or tie_rule index)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F},   // the octree answers flagged ties in the main loop
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 1, F},   // ... or the redo phase does (deferred ties)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, T},   // tmpt_render_radiance without the colour buffer
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, T},
+    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F},   // the visit counters (TIES 0 with the octree too)
+    // ... layout=soa: 4 waves, never flagging or deferring
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F},
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, T},
+    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F},
+    // ... 5 waves per SIMD (the default; option path_waves)
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T},
+    // ---- pixel seeding (render_persistent, SAMP 0): 4 or 5 waves, with or
+    // without the shadow helpers (HELP), lowest-index ties or flagged for the octree
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 2, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 0, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 2, F},
+    {T, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F},      // the visit counters
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 0, F},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 2, F},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 0, F},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 2, F},
+    // ---- the row engines.  Iterated (render_rowspec, and
+    // render_persistent's pixel chains): units in full (SAMP 2), shadow-free (SAMP 3)
+    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, 4, 0, 0, 2, F, 0, F},
+    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, kRsOcc3, 0, 0, 3, F, 0, F},
+    // streaming (render_rowstream): the chain's full re-trace (SAMP 2) at 4 or
+    // 5 waves, the workers (SAMP 4) at 4 waves or kRsOcc3 blocks per CU; ties
+    // flagged for the octree (option row_flag_leaves) or lowest index
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 0, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 2, F},
+    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 0, F},
+    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 2, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 0, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 2, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 0, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 2, F},
+#ifdef TMPT_DIAG
+    // ---- the diagnostic build's wave-time profiles (TMPT_PROF = prof), one
+    // block per CU: pixel seeding 1 / 2 / 3, sample seeding 1 / 2, and the
+    // shading split (2) of the 5-wave sample kernel the product runs
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 1, 0, 0, F, 0, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 2, 0, 0, F, 0, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 3, 0, 0, F, 0, F},
+    {F, kPathSL, kSampleSteps, kShadeMin, 1, 1, 0, 1, F, 0, F},
+    {F, kPathSL, kSampleSteps, kShadeMin, 1, 2, 0, 1, F, 0, F},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 2, 0, 1, F, 0, F},
+#endif
+};
+constexpr size_t kNumPathVariants = sizeof(kPathVariants) / sizeof(kPathVariants[0]);
+
+constexpr bool same_variant(const PathVariant& a, const PathVariant& b)
+{
+    return a.count == b.count && a.sl == b.sl && a.steps == b.steps && a.shade_min == b.shade_min && a.occ == b.occ &&
+           a.prof == b.prof && a.help == b.help && a.samp == b.samp && a.soa == b.soa && a.ties == b.ties &&
+           a.sums == b.sums;
+}
+
+// line I's kernel: the table's fields in k_path's parameter order
+template <size_t I>
+constexpr PathFn variant_kernel()
+{
+    constexpr PathVariant v = kPathVariants[I];
+    return k_path<v.count, kBlk, v.sl, v.steps, v.shade_min, v.occ, path_tail(v.samp), v.prof, v.help, v.samp, v.soa,
+                  v.ties, v.sums>;
+}
+
+template <size_t... I>
+PathFn kernel_at(size_t i, std::index_sequence<I...>)
+{
+    static const PathFn fns[] = {variant_kernel<I>()...};
+    return fns[i];
+}
+}  // namespace
+
+PathFn path_kernel(const PathVariant& v)
+{
+    for (size_t i = 0; i < kNumPathVariants; ++i)
+        if (same_variant(v, kPathVariants[i])) return kernel_at(i, std::make_index_sequence<kNumPathVariants>{});
+    return nullptr;
+}
+
+int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn)
+{
+    fn = path_kernel(v);
+    if (fn) return 0;
+    set_error(std::string(who) + ": no k_path kernel for count " + std::to_string(v.count) + ", sl " +
+              std::to_string(v.sl) + ", steps " + std::to_string(v.steps) + ", shade_min " +
+              std::to_string(v.shade_min) + ", occ " + std::to_string(v.occ) + ", prof " + std::to_string(v.prof) +
+              ", help " + std::to_string(v.help) + ", samp " + std::to_string(v.samp) + ", soa " +
+              std::to_string(v.soa) + ", ties " + std::to_string(v.ties) + ", sums " + std::to_string(v.sums));
+    return -22;
+}
+
 // TMPT_PAIR=<h>: every 64-rank chunk takes h ranks from the expensive end of the
 // order and 64-h from the cheap end, so a wave's cheap pixels finish early and
 // its lanes then help (HELP) with the expensive ones' shadow queries.
@@ -2185,10 +2357,6 @@ __global__ void __launch_bounds__(64) k_resolve_px(const float4* __restrict__ sb
 // chain through the window: take the sample at offset 0, add its colour in
 // sample order, jump to offset + its draws, ...  Each window costs ~draws/2
 // traces per chain sample (speculation), but all of them run in parallel.
-#ifndef TMPT_RS_OCC
-#define TMPT_RS_OCC 5
-#endif
-constexpr int kRsOcc3 = TMPT_RS_OCC;  // blocks per CU of the shadow-free pass (5 waves per SIMD)
 constexpr int kRsMaxWin = 32;  // windows per row and iteration: this pixel + up to 31 lookaheads
 
 struct RowSpec {
@@ -2519,12 +2687,6 @@ __global__ void __launch_bounds__(256) k_rs_count(RowSpec rs, unsigned long long
 
 // ============================================================ host side
 // (kBlk, kSL and the helpers up to make_args: shared with tmpt_aov.hip, tmpt_render.h)
-namespace {
-// the 5-wave path kernels (OCC 5): 30 KB of LDS per block -- a 12-entry LDS
-// stack, the scattered ray's direction only, kTopNodes5 top nodes
-constexpr int kPathSL5 = 12;
-}  // namespace
-
 int occupancy_grid(const void* fn, int block, size_t dyn_lds, int device)
 {
     int per_cu = 0, cus = 0;
@@ -2937,68 +3099,80 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // stream it runs on: the dominant kernel's own time for the roofline
     if (!s.path_ev[0])
         for (auto& e : s.path_ev) TMPT_HIP(hipEventCreate(&e));
-    // traversal rounds between shading checks / lanes waiting that trigger a
-    // shading round (A/B on the bench frame at 1 and 8 shards);
-    // sparse-wave shading threshold divisor (k_path TAIL): 2 -- bench frame,
-    // pixel seeding 235.2 -> 231.9 ms at N=1, 1/8 shard unchanged (41.0 ms);
-    // sample seeding 220.4 -> 218.2 ms at N=1, 29.4 -> 29.0 ms at 1/8
-    // (TMPT_PATH_STEPS / TMPT_SHADE_MIN / TMPT_SPARSE: A/B builds, tools/ab_build.sh)
-    constexpr int kPathSL = 16, kPathSteps = TMPT_PATH_STEPS, kShadeMin = TMPT_SHADE_MIN, kSparse = TMPT_SPARSE;
-    // pixel seeding's kernels: 24 rounds between shading checks -- re-swept at
-    // 5 waves per SIMD (whole renders, steps 16 / 24 / 32: 1/8 shard 36.4 /
-    // 35.2 / 36.1 ms, 1/4 63.7 / 63.2 / 65.1, N=1 198.0 / 196.0 / 208.9; the
-    // sample kernels 172.3 / 172.8 / 182.9 keep 16; 20 and 28 both lose to 24,
-    // +1.4 % at 1/8; profiles/r06_experiments/cadence_5waves*.log,
-    // cadence_pixel_20_24_28.log)
-    constexpr int kPixSteps = TMPT_PIX_STEPS;
-    using PathFn = decltype(&k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse>);
-    // pixel seeding, and sample seeding (its own instantiation: the pixel-mode
-    // kernel keeps its register allocation)
-    // layout=soa: the sample kernel reads the SoA planes (the A/B of DESIGN.md
-    // section 3; the other engines keep the AoS records)
-    const bool soa = s.soa.na != nullptr;
-    PathFn fn = a.jt ? (count ? (soa ? k_path<true, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, true>
-                                     : k_path<true, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1>)
-                              : (soa ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, true>
-                                     : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1>))
-                     : (count ? k_path<true, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse>
-                              : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse>);
-    const PathFn fn_default = fn;
+    // Which k_path: the facts first, then one variant (PathVariant) from them.
+    // Pixel seeding, and sample seeding (its own instantiations: the pixel-mode
+    // kernel keeps its register allocation).
+    const bool jt = a.jt != nullptr;
+    // the reference's octree answers ties (tie_rule visit)
+    const bool oct = s.oct_view && o.tie_rule == 0;
     int prof = 0;
-    bool prof5 = false;
 #ifdef TMPT_DIAG
     // diagnostic build only: TMPT_PROF=1 s_memtime split of wave time (shading /
     // node / leaf rounds); 2: + shading-round split; 3: + per-round cycle counts
     // (more registers: compare its times only among PROF=3 runs)
     if (const char* pe = getenv("TMPT_PROF")) prof = count ? 0 : atoi(pe);
-    if (prof && !a.jt)
-        fn = prof >= 3 ? k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 1, kSparse, 3>
-           : prof == 2 ? k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 1, kSparse, 2>
-                       : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 1, kSparse, 1>;
-    if (prof && a.jt)
-        fn = prof >= 2 ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 1, kSparse, 2, 0, 1>
-                       : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 1, kSparse, 1, 0, 1>;
+#endif
+    // k_path's PROF of that: sample seeding has no level 3
+    const int prof_level = !prof ? 0 : prof >= 3 && !jt ? 3 : prof >= 2 ? 2 : 1;
+    // layout=soa: the sample kernel reads the SoA planes (the A/B of DESIGN.md
+    // section 3; the other engines keep the AoS records, and so do the
+    // profiling kernels)
+    const bool soa = s.soa.na != nullptr;
+    const bool soa_kernel = jt && soa && !prof;
     // TMPT_PROF=2 in sample seeding: the shading split of the 5-wave kernel the
     // product runs (its LDS layout and 96 VGPRs), unless path_waves = 4
-    prof5 = prof == 2 && a.jt && !soa && o.path_waves != 4;
-    if (prof5) fn = k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 2, 0, 1>;
-#endif
+    const bool prof5 = prof == 2 && jt && !soa && o.path_waves != 4;
     // Sample seeding's path kernels run 5 waves per SIMD (OCC 5: the 30-KB LDS
-    // layout, 96 VGPRs; option path_waves): the lanes below are theirs
-    const bool waves5 = a.jt && !count && (!prof || prof5) && !soa && o.path_waves != 4;
+    // layout, 96 VGPRs; option path_waves): the lanes below are theirs.  No
+    // instrumented, profiling (but prof5) or SoA kernel has a 5-wave variant.
+    const bool waves5 = jt && !count && (!prof || prof5) && !soa && o.path_waves != 4;
+    // Ties: the leaves flag them for the octree (TIES 2; 1 when the flagged
+    // samples are deferred, below).  An instrumented or profiling render keeps
+    // the lowest-index leaf (TIES 0) even with the octree, and SoA has no
+    // flagging or deferring variant.
+    const bool flag = oct && !count && !prof && !soa_kernel;
+    // Every field once, from the facts above and those that depend on the
+    // load: 5 waves per SIMD, the shadow helpers, the tie rule (0, or with
+    // `flag` 2 or 1) and the float sums.  prof forces one block per CU (OCC 1)
+    // except the prof5 case, which is a 5-wave kernel.
+    auto variant = [&](bool w5, int help, int ties, bool sums) {
+        PathVariant v{};
+        v.count = count;
+        v.sl = w5 ? kPathSL5 : kPathSL;
+        v.steps = jt ? kSampleSteps : kPixSteps;
+        v.shade_min = kShadeMin;
+        v.occ = w5 ? 5 : prof ? 1 : 4;
+        v.prof = prof_level;
+        v.help = help;
+        v.samp = jt ? 1 : 0;
+        v.soa = soa_kernel;
+        v.ties = ties;
+        v.sums = sums;
+        return v;
+    };
     // Pixel seeding's instantiations too, but only with several pixels per
     // lane: at low load a pixel's sample chain is the frame's critical path
     // and a fifth wave on the SIMD slows every chain (whole renders, 4 / 5
     // waves: N=1 207.2 / 197.6 ms, 1/2 116.9 / 113.9, 1/4 63.6 / 65.7, 1/8
     // 36.2 / 39.1; profiles/r06_experiments/occ5/ab_pixel_waves.log), so from
-    // 3 pixels per 4-wave lane (option path_waves 5 forces it, 4 keeps 4)
-    // (every OCC 5 instantiation has the same LDS and VGPR footprint, so one
-    // of them gives the 5-wave grid)
-    const int grid4 = occupancy_grid((const void*)fn, kBlk, 0, s.device);
-    const int grid5 = occupancy_grid(
-        (const void*)k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 1>, kBlk, 0,
-        s.device);
-    const bool waves5p = !a.jt && !count && !prof &&
+    // 3 pixels per 4-wave lane (option path_waves 5 forces it, 4 keeps 4).
+    // The 4-wave grid is that of the render's kernel before the load-dependent
+    // choices (no helpers, no flagged ties); the 5-wave grid that of the
+    // 5-wave deferring sample kernel, in pixel seeding too (every OCC 5
+    // instantiation has the same LDS and VGPR footprint).
+    PathVariant probe5{};
+    probe5.sl = kPathSL5;
+    probe5.steps = kSampleSteps;
+    probe5.shade_min = kShadeMin;
+    probe5.occ = 5;
+    probe5.samp = 1;
+    probe5.ties = 1;
+    PathFn fn_base, fn_probe5;
+    if (int rc = find_path_kernel(variant(prof5, 0, 0, false), "tmpt_render", fn_base)) return rc;
+    if (int rc = find_path_kernel(probe5, "tmpt_render", fn_probe5)) return rc;
+    const int grid4 = occupancy_grid((const void*)fn_base, kBlk, 0, s.device);
+    const int grid5 = occupancy_grid((const void*)fn_probe5, kBlk, 0, s.device);
+    const bool waves5p = !jt && !count && !prof &&
                          (o.path_waves == 5 || (o.path_waves == 0 && a.slots >= 3 * (int64_t)grid4 * kBlk));
     const int grid = waves5 || waves5p ? grid5 : grid4;
     // Sample seeding: the work units are (pixel, block of blk samples).  The
@@ -3129,23 +3303,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // per resident lane and loses from ~8 (the extra shading code), so it is
     // on at <= 4.5.  Options help and pair override the choice.
     const int64_t lanes = (int64_t)grid * kBlk;
-    int help = ordered && fn == fn_default && 2 * P <= 9 * lanes ? 1 : 0;
-    if (o.help >= 0) help = o.help != 0 && !count && !prof && !a.jt;
+    int help = ordered && !prof && 2 * P <= 9 * lanes ? 1 : 0;  // (ordered: pixel seeding, not instrumented)
+    if (o.help >= 0) help = o.help != 0 && !count && !prof && !jt;
     const uint32_t oct_shadow = oct_shadow_check(s);
     if (oct_shadow) help = 0;  // the helpers' shadow answers are not checked
     int pair = help && ordered ? (2 * P <= 3 * lanes ? 52 : 56) : 0;
     if (o.pair >= 0) pair = o.pair;
-    if (help)
-        fn = waves5p ? k_path<false, kBlk, kPathSL5, kPixSteps, kShadeMin, 5, kSparse, 0, 1>
-                     : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse, 0, 1>;
-    else if (waves5p)
-        fn = k_path<false, kBlk, kPathSL5, kPixSteps, kShadeMin, 5, kSparse>;
-    // pixel seeding with the octree there: the leaves only flag ties (TIES 2)
-    if (!a.jt && !count && !prof && s.oct_view && o.tie_rule == 0)
-        fn = help ? (waves5p ? k_path<false, kBlk, kPathSL5, kPixSteps, kShadeMin, 5, kSparse, 0, 1, 0, false, 2>
-                             : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse, 0, 1, 0, false, 2>)
-                  : (waves5p ? k_path<false, kBlk, kPathSL5, kPixSteps, kShadeMin, 5, kSparse, 0, 0, 0, false, 2>
-                             : k_path<false, kBlk, kPathSL, kPixSteps, kShadeMin, 4, kSparse, 0, 0, 0, false, 2>);
+    const bool w5 = jt ? waves5 : waves5p;
     // stack spill areas for either kind of kernel's lanes (4 waves, 16 LDS
     // entries; 5 waves, 12)
     const size_t ovf_words = std::max((size_t)grid4 * (kStackTotal - kPathSL),
@@ -3207,13 +3371,6 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     }
     pc.chunk = std::min<uint32_t>(kChunk, pc.lane_cap);
     pc.nchunks = (uint32_t)((P + pc.chunk - 1) / pc.chunk);
-    auto final_launch = [&](const RenderArgs& af, int grid_final) -> int {
-        TMPT_HIP(hipEventRecord(s.path_ev[2], s.stream));
-        fn<<<grid_final, kBlk, 0, s.stream>>>(view(s), af, pc, d_out, (uint32_t*)s.ws, d_counters);
-        TMPT_HIP(hipGetLastError());
-        TMPT_HIP(hipEventRecord(s.path_ev[3], s.stream));
-        return 0;
-    };
     if (!ordered) {
         // Deferred ties (PathCtl::redo, k_path DEFER): with per-sample colours
         // (sbuf) a tied sample can be traced again on its own, so the main loop
@@ -3229,10 +3386,10 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // shard (51 samples per lane; inline / deferred with its block rule:
         // 1/4 47.3 / 45.9, 1/8 24.3 / 24.2 ms), so from 48 per lane
         // (profiles/r06_experiments/occ5/ab_low_rules.log)
-        const bool defer = a.jt && !count && !prof && !soa && pc.sbuf && a.root_check == 0 && o.tie_defer != 0 &&
+        const bool defer = jt && !count && !prof && !soa && pc.sbuf && a.root_check == 0 && o.tie_defer != 0 &&
                            !oct_shadow &&
                            (o.tie_defer > 0 || a.slots * (int64_t)a.spp >= (waves5 ? 48 : 192) * lanes);
-        bool redo = defer && s.oct_view && o.tie_rule == 0;
+        bool redo = defer && oct;
         if (redo && o.redo_cap > 0 && s.redo_cap != (uint32_t)o.redo_cap) free_redo(s);  // the test hook's size
         if (redo && s.redo_cap == 0) {
             int64_t cap = std::min<int64_t>(1ll << 31, std::max<int64_t>(1 << 16, a.slots * (int64_t)a.spp / 128));
@@ -3247,32 +3404,20 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // five waves per SIMD (waves5, option path_waves; the 30-KB LDS layout
         // of OCC 5, 96 VGPRs): bench frame, k_path ms, 4 / 5 waves, same box:
         // N=1 185.6 / 171.0, 1/2 94.3 / 87.7
-        PathFn fn_main = fn;
-        if (redo)
-            fn_main = waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 1>
-                             : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 1>;
-        else if (fn == fn_default && a.jt && !count && !soa && s.oct_view && o.tie_rule == 0)
-            fn_main = waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 2>
-                             : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 2>;
-        else if (waves5 && fn == fn_default)
-            fn_main = k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1>;
         // tmpt_render_radiance in sample seeding without the colour buffer (a
-        // pixel is one unit): the kernel chosen above with SUMS, which stores
+        // pixel is one unit): the launch's kernel with SUMS, which stores
         // the pixel's float sum in a.prog beside the packed pixel.  With the
         // buffer k_resolve_px stores it, in pixel seeding k_path<SAMP 0> does.
-        if (a.jt && a.prog && !pc.sbuf) {
-            if (count || prof) {
-                set_error("tmpt_render_radiance: no instrumented kernel stores the float sums");
-                return -22;
-            }
-            const bool oct = s.oct_view && o.tie_rule == 0;
-            fn_main =
-                soa      ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, true, 0, true>
-                : oct    ? (waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 2, true>
-                                   : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 2, true>)
-                : waves5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 0, true>
-                         : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 0, true>;
+        const bool sums = jt && a.prog && !pc.sbuf;
+        if (sums && (count || prof)) {
+            set_error("tmpt_render_radiance: no instrumented kernel stores the float sums");
+            return -22;
         }
+        // the launch's kernel: flagged ties deferred (TIES 1) with the redo list,
+        // answered in the main loop (TIES 2) without
+        PathVariant v_main = variant(w5, help, flag ? (redo ? 1 : 2) : 0, sums);
+        PathFn fn_main;
+        if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
         // the launch's grid is the launched kernel's co-resident block count
         // (the deferred re-traces' completion count relies on it)
         int grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
@@ -3280,7 +3425,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
             return -1;
         }
-        s.tie_path = !(s.oct_view && o.tie_rule == 0) ? 0 : redo ? 2 : redo_nomem ? 3 : 1;
+        s.tie_path = !oct ? 0 : redo ? 2 : redo_nomem ? 3 : 1;
         s.path_launches = 1;
         for (int attempt = 0;; ++attempt) {
             pc.redo = redo ? s.redo : nullptr;
@@ -3306,9 +3451,8 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                 // the same samples) or, failing that, render with the exact kernel
                 if (!(n < (1ull << 31) && alloc_redo(s, (int64_t)n))) {
                     redo = false;
-                    fn_main = waves5
-                                  ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 1, false, 2>
-                                  : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 1, false, 2>;
+                    v_main.ties = 2;  // the same kernel but for the ties: answered in the main loop
+                    if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
                     grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
                     s.redo_samples = 0;
                     s.tie_path = 3;
@@ -3338,9 +3482,12 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         }
         return 0;
     }
-    s.tie_path = s.oct_view && o.tie_rule == 0 ? 1 : 0;  // pixel seeding answers in the main loop
-    // both pixel launches run `fn`: their grid is its own co-resident block
-    // count (`grid` above came from the instantiations the choice started from)
+    s.tie_path = oct ? 1 : 0;  // pixel seeding answers in the main loop
+    // both pixel launches run one kernel -- 4 or 5 waves, with or without the
+    // helpers, ties flagged for the octree when it answers: their grid is its
+    // own co-resident block count (`grid` above came from the two probes)
+    PathFn fn;
+    if (int rc = find_path_kernel(variant(w5, help, flag ? 2 : 0, false), "tmpt_render", fn)) return rc;
     const int grid_px = occupancy_grid((const void*)fn, kBlk, 0, s.device);
     if ((size_t)grid_px * kBlk * (kStackTotal - (waves5p ? kPathSL5 : kPathSL)) > ovf_words) {
         set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
@@ -3439,13 +3586,31 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         pc.dprio[2] = 0.105f;
         pc.dprio_cost = cost;
     }
-    if (final_launch(a2, grid_px)) return -1;
+    TMPT_HIP(hipEventRecord(s.path_ev[2], s.stream));
+    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a2, pc, d_out, (uint32_t*)s.ws, d_counters);
+    TMPT_HIP(hipGetLastError());
+    TMPT_HIP(hipEventRecord(s.path_ev[3], s.stream));
     s.path_launches = 2;
     // tmpt_render_radiance: pass 2 (and k_resolve_chains) left every pixel's
     // float sum in the pilot's state array
     if (a.prog)
         TMPT_HIP(hipMemcpyAsync(a.prog, state, sizeof(float4) * (size_t)P, hipMemcpyDeviceToDevice, s.stream));
     return 0;
+}
+
+// A row engine's k_path variant (PathVariant; the table's rows group): its
+// unit kind, LDS stack, blocks per CU, cadence and tie rule.  The row engines
+// never count, profile, offload shadows, read the SoA planes or store sums.
+static PathVariant row_variant(int samp, int sl, int occ, int steps, int shade_min, int ties)
+{
+    PathVariant v{};
+    v.sl = sl;
+    v.steps = steps;
+    v.shade_min = shade_min;
+    v.occ = occ;
+    v.samp = samp;
+    v.ties = ties;
+    return v;
 }
 
 // Streaming row engine (RsStream above): one k_path<SAMP 4> launch whose first
@@ -3457,29 +3622,25 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
 int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters)
 {
     const Options& o = s.opt;
-    // a shading round once 24 lanes wait (16 before round 6): whole row renders,
-    // 16 / 24 / 28 / 32, N=1 1835.9 / 1811.4 / 1811.9 / 1833.8 ms, 1/2 1034.8 /
-    // 1023.5 / 1023.6, 1/8 432.1 / 430.4 / 427.6 / 428.3; 24 or 32 rounds per
-    // check instead of 16: -0.8 / +1.2 % at N=1 (profiles/r06_experiments/row_cadence*.log)
-    constexpr int kPathSL = 16, kPathSteps = TMPT_ROW_STEPS, kShadeMin = TMPT_ROW_SHADE_MIN, kSparse = 2;
     // with the reference's octree answering (tie_rule visit) the leaves only
     // flag a tie and keep the first triangle met (TIES 2): the flagged query's
     // answer comes from the octree either way, so the lowest-index bookkeeping
     // is not needed (option row_flag_leaves 0 keeps it, for A/B)
     const bool flag = s.oct_view && o.tie_rule == 0 && o.row_flag_leaves;
-    using RsFn = decltype(&k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 2>);
+    const int ties = flag ? 2 : 0;
     // the chain's full re-trace at 5 waves per SIMD (option path_waves, as the
     // sample kernels: the 30-KB LDS layout of OCC 5)
     const bool w5 = o.path_waves != 4;
-    const RsFn fn2 = flag ? (w5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 2, false, 2>
-                                : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 2, false, 2>)
-                          : (w5 ? k_path<false, kBlk, kPathSL5, kPathSteps, kShadeMin, 5, kSparse, 0, 0, 2>
-                                : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 2>);
-    RsFn fn4 = flag ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, kRsOcc3, kSparse, 0, 0, 4, false, 2>
-                    : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, kRsOcc3, kSparse, 0, 0, 4>;
-    // the workers at 4 waves per SIMD (no spills) for light loads (option row_occ)
-    const RsFn fn4_occ4 = flag ? k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 4, false, 2>
-                               : k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 4>;
+    // the workers at kRsOcc3 blocks per CU, or at 4 waves per SIMD (no spills)
+    // for light loads (option row_occ)
+    PathFn fn2, fn4, fn4_occ4;
+    if (int rc = find_path_kernel(row_variant(2, w5 ? kPathSL5 : kPathSL, w5 ? 5 : 4, kRowSteps, kRowShadeMin, ties),
+                                  "render_rowstream", fn2))
+        return rc;
+    if (int rc = find_path_kernel(row_variant(4, kPathSL, kRsOcc3, kRowSteps, kRowShadeMin, ties), "render_rowstream", fn4))
+        return rc;
+    if (int rc = find_path_kernel(row_variant(4, kPathSL, 4, kRowSteps, kRowShadeMin, ties), "render_rowstream", fn4_occ4))
+        return rc;
     const int rows = a.tile_rows;
     const uint32_t W = (uint32_t)a.W, spp = (uint32_t)a.spp, T = (uint32_t)kRssT;
     const size_t lcap = (size_t)a.slots * spp;  // chain samples of the tile
@@ -3749,12 +3910,17 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
     // rows: a.tile_rows chains of W pixels x spp samples; pixel chains (ch):
     // ch->n chains of one pixel x ch->cspp samples
     const int cspp = ch ? ch->cspp : a.spp;
-    constexpr int kPathSL = 16, kPathSteps = 16, kShadeMin = 16, kSparse = 2, kCheck = 64;
-    auto fn = k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, 4, kSparse, 0, 0, 2>;
+    constexpr int kCheck = 64;
+    // the units in full (SAMP 2; lowest-index ties whatever the octree: this
+    // engine has no flagging variant), and
     // the shadow-free pass: its own instantiation (no shadow, light or colour
     // code, no light / next-ray LDS): 96 VGPRs, 5 waves per SIMD (6 waves: 80
     // VGPRs and 21 spilled dwords, neutral)
-    auto fn3 = k_path<false, kBlk, kPathSL, kPathSteps, kShadeMin, kRsOcc3, kSparse, 0, 0, 3>;
+    PathFn fn, fn3;
+    if (int rc = find_path_kernel(row_variant(2, kPathSL, 4, kRowIterSteps, kRowIterShadeMin, 0), "render_rowspec", fn))
+        return rc;
+    if (int rc = find_path_kernel(row_variant(3, kPathSL, kRsOcc3, kRowIterSteps, kRowIterShadeMin, 0), "render_rowspec", fn3))
+        return rc;
     const int grid = occupancy_grid((const void*)fn, kBlk, 0, s.device);
     const int grid3 = occupancy_grid((const void*)fn3, kBlk, 0, s.device);
     const int rows = ch ? ch->n : a.tile_rows;
