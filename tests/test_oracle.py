@@ -307,7 +307,7 @@ def _sample_from_state(sc, cam, x, y, w, h, st):
 
 
 def test_speculative_row_chains_restated():
-    """The speculative row engine's method (tmpt_render.hip render_rowspec),
+    """The speculative row engine's method (tmpt_rows.hip render_rowspec),
     restated in Python over the oracle's primitives: per row and iteration,
     trace one sample at EVERY even RNG offset of a window (and of a lookahead
     window for the next pixel), then walk the chain through them.  The image

@@ -4,8 +4,8 @@ for gfx950, from the compiler's kernel-resource-usage remarks (no GPU needed).
 
   python tools/resource_usage.py [--digest] [source.hip ...] [filter]
 
-Several sources give one table; without a source: the render unit
-(tmpt_render.hip).  --digest adds a column with a
+Several sources give one table; without a source: the path tracer's units
+(RENDER_UNITS: tmpt_render.hip and the engines split off it).  --digest adds a column with a
 digest of each kernel's code bytes (its symbol's range of .text in the unit's
 device code object), so two builds can be compared kernel by kernel:
 
@@ -23,7 +23,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "toymeshpathtracer_amd", "csrc")
-RENDER_UNITS = ("tmpt_render.hip",)
+RENDER_UNITS = ("tmpt_mega.hip", "tmpt_hitscene.hip", "tmpt_wavefront.hip", "tmpt_rows.hip", "tmpt_render.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero",
          f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}", "-O2", "-fno-slp-vectorize"]

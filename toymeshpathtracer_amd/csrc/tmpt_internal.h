@@ -447,7 +447,7 @@ struct Scene {
     bool pixel_render = false;  // ... is pixel-seeded (view(): pop_cull's default)
     double redo_ms = 0.0;       // and their time (not in extend_ms)
     uint64_t redo_rays = 0;     // and their rays (in the render's count)
-    // speculative row seeding (tmpt_render.hip render_rowspec): jump tables
+    // speculative row seeding (tmpt_rows.hip render_rowspec): jump tables
     // M^(2j) for j in [0, jt2_n), and its row/unit buffers
     uint32_t* jt2 = nullptr;
     int32_t jt2_n = 0;

@@ -66,7 +66,7 @@ TMPT_HD float random_float01(uint32_t& state) { return key_to_float01(xorshift32
 // RandomInUnitDisk, maths.cpp:20-28; the draws of one argument list are taken
 // left to right (x first): SURVEY.md §0.4.
 // `draws` counts the RNG draws taken (2 per try; the speculative row engine
-// needs each sample's draw count, tmpt_render.hip render_rowspec).
+// needs each sample's draw count, tmpt_rows.hip render_rowspec).
 TMPT_HD f3 random_in_unit_disk(uint32_t& state, uint32_t& draws)
 {
     f3 p;

@@ -1,0 +1,253 @@
+// tmpt_path.h -- the contract between k_path (tmpt_render.hip) and its three
+// launchers (render_persistent there; render_rowstream and render_rowspec in
+// tmpt_rows.hip): the kernel's control block and what it carries for the row
+// engines, the variants the library instantiates and their lookup, the
+// cadences, and the host functions beside k_path that the row engines call.
+#pragma once
+
+#include "tmpt_render.h"
+
+namespace tmpt {
+
+// Streaming row engine (SAMP 4, render_rowstream): the speculative row chains
+// of render_rowspec without iterations.  One persistent launch: chaser waves
+// (the first blocks, one lane per row) walk each row's chain as soon as the
+// unit it needs is done and plan pixel windows ahead of it; worker waves take
+// units from the rows' windows and trace them shadow-free.  A unit (row,
+// pixel p, offset j) starts at M^(2j) row_seed, like render_rowspec's.
+//   slots[row][kRssT + 1]: pixel windows, word = (p+1) << 48 | q << 24 | hi
+//     (offsets [q, hi) of pixel p not handed out yet; slot p % kRssT; the last
+//     slot is the chain's demand window for the current pixel); workers take
+//     offsets by CAS, the chaser plans and extends by CAS
+//   res[row][p % kRssT][j % R]: a finished unit, word = ((p+1) << 24 | j) << 28
+//     | draws | rays << 14 | closest-hit rays << 19, written by atomicMax, so a
+//     late unit of a pixel kRssT back never overwrites a live one
+//   chainpos[row] = x << 32 | c: the chain's pixel and next sample's offset
+//   list[(row * W + x) * spp + k] = offset of sample k of pixel x on the chain
+//   ctl: [0] rows done, [1] abort, [2] chain progress ticks, [3] error, [4] P,
+//        [5..11] statistics, [12] block arrival tickets (the first nchase are chasers)
+#ifndef TMPT_RSS_T
+#define TMPT_RSS_T 8
+#endif
+constexpr int kRssT = TMPT_RSS_T;  // live pixel windows per row at most kRssT - 1 (plus the demand slot)
+static_assert(kRssT >= 4 && kRssT <= 31, "the worker's pick key holds the slot in 5 bits");
+constexpr uint32_t kRssM24 = 0xFFFFFFu;
+struct RsStream {
+    unsigned long long* __restrict__ slots;
+    unsigned long long* __restrict__ res;
+    unsigned long long* __restrict__ chainpos;
+    uint32_t* __restrict__ list;
+    uint32_t* __restrict__ rowrays;    // [row][2]: chain rays, closest-hit
+    uint32_t* __restrict__ lo;         // [row][kRssT]: chaser-private window starts
+    uint32_t* __restrict__ ctl;
+    const uint32_t* __restrict__ anchors;  // [row][na]: M^(2^15 a) row_seed
+    const uint32_t* __restrict__ t1;       // M^(2c), c < 128 (byte tables)
+    const uint32_t* __restrict__ t2;       // M^(256 b), b < 128
+    uint32_t na, R, rmask;
+    uint32_t jlimit;        // na * 2^14: offsets with an anchor
+    int nrows, nchase, nw;  // rows, chaser blocks, live pixel windows per row
+    float spread;
+    // live windows and spread follow the live rows (the load law of the
+    // launch-time rule, applied as rows finish): room = room_lanes / live rows;
+    // dyn bit 0: windows, bit 1: spread (an option fixes either)
+    float room_lanes;
+    uint32_t dyn;
+    uint32_t watchdog;      // 100-MHz ticks without chain progress before the workers abort
+    int test_abort;         // option rowstream_test_abort: chasers leave at once (the abort path's test)
+};
+
+// M^(2j) row_seed of row `row` (j < na * 2^14)
+__device__ __forceinline__ uint32_t rss_state(const RsStream& S, int row, uint32_t j)
+{
+    uint32_t s = S.anchors[(size_t)row * S.na + (j >> 14)];
+    s = sample_seed(S.t2, (j >> 7) & 127u, s);
+    return sample_seed(S.t1, j & 127u, s);
+}
+
+struct PathCtl {
+    uint32_t* heads;  // kSeg chunk counters, stride kCtr
+    uint32_t nchunks;
+    // SIMD-balanced first chunks (ordered pass, cost-descending chunks): the
+    // wave of rank r on the d-th SIMD to register takes chunk r*nsimd + d (r
+    // even) or r*nsimd + nsimd-1-d (r odd), so every SIMD's resident waves sum
+    // to about the same work.  Every chunk has a claim word: the first chunk
+    // and the segment supply both claim, so a chunk the placement left
+    // unassigned (uneven waves per SIMD) is still taken, and none twice.
+    // simd_reg = 2 words per hardware SIMD key (waves seen, dense index + 1)
+    // plus a dense counter at kSimdKeys*2.  null = off.
+    uint32_t* simd_reg;
+    uint32_t* claim;  // nchunks words, zeroed per launch
+    uint32_t nsimd, wps;
+    int64_t P;
+    const uint32_t* __restrict__ order;  // rank -> pixel, or null
+    uint32_t* __restrict__ cost_out;     // per-pixel traversal steps of this call, or null
+    // dynamic issue priority (longest remaining first): each shading round the
+    // wave estimates its lanes' remaining traversal steps (steps so far per
+    // finished sample x samples left) and sets s_setprio 3/2/1/0 at the
+    // thresholds dprio[0] > dprio[1] > dprio[2] (steps); dprio[0] = 0: off.
+    // With dprio_cost (the pilot pass's per-pixel steps), the thresholds are
+    // fractions of the heaviest pixel's (order[0]) projected remaining steps.
+    float dprio[3];
+    const uint32_t* __restrict__ dprio_cost;
+    uint32_t lane_cap;  // pixels a wave holds at once (64: all lanes)
+    uint32_t chunk;     // ranks per chunk (kChunk, or lane_cap when capped)
+    // Sample seeding: the supply hands out units = (pixel, block of blk
+    // samples), nblk blocks per pixel, unit u = pixel * nblk + block (P counts
+    // units).  With nblk > 1 each sample's colour goes to sbuf[s * slots + pixel]
+    // and k_resolve sums them in sample order (main.cpp:218's col += Trace).
+    uint32_t nblk, blk;
+    FastDiv div_nblk, div_blk;  // their dividers (the unit decode)
+    uint32_t blk0;  // progressive pass: the block of its first sample (units = the pass's blocks)
+    // the frame's tail (option sample_tail): units >= ua are single samples,
+    // unit ua + v = sample v % blk of block ua + v / blk, so the last units
+    // handed out are one sample long, not one block
+    uint32_t ua;
+    float4* __restrict__ sbuf;
+    uint32_t sb_ss, sb_sp;  // sbuf index = sample * sb_ss + pixel * sb_sp ([pixel][sample]: 1, spp)
+    uint32_t pair;          // sample pairs (2k, 2k+1) of a unit written back to back (one 32-B sector)
+    // Speculative row seeding (SAMP 2, render_rowspec): unit u traces ONE
+    // sample of tile pixel upix[u] from RNG state ustate[u] and writes its
+    // colour with w = draws | rays << 27 to rs_out[u], and its final RNG state
+    // to rs_end[u]
+    const uint32_t* __restrict__ upix;
+    const uint32_t* __restrict__ ustate;
+    float4* __restrict__ rs_out;
+    uint32_t* __restrict__ rs_end;
+    const uint32_t* __restrict__ p_dev;  // the unit count (replaces P, nchunks at launch)
+    // no-shadow speculation (option rowspec_noshadow): the speculative pass skips
+    // shadow traversals (they never change a sample's draws); the chain's
+    // samples are traced again in full at the end of the frame, unit u as
+    // sample uslot[u] of its pixel, colour into sbuf (resolved in order)
+    int rs_noshadow;
+    const uint32_t* __restrict__ uslot;
+    RsStream rss;  // SAMP 4
+    // Deferred ties (SAMP 1, k_path DEFER): the main loop carries no octree
+    // walk; a sample whose closest-hit query ends on a flagged tie is dropped
+    // and (pixel, sample) appended to redo (counters[kRedoCounter] counts them,
+    // redo_cap entries are kept, kRedoEmpty until written).  Waves past the
+    // main loop trace the listed samples again, ties settled (redo_sample);
+    // k_redo takes any they leave.
+    uint2* __restrict__ redo;
+    float4* __restrict__ redo_state;  // kRedoState4 float4 per slot: where the dropped path stopped
+    uint32_t redo_cap;
+    uint32_t redo_inline;  // 0 (test hook, option redo_inline): no redo phase, k_redo takes every entry
+    uint32_t redo_lanes;   // lanes per wave that take redo tickets (1..64)
+    // With the octree: shadow answers can need it too (a flat triangle in the
+    // scene, or the light direction can run along a crack; render_persistent
+    // decides) -- the finished shadow queries are checked as closest hits are
+    // (octree_flag), so HELP and DEFER are off then.
+    uint32_t oct_shadow;
+    // Top-walk rounds (option top_walk): at the end of a shading round, up to
+    // this many wave-uniform node rounds for the lanes standing on a node of
+    // the block's LDS copy of the top levels -- every query starts at node 0
+    // -- with no global load in them (trav_step4q2_mixed TOPONLY).  0 = off.
+    uint32_t top_walk;
+};
+
+// ---- k_path's variants
+// What varies between k_path's instantiations, by its template parameters'
+// names (BLOCK is kBlk in all of them; TAIL follows samp, path_tail below).
+// The table after k_path (kPathVariants) lists the ones the library instantiates.
+struct PathVariant {
+    bool count;                     // COUNT: the visit counters
+    int sl, steps, shade_min, occ;  // LDS stack entries per lane, rounds per shading check, lanes that trigger one, blocks per CU
+    int prof;                       // PROF (TMPT_DIAG builds): the wave-time split
+    int help;                       // HELP: idle lanes trace other lanes' shadow queries
+    int samp;                       // SAMP: 0 pixel, 1 sample seeding; 2 / 3 / 4 the row engines' units
+    bool soa;                       // the SoA planes (layout=soa)
+    int ties;                       // TIES: 0 lowest index, 2 flag for the octree, 1 flag and defer
+    bool sums;                      // SUMS: the float sums beside the packed pixels
+};
+
+// The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel
+// seeding and the rows' full re-trace (OCC 5): 30 KB of LDS per block -- a
+// 12-entry LDS stack, the scattered ray's direction only, kTopNodes5 top nodes
+constexpr int kPathSL = 16, kPathSL5 = 12;
+
+// The cadences, each with its A/B macro (tools/ab_build.sh, tools/ab_kpath.py).
+#ifndef TMPT_PATH_STEPS
+#define TMPT_PATH_STEPS 16
+#endif
+#ifndef TMPT_PIX_STEPS
+#define TMPT_PIX_STEPS 24
+#endif
+#ifndef TMPT_ROW_STEPS
+#define TMPT_ROW_STEPS 16
+#endif
+#ifndef TMPT_ROW_SHADE_MIN
+#define TMPT_ROW_SHADE_MIN 24
+#endif
+#ifndef TMPT_SHADE_MIN
+#define TMPT_SHADE_MIN 16
+#endif
+#ifndef TMPT_SPARSE
+#define TMPT_SPARSE 2
+#endif
+#ifndef TMPT_RS_OCC
+#define TMPT_RS_OCC 5
+#endif
+// Sample and pixel seeding (render_persistent): traversal rounds between
+// shading checks / lanes waiting that trigger a shading round (A/B on the
+// bench frame at 1 and 8 shards);
+// sparse-wave shading threshold divisor (k_path TAIL): 2 -- bench frame,
+// pixel seeding 235.2 -> 231.9 ms at N=1, 1/8 shard unchanged (41.0 ms);
+// sample seeding 220.4 -> 218.2 ms at N=1, 29.4 -> 29.0 ms at 1/8
+// (TMPT_PATH_STEPS / TMPT_SHADE_MIN / TMPT_SPARSE: A/B builds, tools/ab_build.sh)
+constexpr int kSampleSteps = TMPT_PATH_STEPS, kShadeMin = TMPT_SHADE_MIN, kSparse = TMPT_SPARSE;
+// pixel seeding's kernels: 24 rounds between shading checks -- re-swept at
+// 5 waves per SIMD (whole renders, steps 16 / 24 / 32: 1/8 shard 36.4 /
+// 35.2 / 36.1 ms, 1/4 63.7 / 63.2 / 65.1, N=1 198.0 / 196.0 / 208.9; the
+// sample kernels 172.3 / 172.8 / 182.9 keep 16; 20 and 28 both lose to 24,
+// +1.4 % at 1/8; profiles/r06_experiments/cadence_5waves*.log,
+// cadence_pixel_20_24_28.log)
+constexpr int kPixSteps = TMPT_PIX_STEPS;
+// The streaming row engine (render_rowstream), SAMP 2 and 4:
+// a shading round once 24 lanes wait (16 before round 6): whole row renders,
+// 16 / 24 / 28 / 32, N=1 1835.9 / 1811.4 / 1811.9 / 1833.8 ms, 1/2 1034.8 /
+// 1023.5 / 1023.6, 1/8 432.1 / 430.4 / 427.6 / 428.3; 24 or 32 rounds per
+// check instead of 16: -0.8 / +1.2 % at N=1 (profiles/r06_experiments/row_cadence*.log)
+constexpr int kRowSteps = TMPT_ROW_STEPS, kRowShadeMin = TMPT_ROW_SHADE_MIN;
+// the iterated row engine (render_rowspec), SAMP 2 and 3: no macro
+constexpr int kRowIterSteps = 16, kRowIterShadeMin = 16;
+// blocks per CU of the shadow-free row units, SAMP 3 and 4 (5 waves per SIMD)
+constexpr int kRsOcc3 = TMPT_RS_OCC;
+// TAIL of a variant: kSparse in sample and pixel seeding, 2 in the row engines
+constexpr int path_tail(int samp) { return samp <= 1 ? kSparse : 2; }
+
+using PathFn = void (*)(SceneView, RenderArgs, PathCtl, uint32_t*, uint32_t*, unsigned long long*);
+
+// The kernel of a variant, or null when the table does not hold it.
+PathFn path_kernel(const PathVariant& v);
+// The same for a render call: 0 and the kernel, or -22 with the variant's
+// fields in the error (set_error) -- never a neighbouring kernel.
+int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn);
+
+// The heaviest pixels of a pixel-seeded frame as speculative chains
+// (render_rowspec's engine with a chain = one pixel): pixel cpix[r], its
+// samples smp0 .. smp0 + cspp - 1, from the state the pilot pass left in
+// cinit[pixel] (colour sum of samples 0 .. smp0-1, RNG state in .w).
+struct PixelChains {
+    const uint32_t* cpix;
+    const float4* cinit;
+    int n, smp0, cspp;
+};
+
+// PathCtl::top_walk and PathCtl::oct_shadow of a launch (beside render_persistent)
+uint32_t top_walk_cap(const Options& o, int seeding);
+uint32_t oct_shadow_check(const Scene& s);
+
+// k_resolve_px (beside k_path) over a whole tile's colour buffer, for the row engines
+void launch_resolve_px(hipStream_t stream, const float4* sbuf, int64_t P, int32_t spp, float spp_recip,
+                       uint32_t* out);
+
+#ifdef TMPT_EXP_WAVETIME  // timeline experiment: per wave, s_memrealtime at start / main loop end / exit
+constexpr int kWaveTimeMax = 16384;
+// g_wavetime (3 * kWaveTimeMax words) / g_rowtime and g_claimtime (kWaveTimeMax
+// words each), defined beside k_path: copied to the host (false: a copy failed), set from it
+bool wavetime_get(unsigned long long* w);
+bool rowtime_get(unsigned long long* r, unsigned long long* cl);
+void wavetime_put(const unsigned long long* w);
+void rowtime_put(const unsigned long long* r);  // both arrays from r
+#endif
+
+}  // namespace tmpt

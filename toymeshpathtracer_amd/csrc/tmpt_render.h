@@ -1,8 +1,12 @@
 // tmpt_render.h -- what the render translation units share (tmpt_render.hip:
-// the path tracer's engines; tmpt_aov.hip: the AOV pass; tmpt_denoise.hip: the
-// filter over a finished frame): the kernel argument
-// block of one render call, the wave helpers, and the host helpers of a render
-// call (defined in tmpt_render.hip).
+// the persistent path engine and the host side of a render call;
+// tmpt_rows.hip: the row engines; tmpt_mega.hip: the megakernel;
+// tmpt_wavefront.hip: the wavefront engine; tmpt_hitscene.hip: the batched
+// queries; tmpt_aov.hip: the AOV pass;
+// tmpt_denoise.hip: the filter over a finished frame): the kernel argument
+// block of one render call, the wave helpers, the host helpers of a render
+// call (defined in tmpt_render.hip) and the entry points of the engines that
+// have a unit of their own.
 #pragma once
 
 #include "tmpt.h"
@@ -59,6 +63,64 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return v;
 }
 
+// wave64 ballot straight from the predicate (HIP's __ballot widens the bool to
+// an int and compares it again: two extra VALU per call in the hot loops)
+__device__ __forceinline__ uint64_t wballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool wany(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
+
+// s_memtime (shader clock), for the PROF build of k_path only
+__device__ __forceinline__ uint64_t stamp()
+{
+    uint64_t t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+
+// Compacted append: every lane of the wave calls; lanes with pred get
+// consecutive slots, one atomic per wave (ballot + mbcnt prefix).
+__device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred)
+{
+    uint64_t m = wballot(pred);
+    if (m == 0) return 0;
+    int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if (lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, leader);
+    uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                               __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    return base + below;
+}
+
+template <int BLOCK, bool COUNT>
+__device__ __forceinline__ void flush_counts(unsigned long long* counters, uint32_t rays,
+                                             const TravCount& cnt)
+{
+    uint32_t r = wave_sum(rays);
+    uint32_t nv = COUNT ? wave_sum(cnt.nodes) : 0u;
+    uint32_t nt = COUNT ? wave_sum(cnt.tris) : 0u;
+    if (lane_id() == 0) {
+        atomicAdd(&counters[0], (unsigned long long)r);
+        if (COUNT) {
+            atomicAdd(&counters[1], (unsigned long long)nv);
+            atomicAdd(&counters[2], (unsigned long long)nt);
+        }
+    }
+}
+
+// Queues are segmented: the P path slots are cut into kSeg contiguous ranges
+// of seg_cap slots (seg_cap a multiple of the 256-slot shade block); segment j
+// of a queue holds only entries of slots in range j, at [j*seg_cap, +count_j).
+// Every counter and fetch head sits on its own 64-B line, so the producers'
+// wave appends and the consumers' chunk reservations spread over kSeg words
+// instead of serialising on one (MI355X_MICROARCH.md: one word saturates at
+// ~88 atomics/us).
+constexpr int kSeg = 64;  // == wave width: one lane probes one segment
+static_assert(kSeg == 64, "segment probing maps segments to the 64 lanes of a wave");
+constexpr int kCtr = 16;  // words between counters (64 B)
+constexpr uint32_t kChunk = 64;  // queue entries a wave reserves per atomic
+
 // ---- host helpers of a render call (tmpt_render.hip)
 constexpr int kBlk = 256;
 constexpr int kSL = 16;  // LDS stack entries per lane
@@ -78,6 +140,20 @@ int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what);
 int32_t camera_root_check(const Scene& s, const Camera& cam);
 // the statistics of the last render, zeroed before a new one
 void reset_render_stats(Scene& s);
+// sample_seed's byte tables for jumps J_i = M^(i * stride), i in [0, count)
+void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& tab);
+
+// ---- the engines outside tmpt_render.hip (its render() picks one)
+// tmpt_mega.hip
+int render_megakernel(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count,
+                      unsigned long long* d_counters);
+// tmpt_wavefront.hip
+int render_wavefront(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count);
+// tmpt_rows.hip
+struct PixelChains;  // tmpt_path.h
+int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters);
+int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters,
+                   const PixelChains* ch = nullptr);
 
 // tmpt_aov.hip: the AOV pass of one shard (tmpt_render_aov), d_out on the device
 int render_aov(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt_aov_pixel* d_out,

@@ -1,17 +1,10 @@
-// tmpt_render.hip -- the path tracer of main.cpp:44-119 / 172-246 on gfx950.
-//
-// Engines (DESIGN.md "Kernels"):
-//  * wavefront (pixel mode): per-pixel path state in HBM (SoA), one slot per
-//    pixel of the tile; every iteration runs
-//        extend  closest-hit traversal of the active queue     (persistent waves)
-//        shade   hit -> shadow ray + next bounce; miss/max depth -> backward
-//                recurrence, accumulate, next camera sample or pixel write
-//        shadow  any-hit traversal of the shadow queue          (persistent waves)
-//    queues are compacted with wave64 ballot + mbcnt prefix and ONE atomic per
-//    wave.  Samples of a pixel stay sequential (its RNG stream threads through
-//    them, main.cpp:204-218), so parallelism is over pixels.
-//  * megakernel: one lane per pixel (pixel mode) or per row (row mode: the
-//    unmodified reference RNG chain, H-way parallel -- a correctness mode).
+// tmpt_render.hip -- the path tracer of main.cpp:44-119 / 172-246 on gfx950:
+// the persistent path engine (k_path and its variants, render_persistent) and
+// the host side of a render call (render(), which tmpt_api.cpp calls).  The
+// row engines launch k_path's row variants from tmpt_rows.hip, through the
+// contract in tmpt_path.h.  The megakernel, the wavefront engine and the
+// batched HitScene have units of their own too (tmpt_mega.hip,
+// tmpt_wavefront.hip, tmpt_hitscene.hip; tmpt_render.h).
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
@@ -25,141 +18,34 @@
 #include <utility>
 #include <vector>
 
-#include "tmpt_render.h"
+#include "tmpt_lane_path.h"
+#include "tmpt_path.h"
 
 namespace tmpt {
 
-// wave64 ballot straight from the predicate (HIP's __ballot widens the bool to
-// an int and compares it again: two extra VALU per call in the hot loops)
-__device__ __forceinline__ uint64_t wballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ bool wany(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-
-// s_memtime (shader clock), for the PROF build of k_path only
-__device__ __forceinline__ uint64_t stamp()
-{
-    uint64_t t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-
-// Compacted append: every lane of the wave calls; lanes with pred get
-// consecutive slots, one atomic per wave (ballot + mbcnt prefix).
-__device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred)
-{
-    uint64_t m = wballot(pred);
-    if (m == 0) return 0;
-    int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if (lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, leader);
-    uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                               __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    return base + below;
-}
-
-template <int BLOCK, bool COUNT>
-__device__ __forceinline__ void flush_counts(unsigned long long* counters, uint32_t rays,
-                                             const TravCount& cnt)
-{
-    uint32_t r = wave_sum(rays);
-    uint32_t nv = COUNT ? wave_sum(cnt.nodes) : 0u;
-    uint32_t nt = COUNT ? wave_sum(cnt.tris) : 0u;
-    if (lane_id() == 0) {
-        atomicAdd(&counters[0], (unsigned long long)r);
-        if (COUNT) {
-            atomicAdd(&counters[1], (unsigned long long)nv);
-            atomicAdd(&counters[2], (unsigned long long)nt);
-        }
-    }
-}
-
-// ============================================================ megakernel
-// Whole query; TOPC: the top BVH4 levels from the block's LDS copy (the
-// latency-bound row chains).
-template <bool ANY, bool COUNT, bool TOPC, int BLOCK, int SL, bool CHECK_ANY = true>
-__device__ __forceinline__ int mega_query(const SceneView& sv, f3 o, f3 d, float& t, float& u, float& v,
-                                          TravStack<BLOCK, SL>& st, TravCount& cnt)
-{
-    return traverse<ANY, COUNT, BLOCK, SL, TOPC, false, false, CHECK_ANY>(sv, make_trav_ray(o, d), kMinT, kMaxT, t, u,
-                                                                          v, st, cnt);
-}
-
-// rays: closest-hit queries, srays: shadow queries (the same counter where the
-// caller does not split them)
-// CHECK_ANY: the shadow answers are checked against the octree (settle_any);
-// the deferred-tie redo passes false (tie_defer is off wherever a shadow
-// answer can need the octree, PathCtl::oct_shadow)
-template <bool COUNT, int BLOCK, int SL, bool TOPC = false, bool CHECK_ANY = true>
-__device__ __forceinline__ f3 trace_path(const SceneView& sv, f3 o, f3 d, uint32_t& rng,
-                                         uint32_t& rays, uint32_t& srays, TravStack<BLOCK, SL>& st, float* lbuf,
-                                         TravCount& cnt, bool root_check, int depth0 = 0)
-{
-    int depth = depth0;  // > 0: a path resumed at its depth0-th closest-hit query, lbuf[0, depth0) set
-    f3 color = mk(0.0f, 0.0f, 0.0f);
-    while (depth < kMaxDepth) {  // Trace, main.cpp:89-110
-        ++rays;
-        float t, u, v;
-        int id = -1;
-        if (depth == 0 && root_check && !octree_root_hit(sv, o, d, kMinT, kMaxT)) {
-            atomicAdd(&sv.oct->ties[1], 1ull);  // the camera ray misses the reference's root box
-        } else {
-            id = mega_query<false, COUNT, TOPC>(sv, o, d, t, u, v, st, cnt);
-        }
-        if (id >= 0) {
-            f3 pos, nrm;
-            hit_record(sv, id, u, v, pos, nrm);
-            ++srays;  // shadow ray, main.cpp:57-59 (always counted)
-            float lc = light_cosine(nrm, d);
-            if (lc > 0.0f) {  // a zero light term does not depend on the answer
-                float ts, us, vs;
-                int sid = mega_query<true, COUNT, TOPC, BLOCK, SL, CHECK_ANY>(sv, pos, light_dir(), ts, us, vs, st, cnt);
-                if (sid >= 0) lc = 0.0f;
-            }
-            lbuf[depth * BLOCK] = lc;
-            f3 rnd = random_unit_vector(rng);  // main.cpp:71-72
-            f3 target = pos + nrm + rnd;
-            d = normalize(target - pos);
-            o = pos;
-            ++depth;
-        } else {
-            color = sky(d);
-            break;
-        }
-    }
-    for (int i = depth - 1; i >= 0; --i) color = backward_step(color, lbuf[i * BLOCK]);
-    return color;
-}
-
-template <bool COUNT, int BLOCK, int SL, bool TOPC = false>
-__device__ __forceinline__ uint32_t render_pixel(const SceneView& sv, const RenderArgs& a, int x,
-                                                 int y, uint32_t& rng, uint32_t& rays,
-                                                 TravStack<BLOCK, SL>& st, float* lbuf,
-                                                 TravCount& cnt)
-{
-    f3 col = mk(0.0f, 0.0f, 0.0f);
-    const uint32_t pseed = rng;
-    for (int s = 0; s < a.spp; ++s) {  // main.cpp:209-219
-        f3 o, d;
-        if (a.jt) rng = sample_seed(a.jt, (uint32_t)s, pseed);  // sample seeding
-        camera_sample(a.cam, (uint32_t)x, (uint32_t)y, a.invW, a.invH, rng, o, d);
-        col = col + trace_path<COUNT, BLOCK, SL, TOPC>(sv, o, d, rng, rays, rays, st, lbuf, cnt, a.root_check != 0);
-    }
-    return pack_pixel(col, a.spp_recip);
-}
-
-#ifdef TMPT_EXP_WALKSTAT
-__device__ unsigned long long g_walkstat[4];
-#endif
-#ifdef TMPT_EXP_CRACKSTAT
-__device__ unsigned long long g_crackstat[4];
-#endif
-#ifdef TMPT_EXP_WAVETIME  // timeline experiment: per wave, s_memrealtime at start / main loop end / exit
-constexpr int kWaveTimeMax = 16384;
+#ifdef TMPT_EXP_WAVETIME  // the timeline experiment's arrays (kWaveTimeMax: tmpt_path.h)
 __device__ unsigned long long g_wavetime[3 * kWaveTimeMax];
 __device__ unsigned long long g_rowtime[kWaveTimeMax];  // streaming row engine: when each row's chain ended
 __device__ unsigned long long g_claimtime[kWaveTimeMax];  // streaming row engine: each worker wave's last claim
+// their copies to and from the host (tmpt_path.h)
+bool wavetime_get(unsigned long long* w)
+{
+    return hipMemcpyFromSymbol(w, HIP_SYMBOL(g_wavetime), 3 * kWaveTimeMax * 8) == hipSuccess;
+}
+bool rowtime_get(unsigned long long* r, unsigned long long* cl)
+{
+    return hipMemcpyFromSymbol(r, HIP_SYMBOL(g_rowtime), kWaveTimeMax * 8) == hipSuccess &&
+           hipMemcpyFromSymbol(cl, HIP_SYMBOL(g_claimtime), kWaveTimeMax * 8) == hipSuccess;
+}
+void wavetime_put(const unsigned long long* w)
+{
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wavetime), w, 3 * kWaveTimeMax * 8);
+}
+void rowtime_put(const unsigned long long* r)
+{
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rowtime), r, kWaveTimeMax * 8);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_claimtime), r, kWaveTimeMax * 8);
+}
 #endif
 
 // ============================================================ octree walk, one wave
@@ -176,7 +62,7 @@ __device__ __forceinline__ int rlane(int v, int l) { return __builtin_amdgcn_rea
 // when that t beats the best so far (strict <, scene.cpp:34).  The walk
 // stops at the first triangle at `target` (nothing is nearer).  The
 // reference visits ~100 nodes per tied query on the bench frame (up to ~950:
-// tools/ diag TMPT_EXP_WALKSTAT, profiles/r04_ties/walkstat_n1.log).
+// profiles/r04_ties/walkstat_n1.log).
 __device__ __forceinline__ OctHit octree_walk_wave(const OctNode* __restrict__ nodes, const int32_t* __restrict__ refs,
                                                    int n_oct, const TriOrig* __restrict__ tris, f3 o, f3 d,
                                                    float tmin, float tmax, float target TMPT_CHK_PARAMS)
@@ -364,440 +250,6 @@ static bool alloc_redo(Scene& s, int64_t cap)
     return true;
 }
 
-template <bool ROW, bool COUNT, int BLOCK, int SL>
-__global__ void __launch_bounds__(BLOCK) k_mega(SceneView sv, RenderArgs a,
-                                                uint32_t* __restrict__ out,
-                                                uint32_t* __restrict__ ovf,
-                                                unsigned long long* __restrict__ counters)
-{
-    __shared__ uint32_t s_stack[SL * BLOCK];
-    __shared__ float s_light[kMaxDepth * BLOCK];
-    const int64_t gtid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    TravStack<BLOCK, SL> st{&s_stack[threadIdx.x], ovf + gtid * (kStackTotal - SL)};
-    float* lbuf = &s_light[threadIdx.x];
-    // ROW (one latency-bound chain per wave): the persistent engine's node step,
-    // with the top BVH4 levels copied to LDS
-    constexpr bool TOPC = ROW;
-    if (TOPC) {
-        __shared__ uint4 s_top[TOPC ? kTopNodes * 4 : 1];
-        const uint32_t ntop = (uint32_t)min(kTopNodes, sv.n_nodes4);
-        const uint4* g = reinterpret_cast<const uint4*>(sv.nodes4);
-        for (uint32_t i = threadIdx.x; i < ntop * 4; i += BLOCK) s_top[i] = g[i];
-        __syncthreads();
-        st.top = (const lds_u4*)s_top;
-        st.ntop = ntop;
-    }
-    uint32_t rays = 0;
-    TravCount cnt;
-    const int64_t items = ROW ? (int64_t)a.tile_rows : a.slots;
-    // ROW: lane l < row_lanes of wave v takes rows v*row_lanes + l, strided
-    // over the grid's waves (one chain per lane, spread over the SIMDs)
-    const int64_t first = ROW ? (lane_id() < a.row_lanes ? (gtid >> 6) * a.row_lanes + lane_id() : items) : gtid;
-    const int64_t stride = ROW ? (int64_t)gridDim.x * (BLOCK / 64) * a.row_lanes : (int64_t)gridDim.x * BLOCK;
-    for (int64_t w = first; w < items; w += stride) {
-        if (ROW) {
-            int lr = (int)w;
-            int y = tile_row_to_y(a, lr);
-            uint32_t rng = row_seed((uint32_t)y);  // main.cpp:204, unmodified
-            for (int x = 0; x < a.W; ++x)
-                out[(int64_t)lr * a.W + x] = render_pixel<COUNT, BLOCK, SL, TOPC>(sv, a, x, y, rng, rays, st, lbuf, cnt);
-        } else {
-            int lr = (int)(w / a.W), x = (int)(w - (int64_t)lr * a.W);
-            int y = tile_row_to_y(a, lr);
-            uint32_t rng = pixel_seed((uint32_t)x, (uint32_t)y, (uint32_t)a.W);
-            out[w] = render_pixel<COUNT, BLOCK, SL, TOPC>(sv, a, x, y, rng, rays, st, lbuf, cnt);
-        }
-    }
-    flush_counts<BLOCK, COUNT>(counters, rays, cnt);
-}
-
-// ============================================================ batched HitScene
-// Scene::HitScene (scene.cpp:86-97) over a batch: rays n x {o.xyz, d.xyz}
-// with one [tmin, tmax] for all (RANGED = 0), or n x {o.xyz, d.xyz, tmin, tmax}
-// (RANGED = 1, the per-call range of scene.h:36-37).  hits n x {pos, normal, t}
-// where ids >= 0.
-// NEG: the range can start behind the origin (every per-ray range, and a
-// single range with tmin < 0): the traversal's far-distance slack by magnitude.
-template <bool ANY, bool RANGED, int BLOCK, int SL, bool SOA = false, bool NEG = RANGED>
-__global__ void __launch_bounds__(BLOCK) k_intersect(SceneView sv, const float* __restrict__ rays,
-                                                     int64_t n, float tmin, float tmax,
-                                                     float* __restrict__ hits,
-                                                     int32_t* __restrict__ ids,
-                                                     uint32_t* __restrict__ ovf)
-{
-    __shared__ uint32_t s_stack[SL * BLOCK];
-    const int64_t gtid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    TravStack<BLOCK, SL> st{&s_stack[threadIdx.x], ovf + gtid * (kStackTotal - SL)};
-    TravCount cnt;
-    constexpr int kStride = RANGED ? 8 : 6;
-    for (int64_t i = gtid; i < n; i += (int64_t)gridDim.x * BLOCK) {
-        const float* r = rays + kStride * i;
-        f3 o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
-        const float t0 = RANGED ? r[6] : tmin, t1 = RANGED ? r[7] : tmax;
-        float t, u, v;
-        int id = -1;
-        // with the reference's octree: its root box test first (scene.cpp:25)
-        if (sv.oct && !octree_root_hit(sv, o, d, t0, t1)) {
-            atomicAdd(&sv.oct->ties[1], 1ull);
-        } else {
-            // a range that may start behind the origin: sign-aware slack (NEG)
-            id = traverse<ANY, false, BLOCK, SL, false, SOA, NEG>(sv, make_trav_ray(o, d), t0, t1, t, u, v, st, cnt);
-        }
-        ids[i] = id;
-        if (id >= 0) {
-            f3 pos, nrm;
-            hit_record(sv, id, u, v, pos, nrm);
-            float* h = hits + 7 * i;
-            h[0] = pos.x; h[1] = pos.y; h[2] = pos.z;
-            h[3] = nrm.x; h[4] = nrm.y; h[5] = nrm.z;
-            h[6] = t;
-        }
-    }
-}
-
-// ============================================================ wavefront
-// Queues are segmented: the P path slots are cut into kSeg contiguous ranges
-// of seg_cap slots (seg_cap a multiple of the 256-slot shade block); segment j
-// of a queue holds only entries of slots in range j, at [j*seg_cap, +count_j).
-// Every counter and fetch head sits on its own 64-B line, so the producers'
-// wave appends and the consumers' chunk reservations spread over kSeg words
-// instead of serialising on one (MI355X_MICROARCH.md: one word saturates at
-// ~88 atomics/us).
-constexpr int kSeg = 64;  // == wave width: one lane probes one segment
-static_assert(kSeg == 64, "segment probing maps segments to the 64 lanes of a wave");
-constexpr int kCtr = 16;  // words between counters (64 B)
-constexpr uint32_t kChunk = 64;  // queue entries a wave reserves per atomic
-constexpr uint32_t kSkip = 0x80000000u;  // queue-entry flag: path stopped at kMaxDepth
-constexpr uint32_t kDone = 0xFFFFFFFFu;  // depth value of a finished pixel
-
-struct WfState {
-    uint32_t* rng;
-    uint32_t* smp;
-    uint32_t* depth;
-    float* col;    // [3][P]
-    float* light;  // [kMaxDepth][P]
-    float* ray;    // [6][P]  o.xyz d.xyz
-    float* hit;    // [3][P]  t u v
-    int32_t* hid;  // [P]
-    float* sho;    // [3][P] shadow origin
-    // Extend queues (per parity): kSeg * nbins sub-queues of seg_cap entries,
-    // sub-queue seg * nbins + bin holding the rays of segment seg whose
-    // direction falls in octant bin (the low log2(nbins) bits of the sign
-    // mask; nbins = 1: no binning), so a wave's 64-entry reservation holds
-    // rays from nearby pixels in one octant (sort-by-bounce: every iteration's
-    // queue is one bounce).  Counters and fetch heads per sub-queue.
-    uint32_t* q[2];
-    uint32_t* qs;    // shadow queue: kSeg segments (shadow rays share one direction)
-    uint32_t* cnt[2];  // extend sub-queue counts per parity, kSeg * nbins counters (stride kCtr)
-    uint32_t* cnt_s;   // shadow queue counts
-    uint32_t* head_e;  // fetch heads
-    uint32_t* head_s;
-    uint32_t* total;   // [0]: entries of the queue the next iteration consumes
-    uint32_t* iter_log;  // optional (TMPT_ITER_LOG): per-iteration queue sizes
-    unsigned long long* tot;  // [0] extend rays [1] shadow rays [2,3] extend node/tri visits [4,5] shadow
-    int64_t P;
-    uint32_t seg_cap;
-    uint32_t nbins;  // 1, 2, 4 or 8
-    int walk_check;  // relaxed head check before a walking wave's atomic (low load, binned queues)
-    int root_check;  // RenderArgs::root_check: camera rays (depth 0) take the root box test
-};
-
-// octant bin of a direction: bit 0 = x < 0, bit 1 = y < 0, bit 2 = z < 0, low bits only
-__device__ __forceinline__ uint32_t dir_bin(f3 d, uint32_t nbins)
-{
-    const uint32_t o = (uint32_t)signbit(d.x) | ((uint32_t)signbit(d.y) << 1) | ((uint32_t)signbit(d.z) << 2);
-    return o & (nbins - 1u);
-}
-
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_wf_generate(RenderArgs a, WfState s)
-{
-    int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p < kSeg) {  // initial queue: every slot, in slot order, in bin 0 of its segment
-        int64_t lo = p * s.seg_cap;
-        int64_t c = s.P - lo;
-        s.cnt[0][p * s.nbins * kCtr] = (uint32_t)(c < 0 ? 0 : (c > s.seg_cap ? s.seg_cap : c));
-    }
-    if (p >= s.P) return;
-    int lr = (int)(p / a.W), x = (int)(p - (int64_t)lr * a.W);
-    int y = tile_row_to_y(a, lr);
-    uint32_t rng = pixel_seed((uint32_t)x, (uint32_t)y, (uint32_t)a.W);
-    f3 o, d;
-    camera_sample(a.cam, (uint32_t)x, (uint32_t)y, a.invW, a.invH, rng, o, d);
-    const int64_t P = s.P;
-    s.rng[p] = rng;
-    s.smp[p] = 0;
-    s.depth[p] = 0;
-    s.col[p] = 0.0f; s.col[P + p] = 0.0f; s.col[2 * P + p] = 0.0f;
-    s.ray[p] = o.x; s.ray[P + p] = o.y; s.ray[2 * P + p] = o.z;
-    s.ray[3 * P + p] = d.x; s.ray[4 * P + p] = d.y; s.ray[5 * P + p] = d.z;
-    const int64_t seg = p / s.seg_cap;  // sub-queue (seg, 0) starts at seg * nbins * seg_cap
-    s.q[0][seg * s.nbins * s.seg_cap + (p - seg * s.seg_cap)] = (uint32_t)p;
-}
-
-// Persistent traversal with lane refill ("dynamic fetch", Aila & Laine 2009,
-// re-derived for wave64 and segmented queues): every lane keeps a resumable
-// traversal state in registers.  A wave holds a reservation of up to kChunk
-// queue entries (uniform, in SGPRs); whenever >= REFILL lanes are idle they
-// take the next entries of the reservation (ballot + mbcnt ranks).  An empty
-// reservation is renewed by ONE atomic on the head of the wave's current
-// segment; exhausted segments are skipped, starting from the wave's own, so
-// waves work on nearby pixels and the heads see few atomics.  Lanes run
-// STEPS traversal steps between refill checks, each step of the kind (node or
-// leaf) more lanes are waiting for.
-template <bool ANY, bool COUNT, int BLOCK, int SL, bool TOPC, int MINW, int STEPS = 4, int REFILL = 8>
-__global__ void __launch_bounds__(BLOCK, MINW) k_wf_trace(SceneView sv, WfState s, int parity,
-                                                          uint32_t* __restrict__ ovf)
-{
-    __shared__ uint32_t s_stack[SL * BLOCK];
-    const int64_t gtid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    TravStack<BLOCK, SL> st{&s_stack[threadIdx.x], ovf + gtid * (kStackTotal - SL)};
-    if (TOPC) {  // the top BVH4 levels in LDS (as k_path)
-        __shared__ uint4 s_top[TOPC ? kTopNodes * 4 : 1];
-        const uint32_t ntop = (uint32_t)min(kTopNodes, sv.n_nodes4);
-        const uint4* g = reinterpret_cast<const uint4*>(sv.nodes4);
-        for (uint32_t i = threadIdx.x; i < ntop * 4; i += BLOCK) s_top[i] = g[i];
-        __syncthreads();
-        st.top = (const lds_u4*)s_top;
-        st.ntop = ntop;
-    }
-    TravCount cnt;
-    uint32_t traced = 0;
-    const uint32_t* q = ANY ? s.qs : s.q[parity];
-    const uint32_t* counts = ANY ? s.cnt_s : s.cnt[parity];
-    uint32_t* heads = ANY ? s.head_s : s.head_e;
-    const int64_t P = s.P;
-    const f3 ldir = light_dir();
-    const uint64_t lt = (1ull << lane_id()) - 1ull;
-    const uint32_t wave_gid = (uint32_t)(gtid >> 6);
-    const uint32_t nq = ANY ? (uint32_t)kSeg : (uint32_t)kSeg * s.nbins;  // sub-queues
-    uint32_t seg = wave_gid % nq;  // current sub-queue; starts spread over the frame
-    bool drained = false;
-    uint32_t walked = 0;
-    uint32_t res = 0, res_end = 0;          // reservation [res, res_end) of queue positions
-    bool active = false;
-    uint32_t p = 0;
-    uint32_t steps = 0, max_steps = 0;  // COUNT builds: longest query of this lane
-    TravRay r;
-    TravState ts;
-    for (;;) {
-        uint64_t idle = wballot(!active);
-        uint32_t nidle = (uint32_t)__popcll(idle);
-        if (nidle >= (uint32_t)REFILL && (res < res_end || !drained)) {
-            while (res >= res_end && !drained) {  // renew the reservation (wave-uniform)
-                const uint32_t c = counts[seg * kCtr];
-                uint32_t b = c;
-                // at low load (walk_check) a wave walking past its own
-                // sub-queue takes a relaxed look at the head first, so an
-                // exhausted sub-queue costs no atomic (every wave walks all of
-                // them at the end of an iteration: 1/8 shard 310 -> 193 ms);
-                // at full load that extra round trip per renewal costs more
-                // than it saves (N = 1: 550 -> 773 ms), so the atomic alone
-                if (c != 0 && (walked == 0 || !s.walk_check ||
-                               __hip_atomic_load(&heads[seg * kCtr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c)) {
-                    if (lane_id() == 0) b = atomicAdd(&heads[seg * kCtr], kChunk);
-                    b = (uint32_t)__shfl((int)b, 0);
-                }
-                if (b < c) {
-                    res = seg * s.seg_cap + b;
-                    res_end = seg * s.seg_cap + min(b + kChunk, c);
-                    walked = 0;
-                } else {  // sequential walk: try the next sub-queue, give up after all of them
-                    seg = seg + 1 == nq ? 0u : seg + 1;
-                    if (++walked == nq) drained = true;
-                }
-            }
-            uint32_t take = min(nidle, res_end - res);
-            uint32_t k = (uint32_t)__popcll(idle & lt);
-            if (!active && k < take) {
-                uint32_t e = q[res + k];
-                if (!(e & kSkip)) {  // flagged entries: stopped at kMaxDepth, nothing to trace
-                    p = e;
-                    f3 o, d;
-                    if (ANY) {
-                        o = mk(s.sho[p], s.sho[P + p], s.sho[2 * P + p]);
-                        d = ldir;
-                    } else {
-                        o = mk(s.ray[p], s.ray[P + p], s.ray[2 * P + p]);
-                        d = mk(s.ray[3 * P + p], s.ray[4 * P + p], s.ray[5 * P + p]);
-                    }
-                    r = make_trav_ray(o, d);
-                    trav_init(ts, kMaxT);
-                    ++traced;
-                    steps = 0;
-                    const bool root_miss = !ANY && s.root_check && s.depth[p] == 0 &&
-                                           !octree_root_hit(sv, o, d, kMinT, kMaxT);
-                    if (root_miss) atomicAdd(&sv.oct->ties[1], 1ull);
-                    if (sv.n > 0 && !ray_has_nan(o, d) && !root_miss) {
-                        active = true;
-                    } else if (!ANY) {  // provably no hit (NaN ray, empty scene, root box): a counted miss
-                        s.hid[p] = -1;
-                    }
-                }
-            }
-            res += take;
-        }
-        if (!wany(active)) {
-            if (res >= res_end && drained) break;
-            continue;
-        }
-        if (active) {
-            bool done = false;
-            for (int k = 0; k < STEPS; ++k) {
-                // one step kind per round: inner nodes or leaves, whichever more
-                // lanes are waiting for, so each load issues with more lanes
-                const uint64_t at_leaf = wballot(!done && ts.node < 0);
-                const uint64_t at_node = wballot(!done && ts.node >= 0);
-                if (at_leaf == 0 && at_node == 0) break;
-                const bool leaf_round = __popcll(at_leaf) > __popcll(at_node);
-                // the kind is wave-uniform: a scalar branch to the step that has
-                // only that kind's code (as in k_path's voted rounds)
-                if (leaf_round) {
-                    if (!done && ts.node < 0) {
-                        done = trav_step4q2_mixed<COUNT, BLOCK, SL, TOPC, 2>(sv, r, ANY, ts, st, cnt);
-                        if (COUNT) ++steps;
-                    }
-                } else if (!done && ts.node >= 0) {
-                    done = trav_step4q2_mixed<COUNT, BLOCK, SL, TOPC, 1>(sv, r, ANY, ts, st, cnt);
-                    if (COUNT) ++steps;
-                }
-            }
-            if (done) {
-                active = false;
-                if (COUNT) max_steps = max(max_steps, steps);
-                if (ANY) {
-                    if (octree_flag(sv, r, ts)) settle_any(sv, r, kMinT, kMaxT, ts);  // a flat triangle, a crack
-                    if (ts.best >= 0) s.light[(int64_t)(s.depth[p] - 1) * P + p] = 0.0f;
-                } else {
-                    settle_closest<BLOCK, SL, TOPC, false, false>(sv, r, 0.0f, kMinT, kMaxT, ts, st);
-                    s.hid[p] = ts.best;
-                    s.hit[P + p] = ts.bu;
-                    s.hit[2 * P + p] = ts.bv;
-                }
-            }
-        }
-    }
-    uint32_t rr = wave_sum(traced);
-    uint32_t nv = COUNT ? wave_sum(cnt.nodes) : 0u;
-    uint32_t nt = COUNT ? wave_sum(cnt.tris) : 0u;
-    if (lane_id() == 0) {
-        atomicAdd(&s.tot[ANY ? 1 : 0], (unsigned long long)rr);
-        if (COUNT) {
-            atomicAdd(&s.tot[ANY ? 4 : 2], (unsigned long long)nv);
-            atomicAdd(&s.tot[ANY ? 5 : 3], (unsigned long long)nt);
-        }
-    }
-    if (COUNT) {
-        for (int off = 32; off > 0; off >>= 1) max_steps = max(max_steps, (uint32_t)__shfl_xor((int)max_steps, off));
-        if (lane_id() == 0) atomicMax(&s.tot[ANY ? 7 : 6], (unsigned long long)max_steps);
-    }
-}
-
-// shade: one lane per path slot, in slot order, so every state access is
-// coalesced.  Every unfinished path was extended this iteration (or stopped at
-// kMaxDepth), so each needs exactly one shading step.  Appends (wave-compacted)
-// to the block's segment of the other parity's extend queue and of the shadow
-// queue; writes finished pixels.
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_wf_shade(SceneView sv, RenderArgs a, WfState s,
-                                                    int parity, uint32_t* __restrict__ out)
-{
-    const int64_t P = s.P;
-    const int64_t p64 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const uint32_t p = (uint32_t)p64;
-    const uint32_t seg = (uint32_t)(((int64_t)blockIdx.x * BLOCK) / s.seg_cap);
-    uint32_t depth = p64 < P ? s.depth[p] : kDone;
-    bool cont = false, shadow = false;
-    uint32_t bin = 0;  // octant bin of the next extend ray
-    if (depth != kDone) {
-        uint32_t rng = s.rng[p];
-        f3 d = mk(s.ray[3 * P + p], s.ray[4 * P + p], s.ray[5 * P + p]);
-        int id = depth < (uint32_t)kMaxDepth ? s.hid[p] : -1;
-        bool finish = true;
-        f3 color = mk(0.0f, 0.0f, 0.0f);
-        if (depth < (uint32_t)kMaxDepth) {
-            if (id >= 0) {  // Scatter, main.cpp:44-73
-                f3 pos, nrm;
-                hit_record(sv, id, s.hit[P + p], s.hit[2 * P + p], pos, nrm);
-                s.light[(int64_t)depth * P + p] = light_cosine(nrm, d);  // zeroed by shadow if occluded
-                s.sho[p] = pos.x; s.sho[P + p] = pos.y; s.sho[2 * P + p] = pos.z;
-                f3 rnd = random_unit_vector(rng);
-                f3 target = pos + nrm + rnd;
-                d = normalize(target - pos);
-                s.ray[p] = pos.x; s.ray[P + p] = pos.y; s.ray[2 * P + p] = pos.z;
-                s.ray[3 * P + p] = d.x; s.ray[4 * P + p] = d.y; s.ray[5 * P + p] = d.z;
-                ++depth;
-                shadow = true;
-                cont = true;  // depth == kMaxDepth: finished next iteration, after its shadow
-                finish = false;
-            } else {
-                color = sky(d);  // main.cpp:106-107
-            }
-        }
-        if (finish) {
-            for (int k = (int)depth - 1; k >= 0; --k)
-                color = backward_step(color, s.light[(int64_t)k * P + p]);
-            f3 col = mk(s.col[p], s.col[P + p], s.col[2 * P + p]) + color;
-            uint32_t smp = s.smp[p] + 1;
-            s.smp[p] = smp;
-            depth = 0;
-            if (smp < (uint32_t)a.spp) {
-                s.col[p] = col.x; s.col[P + p] = col.y; s.col[2 * P + p] = col.z;
-                int lr = (int)(p / (uint32_t)a.W), x = (int)(p - (uint32_t)lr * (uint32_t)a.W);
-                int y = tile_row_to_y(a, lr);
-                f3 o;
-                if (a.jt) rng = sample_seed(a.jt, smp, pixel_seed((uint32_t)x, (uint32_t)y, (uint32_t)a.W));
-                camera_sample(a.cam, (uint32_t)x, (uint32_t)y, a.invW, a.invH, rng, o, d);
-                s.ray[p] = o.x; s.ray[P + p] = o.y; s.ray[2 * P + p] = o.z;
-                s.ray[3 * P + p] = d.x; s.ray[4 * P + p] = d.y; s.ray[5 * P + p] = d.z;
-                cont = true;
-            } else {
-                out[p] = pack_pixel(col, a.spp_recip);
-                depth = kDone;
-            }
-        }
-        s.depth[p] = depth;
-        s.rng[p] = rng;
-        if (cont && depth != (uint32_t)kMaxDepth) bin = dir_bin(d, s.nbins);
-    }
-    // the next extend ray into its (segment, octant) sub-queue: one ballot
-    // and at most one atomic per wave and bin
-    for (uint32_t b = 0; b < s.nbins; ++b) {
-        const bool mine = cont && bin == b;
-        const uint32_t sq = seg * s.nbins + b;
-        const uint32_t qi = wave_append(&s.cnt[parity ^ 1][sq * kCtr], mine);
-        if (mine) s.q[parity ^ 1][sq * s.seg_cap + qi] = depth == (uint32_t)kMaxDepth ? (p | kSkip) : p;
-    }
-    uint32_t si = wave_append(&s.cnt_s[seg * kCtr], shadow);
-    if (shadow) s.qs[seg * s.seg_cap + si] = p;
-}
-
-// after the extend of `parity` was consumed: zero its counts and the heads;
-// publish the size of the next queue for the host's termination check
-__global__ void __launch_bounds__(kSeg) k_wf_advance(WfState s, int parity, int it)
-{
-    int j = threadIdx.x;
-    uint32_t next = 0, cur = 0;
-    for (uint32_t k = (uint32_t)j; k < (uint32_t)kSeg * s.nbins; k += kSeg) {  // extend sub-queues
-        next += s.cnt[parity ^ 1][k * kCtr];
-        cur += s.cnt[parity][k * kCtr];
-        s.cnt[parity][k * kCtr] = 0;
-        s.head_e[k * kCtr] = 0;
-    }
-    if (s.iter_log) {  // debug: rays of this iteration's extend (consumed queue) and shadow
-        uint32_t e = wave_sum(cur);
-        uint32_t sh = wave_sum(s.cnt_s[j * kCtr]);
-        if (j == 0) {
-            s.iter_log[2 * it] = e;
-            s.iter_log[2 * it + 1] = sh;
-        }
-    }
-    s.cnt_s[j * kCtr] = 0;
-    s.head_s[j * kCtr] = 0;
-    next = wave_sum(next);
-    if (j == 0) s.total[0] = next;
-}
-
 // ============================================================ persistent path engine
 // One persistent kernel per frame.  Every lane owns one pixel at a time and
 // runs its whole sample sequence (the RNG stream threads through the samples,
@@ -817,218 +269,6 @@ __global__ void __launch_bounds__(kSeg) k_wf_advance(WfState s, int parity, int 
 // chunks taken, so all segments together hand out ranks in increasing order
 // (the waves walk segments from their own one, one atomic per chunk).  Rank r
 // is pixel order[r] (a cost-descending order from a pilot pass) or r itself.
-// Streaming row engine (SAMP 4, render_rowstream): the speculative row chains
-// of render_rowspec without iterations.  One persistent launch: chaser waves
-// (the first blocks, one lane per row) walk each row's chain as soon as the
-// unit it needs is done and plan pixel windows ahead of it; worker waves take
-// units from the rows' windows and trace them shadow-free.  A unit (row,
-// pixel p, offset j) starts at M^(2j) row_seed, like render_rowspec's.
-//   slots[row][kRssT + 1]: pixel windows, word = (p+1) << 48 | q << 24 | hi
-//     (offsets [q, hi) of pixel p not handed out yet; slot p % kRssT; the last
-//     slot is the chain's demand window for the current pixel); workers take
-//     offsets by CAS, the chaser plans and extends by CAS
-//   res[row][p % kRssT][j % R]: a finished unit, word = ((p+1) << 24 | j) << 28
-//     | draws | rays << 14 | closest-hit rays << 19, written by atomicMax, so a
-//     late unit of a pixel kRssT back never overwrites a live one
-//   chainpos[row] = x << 32 | c: the chain's pixel and next sample's offset
-//   list[(row * W + x) * spp + k] = offset of sample k of pixel x on the chain
-//   ctl: [0] rows done, [1] abort, [2] chain progress ticks, [3] error, [4] P,
-//        [5..11] statistics, [12] block arrival tickets (the first nchase are chasers)
-#ifndef TMPT_RSS_T
-#define TMPT_RSS_T 8
-#endif
-constexpr int kRssT = TMPT_RSS_T;  // live pixel windows per row at most kRssT - 1 (plus the demand slot)
-static_assert(kRssT >= 4 && kRssT <= 31, "the worker's pick key holds the slot in 5 bits");
-constexpr uint32_t kRssM24 = 0xFFFFFFu;
-struct RsStream {
-    unsigned long long* __restrict__ slots;
-    unsigned long long* __restrict__ res;
-    unsigned long long* __restrict__ chainpos;
-    uint32_t* __restrict__ list;
-    uint32_t* __restrict__ rowrays;    // [row][2]: chain rays, closest-hit
-    uint32_t* __restrict__ lo;         // [row][kRssT]: chaser-private window starts
-    uint32_t* __restrict__ ctl;
-    const uint32_t* __restrict__ anchors;  // [row][na]: M^(2^15 a) row_seed
-    const uint32_t* __restrict__ t1;       // M^(2c), c < 128 (byte tables)
-    const uint32_t* __restrict__ t2;       // M^(256 b), b < 128
-    uint32_t na, R, rmask;
-    uint32_t jlimit;        // na * 2^14: offsets with an anchor
-    int nrows, nchase, nw;  // rows, chaser blocks, live pixel windows per row
-    float spread;
-    // live windows and spread follow the live rows (the load law of the
-    // launch-time rule, applied as rows finish): room = room_lanes / live rows;
-    // dyn bit 0: windows, bit 1: spread (an option fixes either)
-    float room_lanes;
-    uint32_t dyn;
-    uint32_t watchdog;      // 100-MHz ticks without chain progress before the workers abort
-    int test_abort;         // option rowstream_test_abort: chasers leave at once (the abort path's test)
-};
-
-// M^(2j) row_seed of row `row` (j < na * 2^14)
-__device__ __forceinline__ uint32_t rss_state(const RsStream& S, int row, uint32_t j)
-{
-    uint32_t s = S.anchors[(size_t)row * S.na + (j >> 14)];
-    s = sample_seed(S.t2, (j >> 7) & 127u, s);
-    return sample_seed(S.t1, j & 127u, s);
-}
-
-struct PathCtl {
-    uint32_t* heads;  // kSeg chunk counters, stride kCtr
-    uint32_t nchunks;
-    // SIMD-balanced first chunks (ordered pass, cost-descending chunks): the
-    // wave of rank r on the d-th SIMD to register takes chunk r*nsimd + d (r
-    // even) or r*nsimd + nsimd-1-d (r odd), so every SIMD's resident waves sum
-    // to about the same work.  Every chunk has a claim word: the first chunk
-    // and the segment supply both claim, so a chunk the placement left
-    // unassigned (uneven waves per SIMD) is still taken, and none twice.
-    // simd_reg = 2 words per hardware SIMD key (waves seen, dense index + 1)
-    // plus a dense counter at kSimdKeys*2.  null = off.
-    uint32_t* simd_reg;
-    uint32_t* claim;  // nchunks words, zeroed per launch
-    uint32_t nsimd, wps;
-    int64_t P;
-    const uint32_t* __restrict__ order;  // rank -> pixel, or null
-    uint32_t* __restrict__ cost_out;     // per-pixel traversal steps of this call, or null
-    // dynamic issue priority (longest remaining first): each shading round the
-    // wave estimates its lanes' remaining traversal steps (steps so far per
-    // finished sample x samples left) and sets s_setprio 3/2/1/0 at the
-    // thresholds dprio[0] > dprio[1] > dprio[2] (steps); dprio[0] = 0: off.
-    // With dprio_cost (the pilot pass's per-pixel steps), the thresholds are
-    // fractions of the heaviest pixel's (order[0]) projected remaining steps.
-    float dprio[3];
-    const uint32_t* __restrict__ dprio_cost;
-    uint32_t lane_cap;  // pixels a wave holds at once (64: all lanes)
-    uint32_t chunk;     // ranks per chunk (kChunk, or lane_cap when capped)
-    // Sample seeding: the supply hands out units = (pixel, block of blk
-    // samples), nblk blocks per pixel, unit u = pixel * nblk + block (P counts
-    // units).  With nblk > 1 each sample's colour goes to sbuf[s * slots + pixel]
-    // and k_resolve sums them in sample order (main.cpp:218's col += Trace).
-    uint32_t nblk, blk;
-    FastDiv div_nblk, div_blk;  // their dividers (the unit decode)
-    uint32_t blk0;  // progressive pass: the block of its first sample (units = the pass's blocks)
-    // the frame's tail (option sample_tail): units >= ua are single samples,
-    // unit ua + v = sample v % blk of block ua + v / blk, so the last units
-    // handed out are one sample long, not one block
-    uint32_t ua;
-    float4* __restrict__ sbuf;
-    uint32_t sb_ss, sb_sp;  // sbuf index = sample * sb_ss + pixel * sb_sp ([pixel][sample]: 1, spp)
-    uint32_t pair;          // sample pairs (2k, 2k+1) of a unit written back to back (one 32-B sector)
-    // Speculative row seeding (SAMP 2, render_rowspec): unit u traces ONE
-    // sample of tile pixel upix[u] from RNG state ustate[u] and writes its
-    // colour with w = draws | rays << 27 to rs_out[u], and its final RNG state
-    // to rs_end[u]
-    const uint32_t* __restrict__ upix;
-    const uint32_t* __restrict__ ustate;
-    float4* __restrict__ rs_out;
-    uint32_t* __restrict__ rs_end;
-    const uint32_t* __restrict__ p_dev;  // the unit count (replaces P, nchunks at launch)
-    // no-shadow speculation (option rowspec_noshadow): the speculative pass skips
-    // shadow traversals (they never change a sample's draws); the chain's
-    // samples are traced again in full at the end of the frame, unit u as
-    // sample uslot[u] of its pixel, colour into sbuf (resolved in order)
-    int rs_noshadow;
-    const uint32_t* __restrict__ uslot;
-    RsStream rss;  // SAMP 4
-    // Deferred ties (SAMP 1, k_path DEFER): the main loop carries no octree
-    // walk; a sample whose closest-hit query ends on a flagged tie is dropped
-    // and (pixel, sample) appended to redo (counters[kRedoCounter] counts them,
-    // redo_cap entries are kept, kRedoEmpty until written).  Waves past the
-    // main loop trace the listed samples again, ties settled (redo_sample);
-    // k_redo takes any they leave.
-    uint2* __restrict__ redo;
-    float4* __restrict__ redo_state;  // kRedoState4 float4 per slot: where the dropped path stopped
-    uint32_t redo_cap;
-    uint32_t redo_inline;  // 0 (test hook, option redo_inline): no redo phase, k_redo takes every entry
-    uint32_t redo_lanes;   // lanes per wave that take redo tickets (1..64)
-    // With the octree: shadow answers can need it too (a flat triangle in the
-    // scene, or the light direction can run along a crack; render_persistent
-    // decides) -- the finished shadow queries are checked as closest hits are
-    // (octree_flag), so HELP and DEFER are off then.
-    uint32_t oct_shadow;
-    // Top-walk rounds (option top_walk): at the end of a shading round, up to
-    // this many wave-uniform node rounds for the lanes standing on a node of
-    // the block's LDS copy of the top levels -- every query starts at node 0
-    // -- with no global load in them (trav_step4q2_mixed TOPONLY).  0 = off.
-    uint32_t top_walk;
-};
-
-// ---- k_path's variants
-// What varies between k_path's instantiations, by its template parameters'
-// names (BLOCK is kBlk in all of them; TAIL follows samp, path_tail below).
-// The table after k_path (kPathVariants) lists the ones the library instantiates.
-struct PathVariant {
-    bool count;                     // COUNT: the visit counters
-    int sl, steps, shade_min, occ;  // LDS stack entries per lane, rounds per shading check, lanes that trigger one, blocks per CU
-    int prof;                       // PROF (TMPT_DIAG builds): the wave-time split
-    int help;                       // HELP: idle lanes trace other lanes' shadow queries
-    int samp;                       // SAMP: 0 pixel, 1 sample seeding; 2 / 3 / 4 the row engines' units
-    bool soa;                       // the SoA planes (layout=soa)
-    int ties;                       // TIES: 0 lowest index, 2 flag for the octree, 1 flag and defer
-    bool sums;                      // SUMS: the float sums beside the packed pixels
-};
-
-// The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel
-// seeding and the rows' full re-trace (OCC 5): 30 KB of LDS per block -- a
-// 12-entry LDS stack, the scattered ray's direction only, kTopNodes5 top nodes
-constexpr int kPathSL = 16, kPathSL5 = 12;
-
-// The cadences, each with its A/B macro (tools/ab_build.sh, tools/ab_kpath.py).
-#ifndef TMPT_PATH_STEPS
-#define TMPT_PATH_STEPS 16
-#endif
-#ifndef TMPT_PIX_STEPS
-#define TMPT_PIX_STEPS 24
-#endif
-#ifndef TMPT_ROW_STEPS
-#define TMPT_ROW_STEPS 16
-#endif
-#ifndef TMPT_ROW_SHADE_MIN
-#define TMPT_ROW_SHADE_MIN 24
-#endif
-#ifndef TMPT_SHADE_MIN
-#define TMPT_SHADE_MIN 16
-#endif
-#ifndef TMPT_SPARSE
-#define TMPT_SPARSE 2
-#endif
-#ifndef TMPT_RS_OCC
-#define TMPT_RS_OCC 5
-#endif
-// Sample and pixel seeding (render_persistent): traversal rounds between
-// shading checks / lanes waiting that trigger a shading round (A/B on the
-// bench frame at 1 and 8 shards);
-// sparse-wave shading threshold divisor (k_path TAIL): 2 -- bench frame,
-// pixel seeding 235.2 -> 231.9 ms at N=1, 1/8 shard unchanged (41.0 ms);
-// sample seeding 220.4 -> 218.2 ms at N=1, 29.4 -> 29.0 ms at 1/8
-// (TMPT_PATH_STEPS / TMPT_SHADE_MIN / TMPT_SPARSE: A/B builds, tools/ab_build.sh)
-constexpr int kSampleSteps = TMPT_PATH_STEPS, kShadeMin = TMPT_SHADE_MIN, kSparse = TMPT_SPARSE;
-// pixel seeding's kernels: 24 rounds between shading checks -- re-swept at
-// 5 waves per SIMD (whole renders, steps 16 / 24 / 32: 1/8 shard 36.4 /
-// 35.2 / 36.1 ms, 1/4 63.7 / 63.2 / 65.1, N=1 198.0 / 196.0 / 208.9; the
-// sample kernels 172.3 / 172.8 / 182.9 keep 16; 20 and 28 both lose to 24,
-// +1.4 % at 1/8; profiles/r06_experiments/cadence_5waves*.log,
-// cadence_pixel_20_24_28.log)
-constexpr int kPixSteps = TMPT_PIX_STEPS;
-// The streaming row engine (render_rowstream), SAMP 2 and 4:
-// a shading round once 24 lanes wait (16 before round 6): whole row renders,
-// 16 / 24 / 28 / 32, N=1 1835.9 / 1811.4 / 1811.9 / 1833.8 ms, 1/2 1034.8 /
-// 1023.5 / 1023.6, 1/8 432.1 / 430.4 / 427.6 / 428.3; 24 or 32 rounds per
-// check instead of 16: -0.8 / +1.2 % at N=1 (profiles/r06_experiments/row_cadence*.log)
-constexpr int kRowSteps = TMPT_ROW_STEPS, kRowShadeMin = TMPT_ROW_SHADE_MIN;
-// the iterated row engine (render_rowspec), SAMP 2 and 3: no macro
-constexpr int kRowIterSteps = 16, kRowIterShadeMin = 16;
-// blocks per CU of the shadow-free row units, SAMP 3 and 4 (5 waves per SIMD)
-constexpr int kRsOcc3 = TMPT_RS_OCC;
-// TAIL of a variant: kSparse in sample and pixel seeding, 2 in the row engines
-constexpr int path_tail(int samp) { return samp <= 1 ? kSparse : 2; }
-
-using PathFn = void (*)(SceneView, RenderArgs, PathCtl, uint32_t*, uint32_t*, unsigned long long*);
-
-// The kernel of a variant, or null when the table does not hold it.
-PathFn path_kernel(const PathVariant& v);
-// The same for a render call: 0 and the kernel, or -22 with the variant's
-// fields in the error (set_error) -- never a neighbouring kernel.
-int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn);
 
 constexpr uint32_t kSimdKeys = 8u * 8u * 2u * 16u * 4u;  // XCC x SE x SH x CU x SIMD (HW_ID fields)
 
@@ -2345,344 +1585,10 @@ __global__ void __launch_bounds__(64) k_resolve_px(const float4* __restrict__ sb
     }
 }
 
-// ============================================================ speculative row seeding
-// Row seeding (main.cpp:204) threads ONE xorshift stream through a row's
-// pixels and samples, and a sample's draws depend on its path, so a row is a
-// sequential chain (the megakernel runs one lane per row).  But a sample is
-// a pure function of (pixel, start state), and every draw site takes two
-// draws (maths.cpp:25, 32-33, main.cpp:214-215), so the next sample starts
-// an even number of draws after this one's start.  render_rowspec traces,
-// for each row, one sample at EVERY even offset 2j of a window past the
-// row's current state (units of k_path<SAMP 2>), then a chase walks the
-// chain through the window: take the sample at offset 0, add its colour in
-// sample order, jump to offset + its draws, ...  Each window costs ~draws/2
-// traces per chain sample (speculation), but all of them run in parallel.
-constexpr int kRsMaxWin = 32;  // windows per row and iteration: this pixel + up to 31 lookaheads
-
-struct RowSpec {
-    int row0, nrows;  // this group's tile rows [row0, row0 + nrows)
-    // per row of the group: chain state, current pixel and samples done in it,
-    // its draws so far and the previous pixel's mean draws per sample (window
-    // sizing), chain rays (all, closest-hit), unit offsets (nrows + 1)
-    uint32_t *rng, *x, *k, *pdraws, *prev_mean, *rays, *erays, *offs;
-    // window i (pixel x + i) of row r: offsets [ws[i*nrows + r], + win[i*nrows + r]);
-    // window 0 starts at 0; win = 0: none
-    uint32_t *win, *ws;
-    uint32_t* short_win;  // iterations whose window ended before the pixel did (diagnostic)
-    float4* col;
-    uint32_t* total;  // units of this iteration
-    unsigned long long* planned;  // units over all iterations (diagnostic)
-    uint32_t wmax;
-    float spread;   // windows from expected positions +- spread * sqrt(i) pixels
-    int nwin;       // windows per row (1 = no lookahead)
-    // no-shadow speculation: the chase lists the chain's samples (tile pixel,
-    // start state, sample index) for the full re-trace; scratch holds a row's
-    // (unit, sample index) pairs of one iteration (scap per row)
-    uint32_t *lpix, *lstate, *lslot, *lcount;
-    uint2* scratch;
-    uint32_t scap;
-    // Chains: a row is a chain of cw = W pixels x cspp = spp samples from the
-    // row seed.  Pixel chains (pixel seeding, render_pixel_chains): chain r is
-    // tile pixel cpix[r] alone (cw = 1), its samples smp0 .. smp0 + cspp - 1,
-    // from the RNG state the pilot pass left in cinit[pixel].w.
-    const uint32_t* cpix;
-    const float4* cinit;
-    int cw, cspp, smp0;
-};
-
-// Decode of a unit's rs_out.w: draws | rays << 23 | extend rays << 28.
-constexpr uint32_t kRsDrawBits = 23;
-
-__global__ void __launch_bounds__(256) k_rs_init(RenderArgs a, RowSpec rs)
+void launch_resolve_px(hipStream_t stream, const float4* sbuf, int64_t P, int32_t spp, float spp_recip,
+                       uint32_t* out)
 {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= rs.nrows) return;
-    rs.rng[r] = rs.cpix ? __float_as_uint(rs.cinit[rs.cpix[r]].w)           // pixel chain: after its pilot
-                        : row_seed((uint32_t)tile_row_to_y(a, rs.row0 + r));  // main.cpp:204, unmodified
-    rs.x[r] = rs.k[r] = rs.pdraws[r] = rs.rays[r] = rs.erays[r] = rs.short_win[r] = 0u;
-    rs.prev_mean[r] = __float_as_uint(17.0f);  // draws per sample before any is seen
-    rs.col[r] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// Windows per row.  E = a pixel's expected units (spp x mean draws per
-// sample / 2: even offsets only), the mean the larger of this pixel's so far
-// and the previous pixel's.  Pixel x + i is expected to start c_i = e0 +
-// (i - 1) E units ahead (e0 = this pixel's expected rest) and end c_i + E,
-// each give or take spread * sqrt(i) * E; window i spans its start's and its
-// end's ranges (window 0 starts at 0).  Exclusive scan into offs; total units.
-// One block.
-__global__ void __launch_bounds__(1024) k_rs_plan(RenderArgs a, RowSpec rs)
-{
-    __shared__ uint32_t part[1024];
-    const int rows = rs.nrows;
-    const int per = (rows + 1023) / 1024;
-    const int r0 = min(rows, (int)threadIdx.x * per), r1 = min(rows, r0 + per);
-    uint32_t sum = 0;
-    for (int r = r0; r < r1; ++r) {
-        const uint32_t x = rs.x[r];
-        uint32_t t = 0;  // end of the previous window
-        float mean = 0.0f, e0 = 0.0f, E = 0.0f;
-        if (x < (uint32_t)rs.cw) {
-            const uint32_t k = rs.k[r];
-            mean = __uint_as_float(rs.prev_mean[r]);
-            if (k > 0) mean = fmaxf(mean, (float)rs.pdraws[r] / (float)k);
-            e0 = (float)((uint32_t)rs.cspp - k) * mean * 0.5f;  // expected units to this pixel's end
-            E = (float)rs.cspp * mean * 0.5f;                   // ... of one whole pixel
-        }
-        for (int i = 0; i < rs.nwin; ++i) {
-            uint32_t w = 0, s = 0;
-            if (x + (uint32_t)i < (uint32_t)rs.cw) {
-                const float ci = i == 0 ? 0.0f : e0 + (float)(i - 1) * E;
-                const float ui = i == 0 ? 0.0f : rs.spread * sqrtf((float)i) * E;
-                const float ce = e0 + (float)i * E, ue = rs.spread * sqrtf((float)(i + 1)) * E;
-                s = i == 0 ? 0u : min(t, (uint32_t)fmaxf(0.0f, ci - ui));
-                w = min(rs.wmax, (uint32_t)(ce + ue) + 2u - min(s, (uint32_t)(ce + ue)));
-                t = s + w;
-            }
-            rs.win[i * rows + r] = w;
-            rs.ws[i * rows + r] = s;
-            sum += w;
-        }
-    }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // inclusive scan of the thread sums
-        const uint32_t v = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t o = part[threadIdx.x] - sum;
-    for (int r = r0; r < r1; ++r) {
-        rs.offs[r] = o;
-        for (int i = 0; i < rs.nwin; ++i) o += rs.win[i * rows + r];
-    }
-    if (threadIdx.x == 1023) {
-        rs.offs[rows] = part[1023];
-        *rs.total = part[1023];
-        atomicAdd(rs.planned, (unsigned long long)part[1023]);
-    }
-}
-
-// Unit u -> (row, window i, offset index j): pixel x + i and start state
-// M^(2j) rng[row].  Launched over the largest possible count; the plan's
-// total bounds it.
-__global__ void __launch_bounds__(256) k_rs_fill(RenderArgs a, RowSpec rs, const uint32_t* __restrict__ jt2,
-                                                 uint32_t* __restrict__ upix, uint32_t* __restrict__ ustate)
-{
-    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
-    if (u >= *rs.total) return;
-    int lo = 0, hi = rs.nrows - 1;  // last row with offs <= u
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rs.offs[mid] <= u) lo = mid;
-        else hi = mid - 1;
-    }
-    uint32_t l = u - rs.offs[lo];
-    int i = 0;
-    for (; i + 1 < rs.nwin && l >= rs.win[i * rs.nrows + lo]; ++i) l -= rs.win[i * rs.nrows + lo];
-    const uint32_t j = rs.ws[i * rs.nrows + lo] + l;
-    upix[u] = rs.cpix ? rs.cpix[lo] : (uint32_t)(rs.row0 + lo) * (uint32_t)a.W + rs.x[lo] + (uint32_t)i;
-    ustate[u] = sample_seed(jt2, j, rs.rng[lo]);
-}
-
-// The chase, one thread per row: the chain's samples in order through the
-// windows (main.cpp:209-219), each pixel packed after its spp-th (:221-233);
-// on into window i + 1 when the next pixel's first sample falls in it.
-__global__ void __launch_bounds__(64) k_rs_chase(RenderArgs a, RowSpec rs, const float4* __restrict__ rs_out,
-                                                 const uint32_t* __restrict__ rs_end, uint32_t* __restrict__ out,
-                                                 const uint32_t* __restrict__ upix, const uint32_t* __restrict__ ustate)
-{
-    const int r = blockIdx.x * 64 + threadIdx.x;
-    const int rows = rs.nrows;
-    const bool listing = rs.lpix != nullptr;  // no-shadow speculation: list the chain, no colours
-    uint32_t n = r < rows ? rs.win[r] : 0u, nl = 0;
-    if (n > 0) {
-        uint32_t k = rs.k[r], x = rs.x[r], pdraws = rs.pdraws[r], rays = rs.rays[r], erays = rs.erays[r];
-        const float4 c0 = rs.col[r];
-        f3 col = mk(c0.x, c0.y, c0.z);
-        // window i: offsets [lo, lo + n) at wb
-        uint32_t j = 0, last = 0xFFFFFFFFu, lo = 0, wb = rs.offs[r];
-        int i = 0;
-        while (j >= lo && j - lo < n) {
-            const uint32_t idx = wb + (j - lo);
-            const float4 t = rs_out[idx];
-            const uint32_t w = __float_as_uint(t.w);
-            const uint32_t draws = w & ((1u << kRsDrawBits) - 1u);
-            rays += (w >> kRsDrawBits) & 31u;
-            erays += w >> 28;
-            pdraws += draws;
-            if (listing) rs.scratch[(size_t)r * rs.scap + nl++] = make_uint2(idx, (uint32_t)rs.smp0 + k);
-            else col = col + mk(t.x, t.y, t.z);  // col += Trace(...), main.cpp:218
-            last = idx;
-            j += draws >> 1;
-            if (++k == (uint32_t)rs.cspp) {  // the rest of this window belongs to this pixel: dropped
-                if (!listing) out[(size_t)(rs.row0 + r) * a.W + x] = pack_pixel(col, a.spp_recip);
-                rs.prev_mean[r] = __float_as_uint((float)pdraws / (float)k);
-                ++x;
-                k = 0;
-                pdraws = 0;
-                col = mk(0.0f, 0.0f, 0.0f);
-                if (++i >= rs.nwin) break;
-                wb += n;
-                n = rs.win[i * rows + r];
-                lo = rs.ws[i * rows + r];
-                if (n == 0) break;
-            }
-        }
-        if (last != 0xFFFFFFFFu) rs.rng[r] = rs_end[last];  // the next sample's start state
-        if (k != 0) ++rs.short_win[r];
-        rs.k[r] = k;
-        rs.x[r] = x;
-        rs.pdraws[r] = pdraws;
-        rs.rays[r] = rays;
-        rs.erays[r] = erays;
-        rs.col[r] = make_float4(col.x, col.y, col.z, 0.0f);
-    }
-    if (!listing) return;
-    // the row's chain samples into the frame's list: one atomic per wave
-    uint32_t incl = nl;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)incl, off);
-        if ((threadIdx.x & 63) >= (unsigned)off) incl += v;
-    }
-    uint32_t base = 0;
-    if ((threadIdx.x & 63) == 63) base = atomicAdd(rs.lcount, incl);
-    base = (uint32_t)__shfl((int)base, 63) + incl - nl;
-    for (uint32_t t = 0; t < nl; ++t) {
-        const uint2 e = rs.scratch[(size_t)r * rs.scap + t];
-        rs.lpix[base + t] = upix[e.x];
-        rs.lstate[base + t] = ustate[e.x];
-        rs.lslot[base + t] = e.y;
-    }
-}
-
-// The same chase for the listing (shadow-free) pass, one wave per row: the
-// row's unit words are staged in LDS with coalesced loads first, so the
-// chain's walk -- one dependent read per chain sample -- runs on LDS latency
-// instead of a global round trip each (the one-thread-per-row kernel spent
-// ~3.6 us per chain sample there).  The chain's (unit, sample) pairs collect
-// in LDS and the wave copies them into the frame's list.  Rows with more
-// units than kChaseUnits walk from global memory; the host only picks this
-// kernel when a row's chain samples per iteration fit kChaseList.
-constexpr uint32_t kChaseUnits = 8192, kChaseList = 2048;
-__global__ void __launch_bounds__(64) k_rs_chase_lds(RenderArgs a, RowSpec rs, const float4* __restrict__ rs_out,
-                                                     const uint32_t* __restrict__ rs_end,
-                                                     const uint32_t* __restrict__ upix,
-                                                     const uint32_t* __restrict__ ustate)
-{
-    __shared__ uint32_t s_w[kChaseUnits];
-    __shared__ uint2 s_l[kChaseList];
-    __shared__ uint32_t s_n, s_base;
-    const int r = blockIdx.x;
-    const int rows = rs.nrows;
-    const uint32_t lane = threadIdx.x;
-    if (rs.win[r] == 0) return;  // row finished (block-uniform)
-    const uint32_t u0 = rs.offs[r], nu = rs.offs[r + 1] - u0;
-    const bool staged = nu <= kChaseUnits;
-    if (staged)
-        for (uint32_t i = lane; i < nu; i += 64) s_w[i] = __float_as_uint(rs_out[u0 + i].w);
-    __syncthreads();
-    if (lane == 0) {
-        uint32_t k = rs.k[r], x = rs.x[r], pdraws = rs.pdraws[r], rays = rs.rays[r], erays = rs.erays[r];
-        uint32_t n = rs.win[r], nl = 0;
-        uint32_t j = 0, last = 0xFFFFFFFFu, lo = 0, wb = u0;
-        int i = 0;
-        while (j >= lo && j - lo < n) {
-            const uint32_t idx = wb + (j - lo);
-            const uint32_t w = staged ? s_w[idx - u0] : __float_as_uint(rs_out[idx].w);
-            const uint32_t draws = w & ((1u << kRsDrawBits) - 1u);
-            rays += (w >> kRsDrawBits) & 31u;
-            erays += w >> 28;
-            pdraws += draws;
-            s_l[nl++] = make_uint2(idx, (uint32_t)rs.smp0 + k);
-            last = idx;
-            j += draws >> 1;
-            if (++k == (uint32_t)rs.cspp) {  // the rest of this window belongs to this pixel: dropped
-                rs.prev_mean[r] = __float_as_uint((float)pdraws / (float)k);
-                ++x;
-                k = 0;
-                pdraws = 0;
-                if (++i >= rs.nwin) break;
-                wb += n;
-                n = rs.win[i * rows + r];
-                lo = rs.ws[i * rows + r];
-                if (n == 0) break;
-            }
-        }
-        if (last != 0xFFFFFFFFu) rs.rng[r] = rs_end[last];  // the next sample's start state
-        if (k != 0) ++rs.short_win[r];
-        rs.k[r] = k;
-        rs.x[r] = x;
-        rs.pdraws[r] = pdraws;
-        rs.rays[r] = rays;
-        rs.erays[r] = erays;
-        s_n = nl;
-        s_base = nl ? atomicAdd(rs.lcount, nl) : 0u;
-    }
-    __syncthreads();
-    const uint32_t nl = s_n, base = s_base;
-    for (uint32_t t = lane; t < nl; t += 64) {
-        const uint2 e = s_l[t];
-        rs.lpix[base + t] = upix[e.x];
-        rs.lstate[base + t] = ustate[e.x];
-        rs.lslot[base + t] = e.y;
-    }
-}
-
-// render_rowstream: each row's anchor states M^(2^15 a) row_seed, a < na, from
-// the byte tables of M^(2^15 a0) (j1) and M^(2^20 a1) (j2), a = 32 a1 + a0;
-// thread 0 also publishes the final pass's unit count.
-__global__ void __launch_bounds__(256) k_rss_anchors(RenderArgs a, RsStream S, const uint32_t* __restrict__ j1,
-                                                     const uint32_t* __restrict__ j2)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) S.ctl[4] = (uint32_t)((size_t)a.slots * (size_t)a.spp);
-    if (i >= (size_t)S.nrows * S.na) return;
-    const int row = (int)(i / S.na);
-    const uint32_t an = (uint32_t)(i - (size_t)row * S.na);
-    const uint32_t seed = row_seed((uint32_t)tile_row_to_y(a, row));  // main.cpp:204, unmodified
-    const_cast<uint32_t*>(S.anchors)[i] = sample_seed(j2, an >> 5, sample_seed(j1, an & 31u, seed));
-}
-
-// The chain list's offsets -> start states, in place (unit u: row u / spp / W).
-__global__ void __launch_bounds__(256) k_rss_states(RenderArgs a, RsStream S)
-{
-    const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (u >= (size_t)a.slots * (size_t)a.spp) return;
-    const int row = (int)(u / ((size_t)a.spp * (size_t)a.W));
-    S.list[u] = rss_state(S, row, S.list[u]);
-}
-
-// The chain rays of render_rowstream's rows: counters[0] all, [3] closest-hit.
-__global__ void __launch_bounds__(256) k_rss_count(RsStream S, unsigned long long* counters)
-{
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    unsigned long long sv = r < S.nrows ? S.rowrays[2 * r] : 0u, se = r < S.nrows ? S.rowrays[2 * r + 1] : 0u;
-    for (int off = 32; off > 0; off >>= 1) {
-        sv += __shfl_xor(sv, off);
-        se += __shfl_xor(se, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&counters[0], sv);
-        atomicAdd(&counters[3], se);
-    }
-}
-
-// The chain's rays (the reference's count): counters[0] all, [3] closest-hit.
-__global__ void __launch_bounds__(256) k_rs_count(RowSpec rs, unsigned long long* counters)
-{
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t v = r < rs.nrows ? rs.rays[r] : 0u, e = r < rs.nrows ? rs.erays[r] : 0u;
-    unsigned long long sv = v, se = e;
-    for (int off = 32; off > 0; off >>= 1) {
-        sv += __shfl_xor(sv, off);
-        se += __shfl_xor(se, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&counters[0], sv);
-        atomicAdd(&counters[3], se);
-    }
+    k_resolve_px<<<(unsigned)((P + 63) / 64), 64, 0, stream>>>(sbuf, P, spp, spp_recip, out);
 }
 
 // ============================================================ host side
@@ -2842,220 +1748,6 @@ RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d)
     return a;
 }
 
-namespace {
-
-template <bool ROW, bool COUNT>
-int launch_mega(Scene& s, const RenderArgs& a, uint32_t* out, unsigned long long* counters)
-{
-    auto fn = k_mega<ROW, COUNT, kBlk, kSL>;
-    int grid = occupancy_grid((const void*)fn, kBlk, 0, s.device);
-    // ROW: one wave per row_lanes rows (up to the resident grid)
-    int64_t items = ROW ? ((int64_t)a.tile_rows + a.row_lanes - 1) / a.row_lanes * 64 : a.slots;
-    grid = (int)std::min<int64_t>(grid, (items + kBlk - 1) / kBlk);
-    grid = std::max(grid, 1);
-    size_t ovf_bytes = (size_t)grid * kBlk * (kStackTotal - kSL) * sizeof(uint32_t);
-    if (ensure_ws(s, ovf_bytes)) return -1;
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a, out, (uint32_t*)s.ws, counters);
-    TMPT_HIP(hipGetLastError());
-    return 0;
-}
-
-}  // namespace
-
-int render_megakernel(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count,
-                      unsigned long long* d_counters)
-{
-    const bool row = a.seed_mode == TMPT_SEED_ROW;
-    if (row) return count ? launch_mega<true, true>(s, a, d_out, d_counters) : launch_mega<true, false>(s, a, d_out, d_counters);
-    return count ? launch_mega<false, true>(s, a, d_out, d_counters) : launch_mega<false, false>(s, a, d_out, d_counters);
-}
-// Wavefront driver.  The host enqueues iterations without reading the queue
-// sizes (the kernels read them from device memory) and checks for completion
-// every kCheck iterations.
-int render_wavefront(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count)
-{
-    const int64_t P = a.slots;
-    if (P >= (int64_t)kSkip) {
-        set_error("wavefront: tile too large");
-        return -22;
-    }
-    // top BVH levels from LDS in both passes, no occupancy floor: measured best
-    // against no LDS copy and 5-8 waves per SIMD (profiles/r03_wavefront_ab/)
-    constexpr bool kTopE = true, kTopS = true;
-    constexpr int kWE = 1, kWS = 1;
-    auto trace_e = count ? k_wf_trace<false, true, kBlk, kSL, kTopE, kWE> : k_wf_trace<false, false, kBlk, kSL, kTopE, kWE>;
-    auto trace_s = count ? k_wf_trace<true, true, kBlk, kSL, kTopS, kWS> : k_wf_trace<true, false, kBlk, kSL, kTopS, kWS>;
-    const int sl = kSL;
-    int grid_t = occupancy_grid((const void*)trace_e, kBlk, 0, s.device);
-    const int grid_sh = (int)((P + kBlk - 1) / kBlk);
-    const size_t seg_cap = (size_t)(((P + kSeg - 1) / kSeg + kBlk - 1) / kBlk) * kBlk;
-    const uint32_t nbins = (uint32_t)s.opt.wf_bins;  // extend sub-queues per segment (octant bins)
-    const size_t qcap = seg_cap * kSeg * nbins, qcap_s = seg_cap * kSeg;
-    const size_t Pz = (size_t)P;
-    size_t ovf_words = (size_t)grid_t * kBlk * (kStackTotal - sl);
-    // layout of the workspace
-    size_t words = 0;
-    auto take = [&](size_t w) { size_t o = words; words += (w + 63) & ~size_t(63); return o; };
-    const size_t ctr_words = (size_t)kSeg * kCtr, ectr_words = ctr_words * nbins;
-    size_t o_rng = take(Pz), o_smp = take(Pz), o_depth = take(Pz), o_col = take(3 * Pz),
-           o_light = take(kMaxDepth * Pz), o_ray = take(6 * Pz), o_hit = take(3 * Pz),
-           o_hid = take(Pz), o_sho = take(3 * Pz), o_q0 = take(qcap), o_q1 = take(qcap),
-           o_qs = take(qcap_s), o_ctl = take(3 * ectr_words + 2 * ctr_words + 64), o_tot = take(16),
-           o_ovf = take(ovf_words);
-#ifdef TMPT_DIAG
-    const bool log_iters = getenv("TMPT_ITER_LOG") != nullptr;  // diagnostic build: queue sizes per iteration
-#else
-    const bool log_iters = false;
-#endif
-    const int64_t max_log = (int64_t)a.spp * (kMaxDepth + 2) + 64 + 16;
-    size_t o_log = log_iters ? take(2 * (size_t)max_log) : 0;
-    if (ensure_ws(s, words * 4)) return -1;
-    uint32_t* w = (uint32_t*)s.ws;
-    WfState st;
-    st.rng = w + o_rng;
-    st.smp = w + o_smp;
-    st.depth = w + o_depth;
-    st.col = (float*)(w + o_col);
-    st.light = (float*)(w + o_light);
-    st.ray = (float*)(w + o_ray);
-    st.hit = (float*)(w + o_hit);
-    st.hid = (int32_t*)(w + o_hid);
-    st.sho = (float*)(w + o_sho);
-    st.q[0] = w + o_q0;
-    st.q[1] = w + o_q1;
-    st.qs = w + o_qs;
-    st.cnt[0] = w + o_ctl;
-    st.cnt[1] = st.cnt[0] + ectr_words;
-    st.head_e = st.cnt[1] + ectr_words;
-    st.cnt_s = st.head_e + ectr_words;
-    st.head_s = st.cnt_s + ctr_words;
-    st.total = st.head_s + ctr_words;
-    st.tot = (unsigned long long*)(w + o_tot);
-    st.iter_log = log_iters ? w + o_log : nullptr;
-    st.P = P;
-    st.seg_cap = (uint32_t)seg_cap;
-    st.nbins = nbins;
-    // low load: under two queue entries per resident traversal lane; binned
-    // queues always (most of their sub-queues are empty)
-    st.walk_check = nbins > 1 || P < 2 * (int64_t)grid_t * kBlk;
-    st.root_check = a.root_check;
-    uint32_t* ovf = w + o_ovf;
-    hipStream_t str = s.stream;
-
-    TMPT_HIP(hipMemsetAsync(w + o_ctl, 0, (3 * ectr_words + 2 * ctr_words + 64) * 4, str));
-    TMPT_HIP(hipMemsetAsync(st.tot, 0, 8 * sizeof(unsigned long long), str));
-    if (st.iter_log) TMPT_HIP(hipMemsetAsync(st.iter_log, 0, 8 * (size_t)max_log, str));
-    k_wf_generate<kBlk><<<(int)((std::max<int64_t>(P, kSeg) + kBlk - 1) / kBlk), kBlk, 0, str>>>(a, st);
-
-    // per-launch timing of the traversal kernels
-    std::vector<hipEvent_t> ev;
-    auto new_ev = [&]() {
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        ev.push_back(e);
-        return e;
-    };
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ext_ev, sh_ev;
-    uint32_t* h_cnt = nullptr;
-    TMPT_HIP(hipHostMalloc((void**)&h_cnt, 16, hipHostMallocDefault));
-    const int kCheck = 8;
-    int parity = 0;
-    int64_t it = 0;
-    int rc = 0;
-    for (;;) {
-        for (int k = 0; k < kCheck; ++k, ++it) {
-            hipEvent_t e0 = new_ev(), e1 = new_ev(), e2 = new_ev(), e3 = new_ev();
-            (void)hipEventRecord(e0, str);
-            trace_e<<<grid_t, kBlk, 0, str>>>(view(s), st, parity, ovf);
-            (void)hipEventRecord(e1, str);
-            k_wf_shade<kBlk><<<grid_sh, kBlk, 0, str>>>(view(s), a, st, parity, d_out);
-            (void)hipEventRecord(e2, str);
-            trace_s<<<grid_t, kBlk, 0, str>>>(view(s), st, parity, ovf);
-            (void)hipEventRecord(e3, str);
-            k_wf_advance<<<1, kSeg, 0, str>>>(st, parity, (int)std::min<int64_t>(it, max_log - 1));
-            ext_ev.push_back({e0, e1});
-            sh_ev.push_back({e2, e3});
-            parity ^= 1;
-        }
-        if (hipGetLastError() != hipSuccess) { rc = -1; break; }
-        if (hipMemcpyAsync(h_cnt, st.total, 4, hipMemcpyDeviceToHost, str) != hipSuccess ||
-            hipStreamSynchronize(str) != hipSuccess) { rc = -1; break; }
-        if (h_cnt[0] == 0) break;
-        if (it > (int64_t)a.spp * (kMaxDepth + 2) + 64) {  // each pixel needs <= spp*(kMaxDepth+1) iterations
-            set_error("wavefront: iteration bound exceeded");
-            rc = -3;
-            break;
-        }
-    }
-    unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (rc == 0) {
-        TMPT_HIP(hipMemcpyAsync(tot, st.tot, sizeof(tot), hipMemcpyDeviceToHost, str));
-        TMPT_HIP(hipStreamSynchronize(str));
-        if (log_iters) {
-            std::vector<uint32_t> lg(2 * (size_t)std::min<int64_t>(it, max_log));
-            TMPT_HIP(hipMemcpy(lg.data(), st.iter_log, lg.size() * 4, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < lg.size() / 2; ++k)
-                fprintf(stderr, "tmpt-iter %zu extend %u shadow %u\n", k, lg[2 * k], lg[2 * k + 1]);
-            if (count) fprintf(stderr, "tmpt-max-steps extend %llu shadow %llu\n", tot[6], tot[7]);
-        }
-    }
-    double ems = 0, sms = 0;
-    for (auto& pr : ext_ev) { float ms = 0; (void)hipEventElapsedTime(&ms, pr.first, pr.second); ems += ms; }
-    for (auto& pr : sh_ev) { float ms = 0; (void)hipEventElapsedTime(&ms, pr.first, pr.second); sms += ms; }
-    for (auto e : ev) (void)hipEventDestroy(e);
-    (void)hipHostFree(h_cnt);
-    if (rc) {
-        if (rc == -1) set_error("wavefront: HIP error");
-        return rc;
-    }
-    s.extend_ms = ems;
-    s.shadow_ms = sms;
-    s.extend_rays = tot[0];
-    s.shadow_rays = tot[1];
-    s.node_visits = tot[2];
-    s.tri_tests = tot[3];
-    s.shadow_node_visits = tot[4];
-    s.shadow_tri_tests = tot[5];
-    s.extend_launches = it;
-    s.shadow_launches = it;
-    s.iterations = it;
-    return 0;
-}
-
-// The heaviest pixels of a pixel-seeded frame as speculative chains
-// (render_rowspec's engine with a chain = one pixel): pixel cpix[r], its
-// samples smp0 .. smp0 + cspp - 1, from the state the pilot pass left in
-// cinit[pixel] (colour sum of samples 0 .. smp0-1, RNG state in .w).
-struct PixelChains {
-    const uint32_t* cpix;
-    const float4* cinit;
-    int n, smp0, cspp;
-};
-int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters,
-                   const PixelChains* ch = nullptr);
-
-// The chains' pixels: the pilot's colour sum, then samples smp0 .. spp-1 from
-// the colour buffer, in sample order (main.cpp:218), packed (main.cpp:221-233).
-// sums (tmpt_render_radiance; null otherwise): the pixel's float sum is kept
-// there too, as pass 2 keeps the other pixels' (it may be cinit itself: each
-// thread reads its own pixel's entry before it writes it).
-__global__ void __launch_bounds__(256) k_resolve_chains(PixelChains ch, const float4* __restrict__ sbuf, int32_t spp,
-                                                        float spp_recip, uint32_t* __restrict__ out,
-                                                        float4* sums = nullptr)
-{
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= ch.n) return;
-    const uint32_t p = ch.cpix[r];
-    const float4 c0 = ch.cinit[p];
-    f3 col = mk(c0.x, c0.y, c0.z);
-    for (int32_t k = ch.smp0; k < spp; ++k) {
-        const float4 c = sbuf[(size_t)p * (size_t)spp + (size_t)k];
-        col = col + mk(c.x, c.y, c.z);
-    }
-    if (sums) sums[p] = make_float4(col.x, col.y, col.z, c0.w);
-    out[p] = pack_pixel(col, spp_recip);
-}
-
 // PathCtl::top_walk from option top_walk: the round cap, or (-1, auto) the
 // seeding's measured default.  seeding: 0 sample, 1 pixel, 2 row (both row
 // engines and the pixel chains).  Bench frame, same box, parent / cap 0 / 2 /
@@ -3068,7 +1760,7 @@ __global__ void __launch_bounds__(256) k_resolve_chains(PixelChains ch, const fl
 // seeding, k_path ms, cap 0 / 2 / 4 / 8: N=1 192.6 / 193.9 / 194.8 / 204.8,
 // 1/8 35.3 / 35.6 / 35.0 / 36.7 -- no cap gains there, so off.
 constexpr int kTopWalkSample = 4, kTopWalkPixel = 0, kTopWalkRow = 4;
-static uint32_t top_walk_cap(const Options& o, int seeding)
+uint32_t top_walk_cap(const Options& o, int seeding)
 {
     if (o.top_walk >= 0) return (uint32_t)o.top_walk;
     return (uint32_t)(seeding == 0 ? kTopWalkSample : seeding == 1 ? kTopWalkPixel : kTopWalkRow);
@@ -3079,7 +1771,7 @@ static uint32_t top_walk_cap(const Options& o, int seeding)
 // drift along a crack (octree_crack's test at the smallest t a hit can have,
 // kMinT): the constant light of main.cpp:36 never can in these scenes, but
 // the test is the device's own.
-static uint32_t oct_shadow_check(const Scene& s)
+uint32_t oct_shadow_check(const Scene& s)
 {
     if (!s.oct_view || s.opt.tie_rule != 0) return 0u;
     if (s.oct_flat > 0) return 1u;
@@ -3598,654 +2290,6 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     return 0;
 }
 
-// A row engine's k_path variant (PathVariant; the table's rows group): its
-// unit kind, LDS stack, blocks per CU, cadence and tie rule.  The row engines
-// never count, profile, offload shadows, read the SoA planes or store sums.
-static PathVariant row_variant(int samp, int sl, int occ, int steps, int shade_min, int ties)
-{
-    PathVariant v{};
-    v.sl = sl;
-    v.steps = steps;
-    v.shade_min = shade_min;
-    v.occ = occ;
-    v.samp = samp;
-    v.ties = ties;
-    return v;
-}
-
-// Streaming row engine (RsStream above): one k_path<SAMP 4> launch whose first
-// blocks chase the rows' chains while the rest trace the windows' units, then
-// the chain's samples in full (k_path<SAMP 2> over the chain list) and the
-// in-order sums (k_resolve_px).  Returns 1 when it does not apply (limits,
-// memory) and 2 when the launch aborted (its watchdog: no chain progress for
-// ~1 s); the caller runs render_rowspec instead.
-int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters)
-{
-    const Options& o = s.opt;
-    // with the reference's octree answering (tie_rule visit) the leaves only
-    // flag a tie and keep the first triangle met (TIES 2): the flagged query's
-    // answer comes from the octree either way, so the lowest-index bookkeeping
-    // is not needed (option row_flag_leaves 0 keeps it, for A/B)
-    const bool flag = s.oct_view && o.tie_rule == 0 && o.row_flag_leaves;
-    const int ties = flag ? 2 : 0;
-    // the chain's full re-trace at 5 waves per SIMD (option path_waves, as the
-    // sample kernels: the 30-KB LDS layout of OCC 5)
-    const bool w5 = o.path_waves != 4;
-    // the workers at kRsOcc3 blocks per CU, or at 4 waves per SIMD (no spills)
-    // for light loads (option row_occ)
-    PathFn fn2, fn4, fn4_occ4;
-    if (int rc = find_path_kernel(row_variant(2, w5 ? kPathSL5 : kPathSL, w5 ? 5 : 4, kRowSteps, kRowShadeMin, ties),
-                                  "render_rowstream", fn2))
-        return rc;
-    if (int rc = find_path_kernel(row_variant(4, kPathSL, kRsOcc3, kRowSteps, kRowShadeMin, ties), "render_rowstream", fn4))
-        return rc;
-    if (int rc = find_path_kernel(row_variant(4, kPathSL, 4, kRowSteps, kRowShadeMin, ties), "render_rowstream", fn4_occ4))
-        return rc;
-    const int rows = a.tile_rows;
-    const uint32_t W = (uint32_t)a.W, spp = (uint32_t)a.spp, T = (uint32_t)kRssT;
-    const size_t lcap = (size_t)a.slots * spp;  // chain samples of the tile
-    // a pixel's offsets per window ~ spp x 8.5 (draws / 2); the ring holds the
-    // live windows with room to spare (pow2 >= 16 x spp x 8)
-    uint32_t R = 1024;
-    while (R < 128u * spp) R <<= 1;
-    // offsets live in 24-bit fields: ~8.5 per sample on average, 14 allowed,
-    // plus 2^20 of room for the workers' fetch-adds past a window's end
-    if (rows < 1 || W > 4094u || (uint64_t)W * spp * 14u + R + (1u << 20) >= (1ull << 24) || lcap >= (1ull << 31))
-        return 1;
-    int grid = occupancy_grid((const void*)fn4, kBlk, 0, s.device);
-    const int grid2 = occupancy_grid((const void*)fn2, kBlk, 0, s.device);
-    const int nchase = (rows + kBlk - 1) / kBlk;  // blocks of 4 waves x 64 rows
-    if (grid <= 2 * nchase) return 1;
-    {
-        // 5 waves per SIMD (96 VGPRs, 10 spilled dwords) win at full load, 4
-        // (no spills) once the GPU has room per row: bench frame, row seeding,
-        // 4 / 5 / 6 waves, N=1 1944.7 / 1854.6 / 1889.9 ms, 1/8 436.0 / 450.5 /
-        // 477.1 ms; 4 / 5 waves at 1/2 1048.8 / 1043.6, 1/4 639.7 / 658.9, 1/8
-        // 434.4 / 450.4 ms (room 1.1, 2.2, 4.4; profiles/r05_experiments/
-        // row_worker_occupancy*.log): 4 waves from room 1.6
-        const double room5 = (double)(grid - nchase) * kBlk / ((double)rows * (double)spp * 8.5);
-        const bool occ4 = o.row_occ == 4 || (o.row_occ == 0 && room5 >= 1.6);
-        const int g4 = occ4 ? occupancy_grid((const void*)fn4_occ4, kBlk, 0, s.device) : 0;
-        if (occ4 && g4 > 2 * nchase) {
-            fn4 = fn4_occ4;
-            grid = g4;
-        }
-    }
-    // live windows per row: 2.6 + 1.5 ln(room), room = resident lanes per
-    // pixel window of all rows, within 2..kRssT-1.  Bench frame, 64 spp
-    // (profiles/r03_rowspec/stream_windows_*, with the spread rule below):
-    // best 2 windows at N = 1 (1.82 s), 3 at 1/2 (1.05 s), 4 at 1/4 (0.65 s),
-    // 4-5 at 1/8 (0.44 s); this rule picks 2, 3, 4, 5
-    const int64_t lanes = (int64_t)(grid - nchase) * kBlk;
-    const double E_est = (double)spp * 8.5;
-    const double room = (double)lanes / ((double)rows * E_est);  // resident lanes per pixel window of all rows
-    // Round 5: the chasers re-apply both rules as rows finish (RsStream::dyn,
-    // room per live row): the rows end over ~500 ms of the 1.7 s launch
-    // (profiles/r05_wavetime/row_*.log) and the ones left get more windows;
-    // N=1 1909 -> 1875 ms, 1/2 1085 -> 1054, 1/8 462.5 -> 459.6 (option
-    // rowstream_dynamic; profiles/r05_experiments/row_dynamic_windows.log).
-    // More slots per row (TMPT_RSS_T=16) changed nothing (row_rss16.log).
-    int nw = (int)std::lround(2.6 + 1.5 * std::log(std::max(room, 1e-3)));
-    nw = std::max(2, std::min(kRssT - 1, nw));
-    if (o.rowspec_windows > 0) nw = std::min(kRssT - 1, o.rowspec_windows);
-    const uint32_t na = (uint32_t)(((uint64_t)W * spp * 14u + R) >> 14) + 1u;
-    const size_t ovf_words = std::max((size_t)grid * (kStackTotal - kPathSL), (size_t)grid2 * (kStackTotal - kPathSL5)) * kBlk;
-    const size_t head_words = (size_t)kSeg * kCtr;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_res = al((size_t)rows * T * R * 8), b_slots = al((size_t)rows * (T + 1) * 8),
-                 b_pos = al((size_t)rows * 8), b_rays = al((size_t)rows * 2 * 4), b_lo = al((size_t)rows * T * 4),
-                 b_ctl = al(64), b_ctr = al(24 * 8), b_anch = al((size_t)rows * na * 4),
-                 b_ovf = al((ovf_words + head_words) * 4);
-    const size_t zero_bytes = b_res + b_slots + b_pos + b_rays + b_lo + b_ctl + b_ctr;
-    const size_t need = zero_bytes + b_anch + b_ovf;
-    const size_t lneed = lcap * sizeof(uint32_t), sneed = lcap * sizeof(float4);
-    {
-        size_t fr = 0, tot = 0;
-        const size_t budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.rss_bytes +
-                              s.rs_list_bytes + s.sbuf_bytes;
-        if (need + lneed + sneed > budget) return 1;
-    }
-    auto grow = [](void*& p, size_t& have, size_t want) -> int {
-        if (have >= want) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        have = 0;
-        if (hipMalloc(&p, want) != hipSuccess) return -1;
-        have = want;
-        return 0;
-    };
-    // HBM short after the budget check (another allocation raced it): the
-    // iterated engine may still fit, so fall back rather than fail the frame
-    // (grow() has freed the old buffer; the failed hipMalloc's error is cleared)
-    if (grow(s.rss_buf, s.rss_bytes, need) || grow(s.rs_list, s.rs_list_bytes, lneed)) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    {
-        void* sb = s.sbuf;
-        const int g = grow(sb, s.sbuf_bytes, sneed);
-        s.sbuf = static_cast<float4*>(sb);
-        if (g) {
-            (void)hipGetLastError();
-            return 1;
-        }
-    }
-    if (!s.rss_tab) {  // M^(2c) and M^(256b) for c, b < 128; M^(2^15 a0), M^(2^20 a1) for a0, a1 < 32
-        std::vector<uint32_t> tab, t;
-        jump_tables(2, 128, t);
-        tab.insert(tab.end(), t.begin(), t.end());
-        jump_tables(256, 128, t);
-        tab.insert(tab.end(), t.begin(), t.end());
-        jump_tables(1ull << 15, 32, t);
-        tab.insert(tab.end(), t.begin(), t.end());
-        jump_tables(1ull << 20, 32, t);
-        tab.insert(tab.end(), t.begin(), t.end());
-        uint32_t* nt = nullptr;
-        TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-        if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
-            set_error("render_rowstream: jump table upload failed");
-            return -1;
-        }
-        s.rss_tab = nt;
-    }
-    if (!s.rss_host) TMPT_HIP(hipHostMalloc((void**)&s.rss_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
-    char* p = static_cast<char*>(s.rss_buf);
-    RsStream S;
-    memset(&S, 0, sizeof(S));
-    S.res = reinterpret_cast<unsigned long long*>(p);
-    p += b_res;
-    S.slots = reinterpret_cast<unsigned long long*>(p);
-    p += b_slots;
-    S.chainpos = reinterpret_cast<unsigned long long*>(p);
-    p += b_pos;
-    S.rowrays = reinterpret_cast<uint32_t*>(p);
-    p += b_rays;
-    S.lo = reinterpret_cast<uint32_t*>(p);
-    p += b_lo;
-    S.ctl = reinterpret_cast<uint32_t*>(p);
-    p += b_ctl;
-    unsigned long long* spec_ctr = reinterpret_cast<unsigned long long*>(p);  // traced (not chain) rays
-    p += b_ctr;
-    S.anchors = reinterpret_cast<uint32_t*>(p);
-    p += b_anch;
-    uint32_t* ovf = reinterpret_cast<uint32_t*>(p);
-    uint32_t* heads = ovf + ovf_words;
-    S.list = static_cast<uint32_t*>(s.rs_list);
-    S.t1 = s.rss_tab;
-    S.t2 = s.rss_tab + 128 * 1024;
-    S.na = na;
-    S.jlimit = na << 14;
-    S.R = R;
-    S.rmask = R - 1u;
-    S.nrows = rows;
-    S.nchase = nchase;
-    S.nw = nw;
-    S.watchdog = o.rowstream_test_abort ? 200000u : 100000000u;  // ~1 s (2 ms when testing the abort)
-    S.test_abort = o.rowstream_test_abort;
-    // window spread in pixels: 0.055 x room - 0.015, within 0..0.25.  Bench
-    // frame, 64 spp (profiles/r03_rowspec/stream_spread_*): best at 0 - 0.02
-    // for N = 1 (1.82 s; 2.03 s at the earlier 0.10), 0.06 - 0.08 at 1/2, 0.12 -
-    // 0.15 at 1/4, 0.18 - 0.22 at 1/8 (0.44 s); at full load the chaser's demand
-    // and extension windows are cheaper than a wide spread
-    S.spread = o.rowspec_spread >= 0.0f ? o.rowspec_spread
-                                        : (float)std::min(0.25, std::max(0.0, 0.055 * room - 0.015));
-    S.room_lanes = (float)((double)lanes / E_est);
-    S.dyn = o.rowstream_dynamic ? ((o.rowspec_windows > 0 ? 0u : 1u) | (o.rowspec_spread >= 0.0f ? 0u : 2u)) : 0u;
-    TMPT_HIP(hipMemsetAsync(s.rss_buf, 0, zero_bytes, s.stream));
-    {
-        const size_t n = (size_t)rows * na;
-        k_rss_anchors<<<(unsigned)((n + 255) / 256), 256, 0, s.stream>>>(a, S, s.rss_tab + 256 * 1024,
-                                                                        s.rss_tab + 288 * 1024);
-        TMPT_HIP(hipGetLastError());
-    }
-    RenderArgs as = a;
-    as.jt = nullptr;
-    as.bmask = 0u;  // every unit is one sample
-    as.smp_begin = 0;
-    as.smp_end = a.spp;
-    PathCtl pc;
-    memset(&pc, 0, sizeof(pc));
-    pc.heads = heads;
-    pc.nblk = pc.blk = 1u;
-    pc.lane_cap = 64u;
-    pc.chunk = kChunk;
-    pc.rs_noshadow = 1;
-    pc.oct_shadow = oct_shadow_check(s);
-    pc.top_walk = top_walk_cap(o, 2);
-    pc.rss = S;
-    fn4<<<grid, kBlk, 0, s.stream>>>(view(s), as, pc, d_out, ovf, spec_ctr);
-    TMPT_HIP(hipGetLastError());
-    TMPT_HIP(hipMemcpyAsync(s.rss_host, S.ctl, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-    TMPT_HIP(hipStreamSynchronize(s.stream));
-#ifdef TMPT_EXP_WAVETIME
-    {
-        std::vector<unsigned long long> w(3 * kWaveTimeMax, 0ull), r(kWaveTimeMax, 0ull), cl(kWaveTimeMax, 0ull);
-        if (hipMemcpyFromSymbol(w.data(), HIP_SYMBOL(g_wavetime), w.size() * 8) == hipSuccess &&
-            hipMemcpyFromSymbol(r.data(), HIP_SYMBOL(g_rowtime), r.size() * 8) == hipSuccess &&
-            hipMemcpyFromSymbol(cl.data(), HIP_SYMBOL(g_claimtime), cl.size() * 8) == hipSuccess) {
-            unsigned long long t0 = ~0ull, tend = 0;
-            for (int i = 0; i < kWaveTimeMax; ++i)
-                if (w[3 * i] && w[3 * i + 2]) {
-                    t0 = std::min(t0, w[3 * i]);
-                    tend = std::max(tend, w[3 * i + 2]);
-                }
-            std::vector<double> rt;
-            for (int i = 0; i < std::min(rows, kWaveTimeMax); ++i)
-                if (r[i]) rt.push_back((r[i] - t0) * 0.01);
-            std::sort(rt.begin(), rt.end());
-            auto q = [&](double f) { return rt.empty() ? 0.0 : rt[std::min(rt.size() - 1, (size_t)(f * (rt.size() - 1)))]; };
-            fprintf(stderr, "rowstream rows %zu done at us p0/p10/p50/p90/p99/p100 %.0f/%.0f/%.0f/%.0f/%.0f/%.0f; "
-                            "last worker exit %.0f\n",
-                    rt.size(), q(0), q(0.1), q(0.5), q(0.9), q(0.99), q(1), (tend - t0) * 0.01);
-            std::vector<double> lc;  // each worker wave's last claim of speculation work
-            for (int i = 0; i < kWaveTimeMax; ++i)
-                if (w[3 * i] && w[3 * i + 2] && cl[i]) lc.push_back((cl[i] - t0) * 0.01);
-            std::sort(lc.begin(), lc.end());
-            auto ql = [&](double f) { return lc.empty() ? 0.0 : lc[std::min(lc.size() - 1, (size_t)(f * (lc.size() - 1)))]; };
-            fprintf(stderr, "rowstream workers %zu: last claim at us p0/p10/p25/p50/p75/p90/p100 "
-                            "%.0f/%.0f/%.0f/%.0f/%.0f/%.0f/%.0f\n",
-                    lc.size(), ql(0), ql(0.1), ql(0.25), ql(0.5), ql(0.75), ql(0.9), ql(1));
-            std::fill(w.begin(), w.end(), 0ull);
-            std::fill(r.begin(), r.end(), 0ull);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wavetime), w.data(), w.size() * 8);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rowtime), r.data(), r.size() * 8);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_claimtime), r.data(), r.size() * 8);
-        }
-    }
-#endif
-    if (s.rss_host[1] != 0u || s.rss_host[3] != 0u || s.rss_host[0] != (uint32_t)rows) {
-#ifdef TMPT_DIAG
-        fprintf(stderr, "rowstream: aborted (rows done %u of %d, abort %u, error %u); iterated engine instead\n",
-                s.rss_host[0], rows, s.rss_host[1], s.rss_host[3]);
-#endif
-        return 2;  // launched and aborted: the caller falls back and records it (tmpt_stats.stream_fallbacks)
-    }
-    // the chain's samples in full (shadows included), then the in-order sums
-    k_rss_states<<<(unsigned)((lcap + 255) / 256), 256, 0, s.stream>>>(a, S);
-    PathCtl pc2 = pc;
-    pc2.upix = nullptr;  // unit u = sample u % spp of tile pixel u / spp
-    pc2.uslot = nullptr;
-    pc2.ustate = S.list;
-    pc2.p_dev = S.ctl + 4;
-    pc2.rs_noshadow = 0;
-    pc2.sbuf = s.sbuf;
-    pc2.sb_ss = 1u;
-    pc2.sb_sp = spp;
-    TMPT_HIP(hipMemsetAsync(heads, 0, head_words * 4, s.stream));
-    fn2<<<grid2, kBlk, 0, s.stream>>>(view(s), as, pc2, d_out, ovf, spec_ctr + 16);
-    k_resolve_px<<<(unsigned)((a.slots + 63) / 64), 64, 0, s.stream>>>(s.sbuf, a.slots, a.spp, a.spp_recip, d_out);
-    k_rss_count<<<(unsigned)((rows + 255) / 256), 256, 0, s.stream>>>(S, d_counters);
-    TMPT_HIP(hipGetLastError());
-    s.path_launches = 1;
-#ifdef TMPT_DIAG
-    if (getenv("TMPT_ROWSPEC_LOG")) {
-        unsigned long long c[2] = {0, 0}, t = 0;
-        TMPT_HIP(hipMemcpyAsync(c, d_counters, sizeof(c), hipMemcpyDeviceToHost, s.stream));
-        TMPT_HIP(hipMemcpyAsync(&t, spec_ctr, sizeof(t), hipMemcpyDeviceToHost, s.stream));
-        TMPT_HIP(hipStreamSynchronize(s.stream));
-        fprintf(stderr,
-                "rowstream: %d rows, %d worker blocks + %d chaser blocks, ring %u, %d windows, traced rays %llu for "
-                "%llu chain rays (x%.2f), chain ticks %u\n"
-                "rowstream: claims %u, row misses %u, lost CAS %u; chaser waits %u, extensions %u, prefixes %u, "
-                "sweeps %u\n",
-                rows, grid - nchase, nchase, R, nw, t, c[0], c[0] ? (double)t / (double)c[0] : 0.0, s.rss_host[2],
-                s.rss_host[5], s.rss_host[6], s.rss_host[7], s.rss_host[8], s.rss_host[9], s.rss_host[10],
-                s.rss_host[11]);
-    }
-#endif
-    return 0;
-}
-
-// Speculative row seeding (k_rs_* above): iterations of plan -> fill ->
-// k_path<SAMP 2> -> chase until every row of the tile has its W pixels.  Each
-// iteration moves every unfinished row through (usually) one pixel.  The rows
-// are split into G groups, each iterating on its own stream, so one group's
-// k_path tail overlaps another's work; the unit counts stay on the device and
-// the host only checks for completion every kCheck iterations.
-int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long long* d_counters,
-                   const PixelChains* ch)
-{
-    const Options& o = s.opt;
-    // rows: a.tile_rows chains of W pixels x spp samples; pixel chains (ch):
-    // ch->n chains of one pixel x ch->cspp samples
-    const int cspp = ch ? ch->cspp : a.spp;
-    constexpr int kCheck = 64;
-    // the units in full (SAMP 2; lowest-index ties whatever the octree: this
-    // engine has no flagging variant), and
-    // the shadow-free pass: its own instantiation (no shadow, light or colour
-    // code, no light / next-ray LDS): 96 VGPRs, 5 waves per SIMD (6 waves: 80
-    // VGPRs and 21 spilled dwords, neutral)
-    PathFn fn, fn3;
-    if (int rc = find_path_kernel(row_variant(2, kPathSL, 4, kRowIterSteps, kRowIterShadeMin, 0), "render_rowspec", fn))
-        return rc;
-    if (int rc = find_path_kernel(row_variant(3, kPathSL, kRsOcc3, kRowIterSteps, kRowIterShadeMin, 0), "render_rowspec", fn3))
-        return rc;
-    const int grid = occupancy_grid((const void*)fn, kBlk, 0, s.device);
-    const int grid3 = occupancy_grid((const void*)fn3, kBlk, 0, s.device);
-    const int rows = ch ? ch->n : a.tile_rows;
-    // window cap: one iteration covers a pixel's samples at up to 2 * wmax / spp
-    // = 48 draws per sample (the stand-in sponza averages ~17, its deepest rows
-    // ~25; a cap of 24 draws left those rows one short window per pixel, and
-    // the slowest row sets the iteration count)
-    uint32_t wmax = (uint32_t)std::min<int64_t>(8192, std::max<int64_t>(64, (int64_t)cspp * 24));
-    if (o.rowspec_wmax > 0) wmax = (uint32_t)o.rowspec_wmax;
-    // row groups, each on its own stream (one group: 3 % slower)
-    const int G = std::max(1, std::min(std::min(o.rowspec_groups, kRowSpecMaxGroups), rows));
-    // every group's k_path gets the whole resident grid (splitting the GPU
-    // between the groups, or reserving fewer than 64 units per wave, did not help)
-    const int pgrid = grid, pgrid3 = grid3;
-    const uint32_t chunk = kChunk;
-    // lookahead windows (pixels x+1, x+2, ...; each around its expected
-    // start and end): one iteration covers up to nwin pixels of a row.  The
-    // extra speculation is cheap while the GPU has room: nwin ~ 5 units per
-    // resident lane over the rows' expected pixel windows (~17 draws per
-    // sample), 2..kRsMaxWin -- 2 on the whole bench frame, 8 from 1/4 of it.
-    // The far windows' spread grows with a pixel's units E = spp x ~8.5, so
-    // the windows of one iteration are also capped at ~4400 units per row
-    // (8 windows at 64 spp).  Measured (profiles/r02_rowspec/rs16): 640x360x4
-    // suzanne 88 -> 51 ms with 8 -> 32 windows; the 1/8 shard of the bench
-    // frame 708 ms with 8 windows, 746 with 18.
-    const int64_t lanes = (int64_t)pgrid * kBlk;
-    const double E_est = (double)cspp * 8.5;
-    int nwin = (int)std::lround(std::min((double)lanes * 5.0 / ((double)rows * E_est), 4400.0 / E_est));
-    nwin = std::max(2, std::min(kRsMaxWin, nwin));
-    if (o.rowspec_windows > 0) nwin = std::min(kRsMaxWin, o.rowspec_windows);
-    if (ch) nwin = 1;  // a pixel chain has one pixel: no lookahead windows
-    const uint32_t jmax = (uint32_t)nwin * wmax;  // window i ends by (i + 1) * wmax
-    // Speculate without shadow traversals and re-trace the chain in full at the
-    // end (the frame's chain list and colour buffer must fit; else the colours
-    // come from the speculative pass).  Bench frame 3.03 -> 2.49 s, 1/8 shard
-    // 0.71 -> 0.61 s (profiles/r02_rowspec/rs19).  Option rowspec_noshadow.
-    bool noshadow = o.rowspec_noshadow != 0 || ch;
-    // chain samples of the tile (pixel chains: theirs); the colour buffer is
-    // the tile's [pixel][sample] in either case
-    const size_t lcap = ch ? (size_t)ch->n * (size_t)cspp : (size_t)a.slots * (size_t)a.spp;
-    const uint32_t scap = (uint32_t)nwin * (uint32_t)cspp;  // a row's chain samples per iteration
-    if (noshadow) {
-        const size_t lneed = lcap * 3 * sizeof(uint32_t) + (size_t)rows * scap * sizeof(uint2) + 256;
-        const size_t sneed = (size_t)a.slots * (size_t)a.spp * sizeof(float4);
-        size_t fr = 0, tot = 0;
-        const size_t budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.rs_list_bytes + s.sbuf_bytes;
-        if (lcap >= (1ull << 32) || lneed + sneed > budget) {
-            if (ch) return 1;  // pixel chains need the re-trace: the caller renders them in pass 2
-            noshadow = false;  // does not fit: the colours come from the speculative pass
-        } else {
-            if (s.rs_list_bytes < lneed) {
-                if (s.rs_list) (void)hipFree(s.rs_list);
-                s.rs_list = nullptr;
-                s.rs_list_bytes = 0;
-                TMPT_HIP(hipMalloc(&s.rs_list, lneed));
-                s.rs_list_bytes = lneed;
-            }
-            if (s.sbuf_bytes < sneed) {
-                if (s.sbuf) (void)hipFree(s.sbuf);
-                s.sbuf = nullptr;
-                s.sbuf_bytes = 0;
-                TMPT_HIP(hipMalloc(&s.sbuf, sneed));
-                s.sbuf_bytes = sneed;
-            }
-        }
-    }
-    uint32_t* lpix = nullptr;
-    uint32_t* lstate = nullptr;
-    uint32_t* lslot = nullptr;
-    uint32_t* lcount = nullptr;
-    uint2* scratch = nullptr;
-    if (noshadow) {
-        lcount = static_cast<uint32_t*>(s.rs_list);
-        scratch = reinterpret_cast<uint2*>(static_cast<char*>(s.rs_list) + 256);
-        lpix = reinterpret_cast<uint32_t*>(scratch + (size_t)rows * scap);
-        lstate = lpix + lcap;
-        lslot = lstate + lcap;
-    }
-    if (s.jt2_n < (int32_t)jmax) {  // J_j = M^(2j): the state 2j draws on
-        std::vector<uint32_t> tab;
-        jump_tables(2, (int32_t)jmax, tab);
-        uint32_t* nt = nullptr;
-        TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-        if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
-            set_error("tmpt_render: jump table upload failed");
-            return -1;
-        }
-        if (s.jt2) (void)hipFree(s.jt2);
-        s.jt2 = nt;
-        s.jt2_n = (int32_t)jmax;
-    }
-    const size_t ovf_words = (size_t)std::max(pgrid, pgrid3) * kBlk * (kStackTotal - kPathSL);
-    const size_t head_words = (size_t)kSeg * kCtr;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    auto group_rows = [&](int g) { return rows / G + (g < rows % G ? 1 : 0); };
-    auto group_bytes = [&](int g) {
-        const size_t R = (size_t)group_rows(g), U = R * jmax;
-        return al(U * (sizeof(float4) + 3 * sizeof(uint32_t)) + R * sizeof(float4) +
-                  ((9 + 2 * (size_t)kRsMaxWin) * R + 2) * sizeof(uint32_t) +
-                  (ovf_words + head_words) * sizeof(uint32_t));
-    };
-    size_t need = al(24 * sizeof(unsigned long long));
-    for (int g = 0; g < G; ++g) need += group_bytes(g);
-    if (s.rs_bytes < need) {
-        if (s.rs_buf) (void)hipFree(s.rs_buf);
-        s.rs_buf = nullptr;
-        s.rs_bytes = 0;
-        TMPT_HIP(hipMalloc(&s.rs_buf, need));
-        s.rs_bytes = need;
-    }
-    if (!s.rs_host) TMPT_HIP(hipHostMalloc((void**)&s.rs_host, kRowSpecMaxGroups * sizeof(uint32_t)));
-    for (int g = 0; g < G; ++g)
-        if (!s.rs_stream[g]) {
-            TMPT_HIP(hipStreamCreateWithFlags(&s.rs_stream[g], hipStreamNonBlocking));
-            TMPT_HIP(hipEventCreateWithFlags(&s.rs_event[g], hipEventDisableTiming));
-        }
-    if (!s.rs_event[kRowSpecMaxGroups]) TMPT_HIP(hipEventCreateWithFlags(&s.rs_event[kRowSpecMaxGroups], hipEventDisableTiming));
-    char* p = static_cast<char*>(s.rs_buf);
-    unsigned long long* spec_ctr = reinterpret_cast<unsigned long long*>(p);  // every traced unit's rays
-    p += al(24 * sizeof(unsigned long long));
-    struct Group {
-        RowSpec rs;
-        PathCtl pc;
-        float4* rs_out;
-        uint32_t *upix, *ustate, *rs_end, *heads, *ovf;
-        size_t U;
-        hipStream_t st;
-    };
-    std::vector<Group> gs(G);
-    RenderArgs as = a;
-    as.jt = nullptr;
-    as.bmask = 0u;  // every unit is one sample
-    as.smp_begin = 0;
-    as.smp_end = a.spp;
-    int row0 = 0;
-    for (int g = 0; g < G; ++g) {
-        Group& q = gs[g];
-        char* gp = p;
-        p += group_bytes(g);
-        const size_t R = (size_t)group_rows(g);
-        q.U = R * jmax;
-        q.st = s.rs_stream[g];
-        q.rs.row0 = row0;
-        q.rs.nrows = (int)R;
-        q.rs.wmax = wmax;
-        q.rs.nwin = nwin;
-        // window placement: expected positions +- spread * sqrt(i) pixels;
-        // bench frame, 64 spp (profiles/r02_rowspec/rs15): spread 0.08 / 0.1 /
-        // 0.12 / 0.15 = 3.06 / 3.03 / 3.04 / 3.10 s whole, 0.85 / 0.74 / 0.69 /
-        // 0.67 s at 1/8 -- wider at low load, where speculation is cheap
-        // (with shadow-free speculation: 1/8 shard spread 0.154 / 0.2 = 640 / 576 ms,
-        // whole frame 0.106 / 0.14 / 0.2 = 2.51 / 2.52 / 2.62 s, rs20)
-        q.rs.spread = o.rowspec_spread >= 0.0f ? o.rowspec_spread : 0.07f + 0.016f * (float)nwin;
-        row0 += (int)R;
-        q.rs_out = reinterpret_cast<float4*>(gp);
-        gp += q.U * sizeof(float4);
-        q.rs.col = reinterpret_cast<float4*>(gp);
-        gp += R * sizeof(float4);
-        uint32_t* w = reinterpret_cast<uint32_t*>(gp);
-        q.upix = w;
-        q.ustate = q.upix + q.U;
-        q.rs_end = q.ustate + q.U;
-        w = q.rs_end + q.U;
-        uint32_t** fields[] = {&q.rs.rng, &q.rs.x, &q.rs.k, &q.rs.pdraws, &q.rs.prev_mean,
-                               &q.rs.rays, &q.rs.erays, &q.rs.short_win};
-        for (uint32_t** f : fields) {
-            *f = w;
-            w += R;
-        }
-        q.rs.win = w;  // kRsMaxWin x R each
-        w += kRsMaxWin * R;
-        q.rs.ws = w;
-        w += kRsMaxWin * R;
-        q.rs.offs = w;  // rows + 1
-        w += R + 1;
-        q.rs.total = w;
-        w += 1;
-        q.ovf = w;
-        q.heads = w + ovf_words;
-        memset(&q.pc, 0, sizeof(q.pc));
-        q.pc.heads = q.heads;
-        q.pc.nblk = q.pc.blk = 1u;
-        q.pc.lane_cap = 64u;
-        q.pc.chunk = chunk;
-        q.pc.upix = q.upix;
-        q.pc.ustate = q.ustate;
-        q.pc.rs_out = q.rs_out;
-        q.pc.rs_end = q.rs_end;
-        q.pc.p_dev = q.rs.total;
-        q.pc.rs_noshadow = noshadow ? 1 : 0;
-        q.pc.oct_shadow = oct_shadow_check(s);
-        q.pc.top_walk = top_walk_cap(o, 2);
-        q.rs.lpix = lpix;
-        q.rs.lstate = lstate;
-        q.rs.lslot = lslot;
-        q.rs.lcount = lcount;
-        q.rs.scratch = scratch ? scratch + (size_t)q.rs.row0 * scap : nullptr;
-        q.rs.scap = scap;
-        q.rs.planned = spec_ctr + 8;
-        q.rs.cpix = ch ? ch->cpix + q.rs.row0 : nullptr;
-        q.rs.cinit = ch ? ch->cinit : nullptr;
-        q.rs.cw = ch ? 1 : a.W;
-        q.rs.cspp = cspp;
-        q.rs.smp0 = ch ? ch->smp0 : 0;
-    }
-    // the groups start after the work already on the scene's stream (the
-    // caller's wait), and that stream resumes after all of them
-    TMPT_HIP(hipMemsetAsync(spec_ctr, 0, 24 * sizeof(unsigned long long), s.stream));
-    if (noshadow) TMPT_HIP(hipMemsetAsync(lcount, 0, 4, s.stream));
-    TMPT_HIP(hipEventRecord(s.rs_event[kRowSpecMaxGroups], s.stream));
-    for (Group& q : gs) {
-        TMPT_HIP(hipStreamWaitEvent(q.st, s.rs_event[kRowSpecMaxGroups], 0));
-        k_rs_init<<<(unsigned)((q.rs.nrows + 255) / 256), 256, 0, q.st>>>(a, q.rs);
-    }
-    TMPT_HIP(hipGetLastError());
-    // the listing pass's chase walks in LDS (one wave per row) when a row's
-    // chain samples of one iteration fit its list; option rowspec_chase 0 = the
-    // one-thread-per-row kernel
-    const bool chase_lds = noshadow && o.rowspec_chase != 0 && (uint64_t)nwin * (uint64_t)cspp <= kChaseList;
-    int it = 0;
-    // every iteration moves each unfinished row by >= 1 sample, so W * spp bounds them
-    const int64_t max_it = (int64_t)(ch ? 1 : a.W) * cspp + kCheck;
-    bool done = false;
-    // pixel chains finish in a few iterations: the host looks after each one
-    // (an empty iteration still launches the persistent grid, ~0.3 ms)
-    const int check = ch ? 1 : kCheck;
-    while (!done && it < max_it) {
-        for (int c = 0; c < check; ++c, ++it)
-            for (Group& q : gs) {
-                k_rs_plan<<<1, 1024, 0, q.st>>>(a, q.rs);
-                k_rs_fill<<<(unsigned)((q.U + 255) / 256), 256, 0, q.st>>>(a, q.rs, s.jt2, q.upix, q.ustate);
-                TMPT_HIP(hipMemsetAsync(q.heads, 0, head_words * 4, q.st));
-                if (noshadow) fn3<<<pgrid3, kBlk, 0, q.st>>>(view(s), as, q.pc, d_out, q.ovf, spec_ctr);
-                else fn<<<pgrid, kBlk, 0, q.st>>>(view(s), as, q.pc, d_out, q.ovf, spec_ctr);
-                if (chase_lds)
-                    k_rs_chase_lds<<<(unsigned)q.rs.nrows, 64, 0, q.st>>>(a, q.rs, q.rs_out, q.rs_end, q.upix,
-                                                                         q.ustate);
-                else
-                    k_rs_chase<<<(unsigned)((q.rs.nrows + 63) / 64), 64, 0, q.st>>>(a, q.rs, q.rs_out, q.rs_end,
-                                                                                    d_out, q.upix, q.ustate);
-            }
-        TMPT_HIP(hipGetLastError());
-        // the last plan of each group: 0 units = the group was already done
-        for (int g = 0; g < G; ++g)
-            TMPT_HIP(hipMemcpyAsync(&s.rs_host[g], gs[g].rs.total, 4, hipMemcpyDeviceToHost, gs[g].st));
-        done = true;
-        for (int g = 0; g < G; ++g) {
-            TMPT_HIP(hipStreamSynchronize(gs[g].st));
-            done = done && s.rs_host[g] == 0;
-        }
-    }
-    if (!done) {  // cannot happen: every iteration moves each unfinished row on
-        set_error("render_rowspec: rows unfinished after " + std::to_string(it) + " iterations");
-        for (Group& q : gs) (void)hipStreamSynchronize(q.st);
-        return -1;
-    }
-    for (int g = 0; g < G; ++g) {
-        k_rs_count<<<(unsigned)((gs[g].rs.nrows + 255) / 256), 256, 0, gs[g].st>>>(gs[g].rs, d_counters);
-        TMPT_HIP(hipEventRecord(s.rs_event[g], gs[g].st));
-        TMPT_HIP(hipStreamWaitEvent(s.stream, s.rs_event[g], 0));
-    }
-    TMPT_HIP(hipGetLastError());
-    if (noshadow) {  // the chain's samples in full (shadows included), then the in-order sums
-        PathCtl pc2 = gs[0].pc;
-        pc2.upix = lpix;
-        pc2.ustate = lstate;
-        pc2.uslot = lslot;
-        pc2.p_dev = lcount;
-        pc2.rs_noshadow = 0;
-        pc2.sbuf = s.sbuf;
-        pc2.sb_ss = 1u;
-        pc2.sb_sp = (uint32_t)a.spp;
-        TMPT_HIP(hipMemsetAsync(gs[0].heads, 0, head_words * 4, s.stream));
-        fn<<<pgrid, kBlk, 0, s.stream>>>(view(s), as, pc2, d_out, gs[0].ovf, spec_ctr + 16);
-        if (ch)
-            // (a radiance render, a.prog set: the chains' sums go back into the pilot's
-            // state array, from which render_persistent copies every pixel's)
-            k_resolve_chains<<<(unsigned)((ch->n + 255) / 256), 256, 0, s.stream>>>(
-                *ch, s.sbuf, a.spp, a.spp_recip, d_out, a.prog ? const_cast<float4*>(ch->cinit) : nullptr);
-        else
-            k_resolve_px<<<(unsigned)((a.slots + 63) / 64), 64, 0, s.stream>>>(s.sbuf, a.slots, a.spp, a.spp_recip,
-                                                                                d_out);
-        TMPT_HIP(hipGetLastError());
-    }
-    s.path_launches = it;
-#ifdef TMPT_DIAG
-    if (getenv("TMPT_ROWSPEC_LOG")) {
-        unsigned long long c[2] = {0, 0};
-        TMPT_HIP(hipMemcpyAsync(c, d_counters, sizeof(c), hipMemcpyDeviceToHost, s.stream));
-        unsigned long long t = 0;
-        TMPT_HIP(hipMemcpyAsync(&t, spec_ctr, sizeof(t), hipMemcpyDeviceToHost, s.stream));
-        std::vector<uint32_t> sw(rows), pm(rows);
-        for (Group& q : gs) {
-            TMPT_HIP(hipMemcpyAsync(sw.data() + q.rs.row0, q.rs.short_win, q.rs.nrows * 4, hipMemcpyDeviceToHost, s.stream));
-            TMPT_HIP(hipMemcpyAsync(pm.data() + q.rs.row0, q.rs.prev_mean, q.rs.nrows * 4, hipMemcpyDeviceToHost, s.stream));
-        }
-        TMPT_HIP(hipStreamSynchronize(s.stream));
-        double pmsum = 0.0;
-        for (uint32_t v : pm) {
-            float f;
-            memcpy(&f, &v, 4);
-            pmsum += f;
-        }
-        unsigned long long planned = 0;
-        TMPT_HIP(hipMemcpy(&planned, spec_ctr + 8, sizeof(planned), hipMemcpyDeviceToHost));
-        fprintf(stderr, "rowspec: last pixel's draws per sample, mean over rows %.2f; units planned %llu (%.1f rays each)\n",
-                rows ? pmsum / rows : 0.0, planned, planned ? (double)t / (double)planned : 0.0);
-        uint64_t swsum = 0;
-        uint32_t swmax = 0;
-        for (uint32_t v : sw) {
-            swsum += v;
-            swmax = std::max(swmax, v);
-        }
-        fprintf(stderr,
-                "rowspec: %d iterations enqueued, %d groups of %d blocks, window cap %u, %d windows, traced rays "
-                "%llu for %llu chain rays (x%.2f); short windows per row: mean %.1f max %u\n",
-                it, G, pgrid, wmax, nwin, t, c[0], c[0] ? (double)t / (double)c[0] : 0.0,
-                rows ? (double)swsum / rows : 0.0, swmax);
-    }
-#endif
-    return 0;
-}
-
-// rays: n x 6 floats (one [tmin, tmax] for all) or, ranged, n x 8 (per ray)
 // the render counters (device), their pinned host copy and the render's two
 // timing events: created once per scene, so a render call costs no allocation
 // (it matters for the small shards of a multi-GPU frame); the octree's
@@ -4292,37 +2336,6 @@ int check_report(Scene& s, const char* what)
     (void)what;
     return 0;
 #endif
-}
-
-int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
-                    float* d_hits, int32_t* d_ids)
-{
-    s.row_render = s.pixel_render = false;
-    if (ensure_counters(s)) return -1;
-    TMPT_HIP(hipMemsetAsync(s.ties, 0, 2 * sizeof(unsigned long long), s.stream));
-    TMPT_HIP(hipMemsetAsync(s.counters + kCrackCounter, 0, sizeof(unsigned long long), s.stream));
-    const bool soa = s.soa.na != nullptr;
-    // one range starting behind the origin takes the NEG slack too
-    const bool neg1 = !ranged && tmin < 0.0f;
-    auto fn = soa ? (ranged ? (any ? k_intersect<true, true, kBlk, kSL, true> : k_intersect<false, true, kBlk, kSL, true>)
-                    : neg1  ? (any ? k_intersect<true, false, kBlk, kSL, true, true>
-                                   : k_intersect<false, false, kBlk, kSL, true, true>)
-                            : (any ? k_intersect<true, false, kBlk, kSL, true> : k_intersect<false, false, kBlk, kSL, true>))
-                  : (ranged ? (any ? k_intersect<true, true, kBlk, kSL> : k_intersect<false, true, kBlk, kSL>)
-                    : neg1  ? (any ? k_intersect<true, false, kBlk, kSL, false, true>
-                                   : k_intersect<false, false, kBlk, kSL, false, true>)
-                            : (any ? k_intersect<true, false, kBlk, kSL> : k_intersect<false, false, kBlk, kSL>));
-    int grid = occupancy_grid((const void*)fn, kBlk, 0, s.device);
-    grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (n + kBlk - 1) / kBlk));
-    size_t ovf_bytes = (size_t)grid * kBlk * (kStackTotal - kSL) * sizeof(uint32_t);
-    if (ensure_ws(s, ovf_bytes)) return -1;
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), d_rays, n, tmin, tmax, d_hits, d_ids, (uint32_t*)s.ws);
-    TMPT_HIP(hipGetLastError());
-    TMPT_HIP(hipMemcpyAsync(s.counters_host + kTieCounter, s.ties, 2 * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, s.stream));
-    TMPT_HIP(hipMemcpyAsync(s.counters_host + kCrackCounter, s.counters + kCrackCounter, sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, s.stream));
-    return 0;
 }
 
 int ensure_sample_tables(Scene& s, int32_t spp, const char* what)
@@ -4515,7 +2528,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
 #ifdef TMPT_EXP_WAVETIME
     {
         std::vector<unsigned long long> w(3 * kWaveTimeMax, 0ull);
-        if (hipMemcpyFromSymbol(w.data(), HIP_SYMBOL(g_wavetime), w.size() * 8) == hipSuccess) {
+        if (wavetime_get(w.data())) {
             std::vector<double> st, ml, ex;
             unsigned long long t0 = ~0ull;
             for (int i = 0; i < kWaveTimeMax; ++i)
@@ -4536,30 +2549,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
                     st.size(), pct(st, 0), pct(st, 0.5), pct(st, 1), pct(ml, 0), pct(ml, 0.1), pct(ml, 0.5),
                     pct(ml, 0.9), pct(ml, 1), pct(ex, 0), pct(ex, 0.5), pct(ex, 0.99), pct(ex, 1));
             std::fill(w.begin(), w.end(), 0ull);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wavetime), w.data(), w.size() * 8);
-        }
-    }
-#endif
-#ifdef TMPT_EXP_CRACKSTAT
-    {
-        unsigned long long w[4] = {0, 0, 0, 0};
-        if (hipMemcpyFromSymbol(w, HIP_SYMBOL(g_crackstat), sizeof(w)) == hipSuccess && w[0]) {
-            fprintf(stderr, "crack test: %llu finished hits, first stage true %llu (%.3f %%), both stages %llu, "
-                            "t < reach %llu (%.3f %%)\n",
-                    w[0], w[1], 100.0 * w[1] / w[0], w[2], w[3], 100.0 * w[3] / w[0]);
-            const unsigned long long z[4] = {0, 0, 0, 0};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_crackstat), z, sizeof(z));
-        }
-    }
-#endif
-#ifdef TMPT_EXP_WALKSTAT
-    {
-        unsigned long long w[4] = {0, 0, 0, 0};
-        if (hipMemcpyFromSymbol(w, HIP_SYMBOL(g_walkstat), sizeof(w)) == hipSuccess && w[3]) {
-            fprintf(stderr, "octree walks %llu: nodes %.1f, triangles %.1f per walk, max nodes %llu\n", w[3],
-                    (double)w[0] / w[3], (double)w[1] / w[3], w[2]);
-            const unsigned long long z[4] = {0, 0, 0, 0};
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_walkstat), z, sizeof(z));
+            wavetime_put(w.data());
         }
     }
 #endif

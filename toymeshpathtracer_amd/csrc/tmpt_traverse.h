@@ -543,13 +543,7 @@ __device__ __forceinline__ OctHit octree_walk(const OctNode* __restrict__ nodes,
 {
     const f3 inv = ref_inverse(d);
     OctHit h{-1, tmax, 0.0f, 0.0f};
-#ifdef TMPT_EXP_WALKSTAT  // cost experiment: nodes and triangles a walk visits
-    uint32_t wn = 0, wt = 0;
-#endif
     for (int i = 0; i < n_oct;) {
-#ifdef TMPT_EXP_WALKSTAT
-        ++wn;
-#endif
         const float4 lo = nodes[i].lo, hi = nodes[i].hi;
         if (!ref_slab(o, inv, lo, hi, tmin, tmax)) {
             const int skip = __float_as_int(lo.w);
@@ -568,9 +562,6 @@ __device__ __forceinline__ OctHit octree_walk(const OctNode* __restrict__ nodes,
                 const float4 a = p[0], b = p[1], c = p[2];
                 const f3 v0 = mk(a.x, a.y, a.z), v1 = mk(a.w, b.x, b.y), v2 = mk(b.z, b.w, c.x);
                 float t, u, v;
-#ifdef TMPT_EXP_WALKSTAT
-                ++wt;
-#endif
                 if (mt_test(o, d, v0, v1 - v0, v2 - v0, tmin, tmax, t, u, v) && t < h.t) {
                     h = OctHit{id, t, u, v};
                     if (t == target) {  // first at the minimum: nothing can replace it
@@ -582,13 +573,6 @@ __device__ __forceinline__ OctHit octree_walk(const OctNode* __restrict__ nodes,
         }
         ++i;  // a leaf's skip link is the next node; an inner node descends to child 0
     }
-#ifdef TMPT_EXP_WALKSTAT
-    extern __device__ unsigned long long g_walkstat[4];
-    atomicAdd(&g_walkstat[0], (unsigned long long)wn);
-    atomicAdd(&g_walkstat[1], (unsigned long long)wt);
-    atomicMax(&g_walkstat[2], (unsigned long long)wn);
-    atomicAdd(&g_walkstat[3], 1ull);
-#endif
     return h;
 }
 
@@ -648,17 +632,6 @@ __device__ __forceinline__ bool octree_flag(const SceneView& sv, const TravRay& 
     const float span = fminf(ts.bt, sv.crack.x);
     const bool ax = fabsf(r.d.x) * span <= sv.crack.y, ay = fabsf(r.d.y) * span <= sv.crack.z,
                az = fabsf(r.d.z) * span <= sv.crack.w;
-#ifdef TMPT_EXP_CRACKSTAT  // cost experiment: how often each stage runs and fires
-    {
-        extern __device__ unsigned long long g_crackstat[4];
-        const bool s2 = (ax | ay | az) && octree_crack_planes(sv.oct->grid, r.o, r.d, ts.bt, ax, ay, az);
-        atomicAdd(&g_crackstat[0], 1ull);
-        if (ax | ay | az) atomicAdd(&g_crackstat[1], 1ull);
-        if (s2) atomicAdd(&g_crackstat[2], 1ull);
-        if (ts.bt < sv.crack.x) atomicAdd(&g_crackstat[3], 1ull);
-        return s2;
-    }
-#endif
     return (ax | ay | az) && octree_crack_planes(sv.oct->grid, r.o, r.d, ts.bt, ax, ay, az);
 }
 
