@@ -442,6 +442,35 @@ def cost(dump, tris):
 
 
 # ---------------------------------------------------------------- reference tree and encoder
+def encode_nodes(klo, khi, links):
+    """The documented node encoding: klo / khi [node, slot, axis] the children's float32 boxes
+    (an empty slot: +inf / -inf), links [node, slot] (an empty slot: the null leaf) ->
+    uint32 [node, 16].  Origin = the children's minimum, the least exponent per axis, faces
+    quantised outward in exact integers, empty slots inverted."""
+    klo, khi = np.array(klo, np.float32), np.array(khi, np.float32)  # [node, slot, axis]
+    n4 = klo.shape[0]
+    links = np.array(links, np.int64)
+    valid = np.isfinite(klo[..., 0])
+    lo, hi = klo.min(1), khi.max(1)
+    olo = f32_units(lo)
+    exp = np.frompyfunc(least_exponent, 1, 1)(f32_units(hi) - olo).astype(np.int64)
+    quant = np.left_shift(1, (exp + 149).astype(object))[:, None, :]
+    v3 = valid[..., None]
+    ql = (f32_units(np.where(v3, klo, 0)) - olo[:, None, :]) // quant
+    qh = -((olo[:, None, :] - f32_units(np.where(v3, khi, 0))) // quant)
+    ql = np.where(v3, np.clip(ql.astype(np.int64), 0, 255), 255)
+    qh = np.where(v3, np.clip(qh.astype(np.int64), 0, 255), 0)
+    nodes = np.zeros((n4, 16), np.uint32)
+    nodes[:, 0:3] = lo.view(np.uint32)
+    nodes[:, 3] = ((exp & 255) << (8 * np.arange(3))).sum(1) | (((1 << valid.sum(1)) - 1) << 24)
+    sh = 8 * np.arange(4)
+    for a in range(3):
+        nodes[:, 4 + 2 * a] = (ql[:, :, a] << sh).sum(1)
+        nodes[:, 5 + 2 * a] = (qh[:, :, a] << sh).sum(1)
+    nodes[:, 12:16] = links
+    return nodes
+
+
 def reference_dump(tris, leaf_max=2):
     """A dump (AoS form) of the median-split reference tree of the triangles: split along the
     largest extent of the box centres, sorted by centre along it, at cnt // 2, leaves of at
@@ -503,28 +532,8 @@ def reference_dump(tris, leaf_max=2):
         khi.append([c[4] for c in kids] + [np.full(3, -np.inf, np.float32)] * pad)
         links.append(row + [0x80000000 | n] * pad)
         i += 1
-    n4 = len(queue)
-    klo, khi = np.array(klo, np.float32), np.array(khi, np.float32)  # [node, slot, axis]
-    links = np.array(links, np.int64)
-    valid = np.isfinite(klo[..., 0])
-    lo, hi = klo.min(1), khi.max(1)
-    olo = f32_units(lo)
-    exp = np.frompyfunc(least_exponent, 1, 1)(f32_units(hi) - olo).astype(np.int64)
-    quant = np.left_shift(1, (exp + 149).astype(object))[:, None, :]
-    v3 = valid[..., None]
-    ql = (f32_units(np.where(v3, klo, 0)) - olo[:, None, :]) // quant
-    qh = -((olo[:, None, :] - f32_units(np.where(v3, khi, 0))) // quant)
-    ql = np.where(v3, np.clip(ql.astype(np.int64), 0, 255), 255)
-    qh = np.where(v3, np.clip(qh.astype(np.int64), 0, 255), 0)
-    nodes = np.zeros((n4, 16), np.uint32)
-    nodes[:, 0:3] = lo.view(np.uint32)
-    nodes[:, 3] = ((exp & 255) << (8 * np.arange(3))).sum(1) | (((1 << valid.sum(1)) - 1) << 24)
-    sh = 8 * np.arange(4)
-    for a in range(3):
-        nodes[:, 4 + 2 * a] = (ql[:, :, a] << sh).sum(1)
-        nodes[:, 5 + 2 * a] = (qh[:, :, a] << sh).sum(1)
-    nodes[:, 12:16] = links
-    info["n_nodes4"], info["depth4"] = n4, max(depth_of)
+    nodes = encode_nodes(klo, khi, links)
+    info["n_nodes4"], info["depth4"] = len(queue), max(depth_of)
     return {"nodes": nodes, "tris": rec, "info": info}
 
 
