@@ -288,6 +288,16 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    buffer (0 = 3/4 of free HBM); over the cap a pixel is one unit
  *   sbuf_pair        sample seeding: a unit's samples 2k and 2k+1 written back to back into
  *                    one 32-B sector of the colour buffer (1) or each on its own (0)
+ *   cam_pre          sample seeding, persistent engine at 5 waves per SIMD: the pass's camera
+ *                    samples (ray and RNG state, a function of pixel and sample there) are made
+ *                    by a pre-pass on full waves in every such render call, 32 B per sample in a
+ *                    buffer the scene keeps, and the path kernel reads them (-1 = the measured
+ *                    default: on; 0 = off; 1 = on).  Where the buffer does not fit -- over
+ *                    cam_pre_max, over half of the device memory still free, or not
+ *                    allocated -- the call runs the kernels that make their own camera samples;
+ *                    the image, the ray counts and every statistic are the same either way
+ *   cam_pre_max      cam_pre: cap in bytes on that buffer (0 = half of the free HBM alone)
+ *   cam_rays_used    read-only (tmpt_scene_get_option): 1 if the last render ran the pre-pass
  *   pilot            pixel seeding: pilot samples of the cost-ordered supply (-1 = auto, 0 = off)
  *   help, pair       pixel seeding: shadow offload to idle lanes (-1 = auto, 0, 1)
  *                    and expensive ranks per 64-rank chunk (-1 = auto, 0..63)
@@ -542,6 +552,26 @@ int tmpt_unit_sincos(int32_t device, uint32_t key0, uint32_t n, float* out);
  * hook like the one above: tests compare it with integer division.  Additive,
  * the ABI version stays. */
 int tmpt_fastdiv(uint32_t divisor, const uint32_t* x, uint64_t n, uint32_t* out, uint32_t mul_shift[2]);
+
+/* Check hook: the camera pre-pass of sample seeding (render option cam_pre) run
+ * alone, its entries copied to host memory.  Reads desc's width, height, spp,
+ * spp_begin / spp_count (the pass, as tmpt_render takes them), band_rows, shard
+ * and num_shards; seed_mode, engine and flags are not read.  out holds
+ * tmpt_tile_rows(desc) * width * count entries of 8 uint32 words, count the
+ * samples of the pass, entry (slot, sample) at slot * count + (sample -
+ * spp_begin), slot the pixel's index in the compact tile layout of tmpt_render:
+ *   [0..2] the ray's origin, [3..5] its direction (f32 bits): Camera::GetRay of
+ *          main.cpp:212-216 for that pixel, from the state sample seeding gives
+ *          the sample (the pixel's seed jumped to the sample)
+ *   [6]    the RNG state after the camera's draws (two for the jitter, two per
+ *          try of the lens disk)
+ *   [7]    flags: 1 the ray holds a NaN, else 2 it misses the reference's root
+ *          box (set only where the render would make that test: the octree
+ *          built, tie_rule visit, the lens not wholly inside the box)
+ * The scene's statistics and progressive state are left alone.  -22 for sizes
+ * outside tmpt_render's limits, -12 when the entries do not fit on the device.
+ * Additive, the ABI version stays. */
+int tmpt_camera_rays(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc, uint32_t* out);
 
 /* Check hook: the BVH a scene holds, as its kernels read it, copied to host
  * memory.  The scene's stream is synchronised first; no kernel is launched and

@@ -190,7 +190,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
-           "tmpt_scene_dump_bvh", "tmpt_radix_sort")
+           "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays")
 
 
 def _check(rc: int, what: str) -> None:
@@ -684,6 +684,25 @@ class Scene:
                         aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
                         img.ctypes.data_as(ctypes.c_void_p)), "denoise")
         return res, img
+
+    def camera_rays(self, camera: Camera, width: int, height: int, spp: int, spp_begin: int = 0,
+                    spp_count: int = 0, band_rows: int = 0, shard: int = 0, num_shards: int = 1) -> np.ndarray:
+        """The camera pre-pass of sample seeding run alone (tmpt_camera_rays; render
+        option ``cam_pre``): uint32[slots, count, 8] -- per tile pixel slot and
+        sample of the pass the ray's origin [0:3] and direction [3:6] as float32
+        bits, the RNG state after the camera's draws [6] and the flag word [7]
+        (include/tmpt.h)."""
+        # bound on first use, as tmpt_fastdiv is
+        fn = _sig("tmpt_camera_rays", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p])
+        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT, 0,
+                  spp_begin, spp_count)
+        slots = int(_tile_rows(ctypes.byref(d))) * width
+        count = spp_count if spp_count > 0 else spp - spp_begin
+        out = np.zeros((slots, max(count, 0), 8), np.uint32)
+        cam = camera._to_c()
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), out.ctypes.data_as(ctypes.c_void_p)), "camera_rays")
+        return out
 
     def dump_bvh(self, layout: str = "aos") -> dict:
         """The built BVH as the kernels read it (tmpt_scene_dump_bvh; include/tmpt.h

@@ -30,6 +30,8 @@ void camera_for_scene(tmpt_camera* cam, f3 sceneMin, f3 sceneMax, int w, int h, 
 int write_png(const char* path, const uint8_t* rgba, int w, int h);
 int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* d_out,
            uint64_t* ray_count, float4* d_sums = nullptr);
+// tmpt_render.hip: the camera pre-pass alone, its entries copied to host memory (tmpt_camera_rays)
+int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* out);
 int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
                     float* d_hits, int32_t* d_ids);
 
@@ -116,6 +118,8 @@ const OptionDef kOptions[] = {
     {"sample_tail", false, -1, 64, &Options::sample_tail, nullptr, nullptr},
     {"sbuf_max", false, 0, 1e18, nullptr, nullptr, &Options::sbuf_max},
     {"sbuf_pair", false, 0, 1, &Options::sbuf_pair, nullptr, nullptr},
+    {"cam_pre", false, -1, 1, &Options::cam_pre, nullptr, nullptr},
+    {"cam_pre_max", false, 0, 1e18, nullptr, nullptr, &Options::cam_pre_max},
     {"pilot", false, -1, 512, &Options::pilot, nullptr, nullptr},
     {"help", false, -1, 1, &Options::help, nullptr, nullptr},
     {"pair", false, -1, 63, &Options::pair, nullptr, nullptr},
@@ -442,6 +446,7 @@ int tmpt_scene_destroy(tmpt_scene* h)
     if (s.prog) (void)hipFree(s.prog);
     if (s.jt) (void)hipFree(s.jt);
     if (s.sbuf) (void)hipFree(s.sbuf);
+    if (s.cam_rays) (void)hipFree(s.cam_rays);
     if (s.redo) (void)hipFree(s.redo);
     if (s.redo_state) (void)hipFree(s.redo_state);
     if (s.jt2) (void)hipFree(s.jt2);
@@ -620,6 +625,10 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
         *value = (double)pop_key_bits(h->s.link_bits, h->s.opt.pop_key_cap);
         return 0;
     }
+    if (key && strcmp(key, "cam_rays_used") == 0) {  // read-only: the last render ran the camera pre-pass
+        *value = (double)h->s.cam_rays_used;
+        return 0;
+    }
     return options_get(h->s.opt, key, value);
     TMPT_GUARD_END
 }
@@ -779,6 +788,24 @@ int tmpt_render_aov(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_des
     }
     if (!dev_out && d_out) (void)hipFree(d_out);
     return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_camera_rays(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* out)
+{
+    TMPT_GUARD_BEGIN
+    if (!h || !cam || !d || !out) return bad("tmpt_camera_rays: null argument");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_camera_rays: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_camera_rays: invalid height");
+    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_camera_rays: invalid samplesPerPixel");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
+        return bad("tmpt_camera_rays: invalid shard");
+    if (d->spp_begin < 0 || d->spp_begin >= d->spp || d->spp_count < 0 || d->spp_count > d->spp - d->spp_begin)
+        return bad("tmpt_camera_rays: invalid spp_begin / spp_count");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    return camera_rays(s, cam, d, out);
     TMPT_GUARD_END
 }
 

@@ -334,6 +334,9 @@ struct Options {
     int sample_tail = -1;     // sample seeding: blocks per resident lane run as single samples at the end (-1 auto)
     double sbuf_max = 0.0;    // sample seeding: cap on the per-sample colour buffer, bytes (0 = 3/4 of free HBM)
     int sbuf_pair = 1;        // sample seeding: a unit's sample pairs written back to back into one 32-B sector
+    int cam_pre = -1;         // sample seeding, 5 waves: the pass's camera samples made by a pre-pass on full
+                              // waves, k_path reads them (-1 = the measured default, 0 off, 1 on where it fits)
+    double cam_pre_max = 0.0; // cam_pre: cap on the pre-pass's buffer, bytes (0 = half of the free HBM)
     int pilot = -1;           // pixel seeding: pilot-pass samples of the cost ordering (-1 auto, 0 off)
     int help = -1;            // pixel seeding: shadow offload to idle lanes (-1 auto, 0 off, 1 on)
     int pair = -1;            // pixel seeding: expensive ranks per 64-rank chunk with offload (-1 auto)
@@ -434,6 +437,11 @@ struct Scene {
     int32_t jt_spp = 0;
     float4* sbuf = nullptr;
     size_t sbuf_bytes = 0;
+    // the camera pre-pass's entries (tmpt_render.hip k_cam_rays; 32 B per sample
+    // of a pass), kept and grown like sbuf, and whether the last render ran it
+    void* cam_rays = nullptr;
+    size_t cam_bytes = 0;
+    int32_t cam_rays_used = 0;
     // deferred ties (PathCtl::redo): the redo list, its capacity in entries,
     // and the samples the last render left to the redo pass
     uint2* redo = nullptr;

@@ -64,6 +64,24 @@ __device__ __forceinline__ uint32_t rss_state(const RsStream& S, int row, uint32
     return sample_seed(S.t1, j & 127u, s);
 }
 
+// One camera sample of sample seeding, as k_cam_rays leaves it for the CAM
+// kernels (32 B, two 16-byte halves): the ray of main.cpp:212-216 and the RNG
+// state after the camera's draws -- a function of (pixel, sample) alone, so
+// the whole pass's are made before k_path starts, on full waves.  flags:
+// kCamNan the ray holds a NaN (ray_has_nan: a counted miss; k_path's query
+// set-up tests every starting ray itself, scattered ones among them, so it
+// does not read this bit); kCamRootMiss, set only under
+// RenderArgs::root_check, the ray misses the reference's root box
+// (octree_root_hit), which k_path CAM reads instead of making the test.
+// include/tmpt.h states the words (tmpt_camera_rays).
+struct alignas(16) CamRay {
+    float ox, oy, oz, dx;
+    float dy, dz;
+    uint32_t rng, flags;
+};
+static_assert(sizeof(CamRay) == 32, "camera entry: two dwordx4 accesses");
+constexpr uint32_t kCamNan = 1u, kCamRootMiss = 2u;
+
 struct PathCtl {
     uint32_t* heads;  // kSeg chunk counters, stride kCtr
     uint32_t nchunks;
@@ -142,6 +160,12 @@ struct PathCtl {
     // the block's LDS copy of the top levels -- every query starts at node 0
     // -- with no global load in them (trav_step4q2_mixed TOPONLY).  0 = off.
     uint32_t top_walk;
+    // The camera pre-pass (k_cam_rays; k_path CAM): the pass's camera samples,
+    // one CamRay per (tile pixel slot, sample of the pass) at slot * cam_count +
+    // (sample - smp_begin), as sbuf is laid out, so a unit's samples are
+    // contiguous.  Read by the CAM kernels only.
+    const CamRay* __restrict__ cam_rays;
+    uint32_t cam_count;  // samples of the pass, smp_end - smp_begin
 };
 
 // ---- k_path's variants
@@ -157,6 +181,7 @@ struct PathVariant {
     bool soa;                       // the SoA planes (layout=soa)
     int ties;                       // TIES: 0 lowest index, 2 flag for the octree, 1 flag and defer
     bool sums;                      // SUMS: the float sums beside the packed pixels
+    int cam;                        // CAM: 0 the camera block, 1 the pre-pass's entries (PathCtl::cam_rays)
 };
 
 // The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel

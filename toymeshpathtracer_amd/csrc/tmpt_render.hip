@@ -450,7 +450,7 @@ __device__ void rss_chaser(const RenderArgs& a, const RsStream& S, int wave)
 
 
 template <bool COUNT, int BLOCK, int SL, int STEPS, int SHADE_MIN, int OCC = 1, int TAIL = 0, int PROF = 0,
-          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false>
+          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false, int CAM = 0>
 __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a, PathCtl pc,
                                                 uint32_t* __restrict__ out,
                                                 uint32_t* __restrict__ ovf,
@@ -469,6 +469,13 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // pixel, as pixel mode's does; the instantiations tmpt_render launches have
     // SUMS false and no such store.
     static_assert(!SUMS || SAMP == 1, "SUMS: the sample kernel's float sums");
+    // CAM (sample seeding, 5 waves): a sample's camera ray and the RNG state
+    // after the camera's draws are the pre-pass's entry (k_cam_rays,
+    // PathCtl::cam_rays) instead of the camera block's work on the few lanes
+    // that start a sample in a round: no pixel decode, seed jump, disk
+    // rejection loop, sqrt or divide here, no jump-table prefetch state, and
+    // the Camera of RenderArgs is not read.
+    static_assert(!CAM || (SAMP == 1 && OCC >= 5 && !COUNT && !SOA && !HELP), "CAM: the 5-wave sample kernels");
     __shared__ uint32_t s_stack[SL * BLOCK];
     // SAMP 3, 4 (shadow-free speculation): no light terms, no pending next ray
     __shared__ float s_light[SAMP >= 3 ? 1 : kMaxDepth * BLOCK];
@@ -769,7 +776,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     } else if (SAMP >= 2) {
                         rng = pc.ustate[cur_unit];
                     } else if (!kFull || a.smp_begin == 0) {
-                        rng = pixel_seed((uint32_t)x, (uint32_t)tile_row_to_y_fd(a, lr), (uint32_t)a.W);
+                        // (CAM: every sample's state comes with its entry)
+                        if (!CAM) rng = pixel_seed((uint32_t)x, (uint32_t)tile_row_to_y_fd(a, lr), (uint32_t)a.W);
                         col = mk(0.0f, 0.0f, 0.0f);
                     } else {  // progressive: continue the previous pass's stream and sum
                         const float4 pv = a.prog[pix];
@@ -1060,7 +1068,21 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     pc_cl += (uint64_t)__popcll(cm);
                 }
             }
-            if (cam) {  // next camera sample of this lane's pixel (main.cpp:212-216)
+            uint32_t cflags = 0;  // CAM: the entry's flag word
+            if (CAM && cam) {  // the pre-pass's entry for (pix, smp): ray, RNG state, flags
+                // nontemporal: 4 GB per bench frame stream through once and
+                // must not evict BVH nodes from L2
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                const u32x4* e = reinterpret_cast<const u32x4*>(
+                    pc.cam_rays + ((size_t)pix * pc.cam_count + (size_t)(smp - (uint32_t)a.smp_begin)));
+                const u32x4 e0 = __builtin_nontemporal_load(e), e1 = __builtin_nontemporal_load(e + 1);
+                so = mk(__uint_as_float(e0.x), __uint_as_float(e0.y), __uint_as_float(e0.z));
+                sd = mk(__uint_as_float(e0.w), __uint_as_float(e1.x), __uint_as_float(e1.y));
+                rng = e1.z;
+                cflags = e1.w;
+                start = true;
+            }
+            if (!CAM && cam) {  // next camera sample of this lane's pixel (main.cpp:212-216)
                 const int lr = (int)fastdiv(pix, a.div_w);
                 const int x = (int)(pix - (uint32_t)lr * (uint32_t)a.W);
                 const uint32_t y = (uint32_t)tile_row_to_y_fd(a, lr);
@@ -1097,7 +1119,9 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 qany = sany;
                 if (sany) ++rays_s; else ++rays_e;
                 in_query = sv.n > 0 && !ray_has_nan(so, sd);  // NaN ray / no triangles: a counted miss
-                if (!DEFER && a.root_check && cam && in_query && !octree_root_hit(sv, so, sd, kMinT, kMaxT)) {
+                // (CAM: the pre-pass made the root box test; its answer is the entry's flag)
+                if (!DEFER && a.root_check && cam && in_query &&
+                    (CAM ? (cflags & kCamRootMiss) != 0u : !octree_root_hit(sv, so, sd, kMinT, kMaxT))) {
                     in_query = false;  // a camera ray outside the reference's root box: a counted miss
                     atomicAdd(&sv.oct->ties[1], 1ull);
                 }
@@ -1395,6 +1419,64 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     }
 }
 
+// ============================================================ the camera pre-pass
+// Sample seeding's camera samples of one pass, before k_path (CAM) starts: in
+// that seeding a sample's camera ray and the RNG state after the camera's
+// draws depend on (pixel, sample) alone, so they need not be made inside
+// k_path, where the camera block ran for ~4.5 of a wave's 64 lanes at a time
+// (DESIGN.md section 5).  One lane per (tile pixel slot, sample of [smp_begin,
+// smp_end)), entry slot * count + (sample - smp_begin), in 64 bits; the
+// statements are the camera block's own -- the same source functions under the
+// same flags, so every bit is what k_path would have made.
+// A block is 64 slots (blockIdx.x) by kCamBlockSamples samples (blockIdx.y),
+// each wave one sample of the 64 slots: the wave's four jump-table gathers
+// then fall into one sample's 4-KB table (8 lines per gather instead of 64,
+// with a wave that held one pixel's 64 samples), and the blocks in flight, x
+// fastest, share a few tables.  The entries go through LDS, so that a slot's
+// samples leave as one contiguous 128-B piece, nontemporal.
+constexpr int kCamBlockSamples = 4;
+__global__ void __launch_bounds__(64 * kCamBlockSamples) k_cam_rays(SceneView sv, RenderArgs a,
+                                                                    CamRay* __restrict__ out, uint32_t count)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t S = kCamBlockSamples;
+    __shared__ u32x4 s_e[64 * S * 2];  // [slot][sample][half]
+    const uint32_t l = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t pix0 = blockIdx.x * 64u, rel0 = blockIdx.y * S;
+    // (past the end: the last slot or sample again, not stored)
+    const uint32_t pix = min(pix0 + l, (uint32_t)a.slots - 1u);
+    const uint32_t smp = (uint32_t)a.smp_begin + min(rel0 + w, count - 1u);
+    const int lr = (int)fastdiv(pix, a.div_w);
+    const int x = (int)(pix - (uint32_t)lr * (uint32_t)a.W);
+    const uint32_t y = (uint32_t)tile_row_to_y_fd(a, lr);
+    const uint32_t ps = pixel_seed((uint32_t)x, y, (uint32_t)a.W);
+    uint32_t rng = sample_seed(a.jt, smp, ps);
+    f3 so, sd;
+    camera_sample(a.cam, (uint32_t)x, y, a.invW, a.invH, rng, so, sd);
+    uint32_t flags = 0;
+    if (ray_has_nan(so, sd)) flags = kCamNan;
+    else if (a.root_check && !octree_root_hit(sv, so, sd, kMinT, kMaxT)) flags = kCamRootMiss;
+    s_e[(l * S + w) * 2u] = (u32x4){__float_as_uint(so.x), __float_as_uint(so.y), __float_as_uint(so.z),
+                                    __float_as_uint(sd.x)};
+    s_e[(l * S + w) * 2u + 1u] = (u32x4){__float_as_uint(sd.y), __float_as_uint(sd.z), rng, flags};
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = threadIdx.x; h < 64u * S * 2u; h += 64u * S) {
+        const uint32_t sl = h / (2u * S), r = h % (2u * S);  // the slot of the block; sample and half within it
+        const uint32_t p = pix0 + sl, rel = rel0 + (r >> 1);
+        if (p < (uint32_t)a.slots && rel < count)
+            __builtin_nontemporal_store(s_e[h], reinterpret_cast<u32x4*>(out + ((size_t)p * count + rel)) + (r & 1u));
+    }
+}
+
+// the pre-pass of a pass (a.smp_begin .. a.smp_end) over the tile's slots, on the scene's stream
+static void launch_cam_rays(Scene& s, const RenderArgs& a, CamRay* out)
+{
+    const uint32_t count = (uint32_t)(a.smp_end - a.smp_begin);
+    const dim3 grid((unsigned)((a.slots + 63) / 64), (count + kCamBlockSamples - 1) / kCamBlockSamples);
+    k_cam_rays<<<grid, 64 * kCamBlockSamples, 0, s.stream>>>(view(s), a, out, count);
+}
+
 // ============================================================ k_path's variants
 // Every k_path the library instantiates, one line per kernel, by who launches
 // it ("The path kernel's variants").  A caller describes
@@ -1404,60 +1486,67 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
 namespace {
 constexpr bool F = false, T = true;
 constexpr PathVariant kPathVariants[] = {
-    // count sl        steps         shade_min  occ prof help samp soa ties sums
+    // count sl        steps         shade_min  occ prof help samp soa ties sums cam
     // ---- sample seeding (render_persistent, SAMP 1): 4 waves per SIMD ...
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F},   // no octree (or tie_rule index)
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F},   // the octree answers flagged ties in the main loop
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 1, F},   // ... or the redo phase does (deferred ties)
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, T},   // tmpt_render_radiance without the colour buffer
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, T},
-    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F},   // the visit counters (TIES 0 with the octree too)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F, 0},   // no octree (or tie_rule index)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F, 0},   // the octree answers flagged ties in the main loop
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 1, F, 0},   // ... or the redo phase does (deferred ties)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, T, 0},   // tmpt_render_radiance without the colour buffer
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, T, 0},
+    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F, 0},   // the visit counters (TIES 0 with the octree too)
     // ... layout=soa: 4 waves, never flagging or deferring
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F},
-    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, T},
-    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F},
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F, 0},
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, T, 0},
+    {T, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, T, 0, F, 0},
     // ... 5 waves per SIMD (the default; option path_waves)
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F},
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F},
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F},
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T},
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T, 0},
+    // ... and their twins that read the camera pre-pass's entries (CAM; option cam_pre)
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T, 1},
     // ---- pixel seeding (render_persistent, SAMP 0): 4 or 5 waves, with or
     // without the shadow helpers (HELP), lowest-index ties or flagged for the octree
-    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F},
-    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 2, F},
-    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 0, F},
-    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 2, F},
-    {T, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F},      // the visit counters
-    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 0, F},
-    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 2, F},
-    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 0, F},
-    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 2, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F, 0},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 2, F, 0},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 0, F, 0},
+    {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 1, 0, F, 2, F, 0},
+    {T, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F, 0},      // the visit counters
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 0, F, 0},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 0, 0, F, 2, F, 0},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 0, F, 0},
+    {F, kPathSL5, kPixSteps, kShadeMin, 5, 0, 1, 0, F, 2, F, 0},
     // ---- the row engines.  Iterated (render_rowspec, and
     // render_persistent's pixel chains): units in full (SAMP 2), shadow-free (SAMP 3)
-    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, 4, 0, 0, 2, F, 0, F},
-    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, kRsOcc3, 0, 0, 3, F, 0, F},
+    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, 4, 0, 0, 2, F, 0, F, 0},
+    {F, kPathSL, kRowIterSteps, kRowIterShadeMin, kRsOcc3, 0, 0, 3, F, 0, F, 0},
     // streaming (render_rowstream): the chain's full re-trace (SAMP 2) at 4 or
     // 5 waves, the workers (SAMP 4) at 4 waves or kRsOcc3 blocks per CU; ties
     // flagged for the octree (option row_flag_leaves) or lowest index
-    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 0, F},
-    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 2, F},
-    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 0, F},
-    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 2, F},
-    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 0, F},
-    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 2, F},
-    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 0, F},
-    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 2, F},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 0, F, 0},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 2, F, 2, F, 0},
+    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 0, F, 0},
+    {F, kPathSL5, kRowSteps, kRowShadeMin, 5, 0, 0, 2, F, 2, F, 0},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 0, F, 0},
+    {F, kPathSL, kRowSteps, kRowShadeMin, 4, 0, 0, 4, F, 2, F, 0},
+    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 0, F, 0},
+    {F, kPathSL, kRowSteps, kRowShadeMin, kRsOcc3, 0, 0, 4, F, 2, F, 0},
 #ifdef TMPT_DIAG
     // ---- the diagnostic build's wave-time profiles (TMPT_PROF = prof), one
     // block per CU: pixel seeding 1 / 2 / 3, sample seeding 1 / 2, and the
     // shading split (2) of the 5-wave sample kernel the product runs
-    {F, kPathSL, kPixSteps, kShadeMin, 1, 1, 0, 0, F, 0, F},
-    {F, kPathSL, kPixSteps, kShadeMin, 1, 2, 0, 0, F, 0, F},
-    {F, kPathSL, kPixSteps, kShadeMin, 1, 3, 0, 0, F, 0, F},
-    {F, kPathSL, kSampleSteps, kShadeMin, 1, 1, 0, 1, F, 0, F},
-    {F, kPathSL, kSampleSteps, kShadeMin, 1, 2, 0, 1, F, 0, F},
-    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 2, 0, 1, F, 0, F},
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 1, 0, 0, F, 0, F, 0},
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 2, 0, 0, F, 0, F, 0},
+    {F, kPathSL, kPixSteps, kShadeMin, 1, 3, 0, 0, F, 0, F, 0},
+    {F, kPathSL, kSampleSteps, kShadeMin, 1, 1, 0, 1, F, 0, F, 0},
+    {F, kPathSL, kSampleSteps, kShadeMin, 1, 2, 0, 1, F, 0, F, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 2, 0, 1, F, 0, F, 0},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 2, 0, 1, F, 0, F, 1},   // ... and its CAM twin
 #endif
 };
 constexpr size_t kNumPathVariants = sizeof(kPathVariants) / sizeof(kPathVariants[0]);
@@ -1466,7 +1555,7 @@ constexpr bool same_variant(const PathVariant& a, const PathVariant& b)
 {
     return a.count == b.count && a.sl == b.sl && a.steps == b.steps && a.shade_min == b.shade_min && a.occ == b.occ &&
            a.prof == b.prof && a.help == b.help && a.samp == b.samp && a.soa == b.soa && a.ties == b.ties &&
-           a.sums == b.sums;
+           a.sums == b.sums && a.cam == b.cam;
 }
 
 // line I's kernel: the table's fields in k_path's parameter order
@@ -1475,7 +1564,7 @@ constexpr PathFn variant_kernel()
 {
     constexpr PathVariant v = kPathVariants[I];
     return k_path<v.count, kBlk, v.sl, v.steps, v.shade_min, v.occ, path_tail(v.samp), v.prof, v.help, v.samp, v.soa,
-                  v.ties, v.sums>;
+                  v.ties, v.sums, v.cam>;
 }
 
 template <size_t... I>
@@ -1501,7 +1590,8 @@ int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn)
               std::to_string(v.sl) + ", steps " + std::to_string(v.steps) + ", shade_min " +
               std::to_string(v.shade_min) + ", occ " + std::to_string(v.occ) + ", prof " + std::to_string(v.prof) +
               ", help " + std::to_string(v.help) + ", samp " + std::to_string(v.samp) + ", soa " +
-              std::to_string(v.soa) + ", ties " + std::to_string(v.ties) + ", sums " + std::to_string(v.sums));
+              std::to_string(v.soa) + ", ties " + std::to_string(v.ties) + ", sums " + std::to_string(v.sums) +
+              ", cam " + std::to_string(v.cam));
     return -22;
 }
 
@@ -1782,6 +1872,35 @@ uint32_t oct_shadow_check(const Scene& s)
     return 0u;
 }
 
+// Option cam_pre's default (-1), from the same-box A/B (DESIGN.md section 5,
+// "The camera pre-pass").
+constexpr int kCamPreDefault = 1;
+
+// The scene's buffer of camera entries (k_cam_rays), grown to `need` bytes and
+// kept, as sbuf is.  False -- the caller then renders with the kernels that
+// make their own camera samples -- where the buffer is over option
+// cam_pre_max, or has to grow and does not fit in half of the device memory
+// still free (the colour buffer of the same call is allocated by then; the
+// buffer held counts as free), or cannot be allocated.
+static bool ensure_cam_rays(Scene& s, size_t need)
+{
+    if (s.opt.cam_pre_max > 0.0 && (double)need > s.opt.cam_pre_max) return false;
+    if (s.cam_bytes >= need) return true;
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
+    if (need > (fr + s.cam_bytes) / 2) return false;
+    if (s.cam_rays) (void)hipFree(s.cam_rays);
+    s.cam_rays = nullptr;
+    s.cam_bytes = 0;
+    if (hipMalloc(&s.cam_rays, need) != hipSuccess) {
+        (void)hipGetLastError();
+        s.cam_rays = nullptr;
+        return false;
+    }
+    s.cam_bytes = need;
+    return true;
+}
+
 // Persistent path engine: one launch per frame (shard).
 int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count,
                       unsigned long long* d_counters)
@@ -1827,7 +1946,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // load: 5 waves per SIMD, the shadow helpers, the tie rule (0, or with
     // `flag` 2 or 1) and the float sums.  prof forces one block per CU (OCC 1)
     // except the prof5 case, which is a 5-wave kernel.
-    auto variant = [&](bool w5, int help, int ties, bool sums) {
+    auto variant = [&](bool w5, int help, int ties, bool sums, int cam = 0) {
         PathVariant v{};
         v.count = count;
         v.sl = w5 ? kPathSL5 : kPathSL;
@@ -1840,6 +1959,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         v.soa = soa_kernel;
         v.ties = ties;
         v.sums = sums;
+        v.cam = cam;
         return v;
     };
     // Pixel seeding's instantiations too, but only with several pixels per
@@ -2105,9 +2225,26 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             set_error("tmpt_render_radiance: no instrumented kernel stores the float sums");
             return -22;
         }
+        // The camera pre-pass (option cam_pre; k_cam_rays, k_path CAM): the
+        // 5-wave sample kernels have twins that read the pass's camera samples
+        // from the scene's buffer.  Taken when the buffer fits
+        // (ensure_cam_rays); otherwise today's kernels, with the same image.
+        // Nothing is kept across calls: the camera moves every frame in real
+        // use, so the pre-pass runs in every such render, inside render_ms.
+        const int cam_pre = o.cam_pre >= 0 ? o.cam_pre : kCamPreDefault;
+        const int64_t cam_n = a.slots * (s1 - s0);
+        const bool cam_on = waves5 && !help && cam_pre != 0 && ensure_cam_rays(s, sizeof(CamRay) * (size_t)cam_n);
+        if (cam_on) {
+            const uint32_t cnt = (uint32_t)(s1 - s0);
+            pc.cam_rays = static_cast<const CamRay*>(s.cam_rays);
+            pc.cam_count = cnt;
+            launch_cam_rays(s, as, static_cast<CamRay*>(s.cam_rays));
+            TMPT_HIP(hipGetLastError());
+            s.cam_rays_used = 1;
+        }
         // the launch's kernel: flagged ties deferred (TIES 1) with the redo list,
         // answered in the main loop (TIES 2) without
-        PathVariant v_main = variant(w5, help, flag ? (redo ? 1 : 2) : 0, sums);
+        PathVariant v_main = variant(w5, help, flag ? (redo ? 1 : 2) : 0, sums, cam_on ? 1 : 0);
         PathFn fn_main;
         if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
         // the launch's grid is the launched kernel's co-resident block count
@@ -2401,6 +2538,38 @@ void reset_render_stats(Scene& s)
     s.redo_ms = 0.0;
     s.redo_rays = 0;
     s.tie_path = 0;
+    s.cam_rays_used = 0;
+}
+
+// tmpt_camera_rays: the camera pre-pass of desc's pass alone, with the
+// arguments a sample-seeded render of that desc gives it, into a buffer of its
+// own; the entries copied to `out` (host memory).  The scene's progressive
+// state, statistics and buffers are left alone.
+int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* out)
+{
+    RenderArgs a = make_args(cam, d);
+    if (int rc = ensure_sample_tables(s, a.spp, "tmpt_camera_rays")) return rc;
+    a.jt = s.jt;
+    a.root_check = camera_root_check(s, a.cam);
+    const uint32_t cnt = (uint32_t)(a.smp_end - a.smp_begin);
+    const int64_t n = a.slots * (int64_t)cnt;
+    if (n <= 0) return 0;
+    CamRay* buf = nullptr;
+    if (hipMalloc(&buf, sizeof(CamRay) * (size_t)n) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("tmpt_camera_rays: out of device memory");
+        return -12;
+    }
+    launch_cam_rays(s, a, buf);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
+    if (e == hipSuccess) e = hipMemcpy(out, buf, sizeof(CamRay) * (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) {
+        set_error(std::string("tmpt_camera_rays: ") + hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
 }
 
 // tmpt_render_radiance's last step: the float sums {r, g, b, -} the render left
