@@ -47,7 +47,9 @@ extern "C" {
                               still 9, additive: tmpt_render_radiance (the float frame of a render),
                               tmpt_denoise and tmpt_denoise_desc (the AOV-guided a-trous filter) and the
                               render option denoise_lds -- again no struct above changed;
-                              still 9, additive: the check hooks tmpt_scene_dump_bvh and tmpt_radix_sort */
+                              still 9, additive: the check hooks tmpt_scene_dump_bvh and tmpt_radix_sort;
+                              still 9, additive: tmpt_render_adaptive with tmpt_adaptive_desc and
+                              tmpt_adaptive_info (adaptive sampling) -- no struct above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -495,6 +497,79 @@ int tmpt_render_aov(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render
  * tmpt_render_aov does: it may run between two passes of a progressive render. */
 int tmpt_render_radiance(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
                          float* rgba32f_out, uint8_t* rgba8_out, uint64_t* ray_count);
+/* Adaptive sampling: per-pixel sample counts by a variance test.  In sample
+ * seeding sample s of a pixel is a function of the pixel and s alone, so a pixel
+ * may stop at any count n and then holds exactly the pixel of an n-spp frame.
+ * desc->spp is the cap S.  The arithmetic below IS the contract, as
+ * tmpt_denoise's is: every operation is float32 and rounds once (no contraction
+ * into fused multiply-adds, `/` correctly rounded), in the order written.
+ *
+ * Pass schedule: n_0 = spp_min, n_(k+1) = min(n_k + spp_step, S).  Pass 0 traces
+ * samples [0, n_0) of every pixel of the tile, pass k+1 samples [n_k, n_(k+1)) of
+ * the pixels still active after pass k.  The call ends when no pixel is active
+ * or n_k = S.  A schedule of more than 64 passes is -22.
+ * Per pixel, carried over the samples it has, in sample order, from 0.0f:
+ *   sum.k = sum.k + c_s.k  for k = r, g, b; c_s = what Trace returned for sample s
+ *   Y_s = (0.2126f * c_s.r + 0.7152f * c_s.g) + 0.0722f * c_s.b
+ *   m1 = m1 + Y_s
+ *   m2 = m2 + Y_s * Y_s
+ * The test after a pass ending at n, for a pixel active through it (tau = threshold):
+ *   fn   = (float)n
+ *   mean = m1 / fn
+ *   var  = fmaxf(0.0f, m2 / fn - mean * mean)
+ *   se2  = var / (fn - 1.0f)
+ *   lim  = (4.0f * (tau * tau)) * fmaxf(mean, 1.0f / 256.0f)
+ *   the pixel stays active iff n < S and se2 > lim
+ * To first order: the standard error of the packed value sqrtf(mean) exceeds tau,
+ * in units of full scale.  fmaxf returns the other operand for a NaN and a NaN
+ * compares false, so a pixel with a sample that is not finite stops at the count
+ * where it appears; nothing is screened, as in tmpt_denoise.  The decision reads
+ * the pixel's own samples only (no neighbourhood rule), so shard tiles assemble
+ * into the whole frame's outputs bit for bit.
+ * Result, n_p the count at which the pixel stopped:
+ *   rgba32f_out = {sum.rgb * (1.0f / (float)n_p), 1.0f}
+ *   rgba8_out   = that pixel packed as every render packs its own (main.cpp:224-233)
+ *   spp_out     = n_p
+ * -- bit for bit the pixel of tmpt_render_radiance at spp = n_p. */
+typedef struct {
+    int32_t spp_min;    /* samples every pixel gets, 2 .. desc->spp; 0 = default: min(24, desc->spp) */
+    int32_t spp_step;   /* samples a still-active pixel gets per further pass, >= 1; 0 = default: 8 */
+    float   threshold;  /* tau >= 0 and finite; < 0 = default: 0.015f; NaN / inf: -22 */
+    int32_t reserved[5];
+} tmpt_adaptive_desc;
+
+typedef struct {
+    int32_t  passes, reserved;
+    uint64_t samples;          /* sum of n_p over the tile */
+    int64_t  pass_pixels[64];  /* pixels pass k traced; 0 past the last pass */
+} tmpt_adaptive_info;
+
+/* The adaptive render of desc's shard (tmpt_adaptive_desc above; ad NULL = all
+ * defaults).  The outputs use the compact tile layout of tmpt_render:
+ * rgba32f_out tmpt_tile_rows(desc) * width * 4 floats, rgba8_out * 4 bytes,
+ * spp_out one int32 per pixel.  Any of the three and info may be NULL; at
+ * least one output is given.  TMPT_FLAG_OUT_DEVICE: all three are device
+ * pointers (rgba32f_out 16-byte aligned, rgba8_out and spp_out 4-byte);
+ * TMPT_FLAG_WAIT_STREAM as in tmpt_render.
+ * *ray_count = every HitScene call of every traced sample.  tmpt_get_stats
+ * afterwards: render_ms covers the whole call (the passes, the update and
+ * compaction kernels, the host's wait after each pass and the final kernel);
+ * extend_ms, redo_ms, extend_rays, shadow_rays, extend_launches, redo_launches,
+ * redo_samples, redo_late, redo_rays, tie_queries, root_misses and
+ * crack_queries are summed over the passes; iterations = the passes;
+ * tie_path is the first pass's.
+ * TMPT_SEED_SAMPLE and the persistent engine only: -22 for another seeding or
+ * engine, for spp_begin / spp_count other than 0, for TMPT_FLAG_COUNT_VISITS,
+ * for spp_min outside 2 .. desc->spp (after the defaults), a negative
+ * spp_step, a threshold that is NaN or infinite, a schedule of more than 64
+ * passes, and a call without any output.  The call needs the per-sample colour buffer (16 B per
+ * sample of the tile at the cap): -12 where that does not fit (render option
+ * sbuf_max), as for a progressive pass.  It leaves the scene's progressive state
+ * alone, as tmpt_render_aov does: it may run between two passes of a
+ * progressive render.  Additive, the ABI version stays. */
+int tmpt_render_adaptive(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
+                         const tmpt_adaptive_desc* ad, float* rgba32f_out, uint8_t* rgba8_out,
+                         int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count);
 /* The filter of tmpt_denoise_desc above, `levels` a-trous levels over the
  * whole frame: rgba32f_in and aov hold width * height pixels / records (the AOV
  * pass at desc->spp); rgba32f_out (may be NULL; may be rgba32f_in itself, else

@@ -16,6 +16,7 @@ reference                   here
                             light, triangle id, coverage of a sample-seeded frame's camera rays)
 (none: float frame)         :meth:`Scene.trace_radiance` (the render's linear radiance beside its bytes)
 (none: denoiser)            :meth:`Scene.denoise` (edge-avoiding a-trous filter guided by the AOV records)
+(none: adaptive sampling)   :meth:`Scene.trace_adaptive` (per-pixel sample counts by a variance test)
 ``stbi_write_png`` :342     :func:`write_png`
 ==========================  ==============================================
 
@@ -105,6 +106,16 @@ class _DenoiseDesc(ctypes.Structure):
                 ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
+class _AdaptiveDesc(ctypes.Structure):
+    _fields_ = [("spp_min", ctypes.c_int32), ("spp_step", ctypes.c_int32), ("threshold", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class _AdaptiveInfo(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("samples", ctypes.c_uint64),
+                ("pass_pixels", ctypes.c_int64 * 64)]
+
+
 class _Stats(ctypes.Structure):
     _fields_ = [("render_ms", ctypes.c_double), ("extend_ms", ctypes.c_double),
                 ("shadow_ms", ctypes.c_double), ("extend_rays", ctypes.c_uint64),
@@ -190,7 +201,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
-           "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays")
+           "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive")
 
 
 def _check(rc: int, what: str) -> None:
@@ -635,6 +646,58 @@ class Scene:
         _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), rad.ctypes.data_as(ctypes.c_void_p),
                                 img.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)), "trace_radiance")
         return rad, img, int(rays.value)
+
+    def trace_adaptive(self, camera: Camera, width: int, height: int, spp: int, spp_min: int = 0, spp_step: int = 0,
+                       threshold: float = -1.0, band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None,
+                       wait_stream="current"):
+        """Adaptive sampling of one shard (tmpt_render_adaptive; include/tmpt.h
+        states its arithmetic): sample seeding on the persistent engine, ``spp``
+        the cap.  Every pixel gets ``spp_min`` samples, a pixel still active
+        ``spp_step`` more per pass, until the standard error of its luminance
+        falls under the limit ``threshold`` sets (0 / 0 / negative: the
+        defaults).  Returns (radiance float32[tile_rows, width, 4], rgba8[tile_rows,
+        width, 4], spp_map int32[tile_rows, width], rays, info) -- a pixel that
+        stopped at n is bit for bit the pixel of :meth:`trace_radiance` at
+        spp = n; info is a dict of ``passes``, ``samples`` (the sum of the map)
+        and ``pass_pixels`` (the pixels each pass traced).  ``out``: a triple of
+        device pointers or None (float tile 16-byte aligned, rgba8 tile, int32
+        map), at least one given; the arrays returned are then None.
+        ``wait_stream`` as in :meth:`trace_image`."""
+        # bound on first use, as tmpt_fastdiv is
+        fn = _sig("tmpt_render_adaptive", ctypes.c_int,
+                  [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_AdaptiveInfo), _u64p])
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        ad = _AdaptiveDesc()
+        ad.spp_min, ad.spp_step, ad.threshold = spp_min, spp_step, threshold
+        rows = int(_tile_rows(ctypes.byref(d)))
+        rays = ctypes.c_uint64()
+        inf = _AdaptiveInfo()
+        cam = camera._to_c()
+
+        def info():
+            return {"passes": int(inf.passes), "samples": int(inf.samples),
+                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
+
+        if out is not None:
+            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
+            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.byref(ad), ptr[0], ptr[1], ptr[2],
+                      ctypes.byref(inf), ctypes.byref(rays)), "trace_adaptive")
+            return None, None, None, int(rays.value), info()
+        rad = np.zeros((rows, width, 4), np.float32)
+        img = np.zeros((rows, width, 4), np.uint8)
+        cnt = np.zeros((rows, width), np.int32)
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.byref(ad), rad.ctypes.data_as(ctypes.c_void_p),
+                  img.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf),
+                  ctypes.byref(rays)), "trace_adaptive")
+        return rad, img, cnt, int(rays.value), info()
 
     def denoise(self, radiance, aov, spp: int, levels: int = 0, normal_exp: int = -1, sigma_depth: float = 0.0,
                 sigma_direct: float = 0.0, out=None, width: Optional[int] = None, height: Optional[int] = None,

@@ -1,0 +1,302 @@
+// tmpt_adaptive.hip -- adaptive sampling (tmpt_render_adaptive): per-pixel
+// sample counts by a variance test, on sample seeding's persistent engine.
+// In that seeding sample s of a pixel is a function of the pixel and s alone,
+// so a pixel may stop at any count n and then holds exactly the pixel of an
+// n-spp frame.  The call runs passes: pass 0 traces samples [0, spp_min) of
+// every pixel of the tile (render_persistent's progressive-style pass), pass
+// k+1 samples [n_k, n_k+1) of the pixels still active (k_path LIST over the
+// device list).  After each pass k_adapt_update continues every listed
+// pixel's sums over the pass's samples, in sample order, from the colour
+// buffer, applies the test of include/tmpt.h and marks the pixels that go on;
+// k_adapt_scan and k_adapt_scatter compact them, in ascending slot order,
+// into the next pass's list.  k_adapt_final scales, packs and writes the three
+// outputs.  The host reads the next list's length (one word, with the pass's
+// counters) after every pass but the last: that length sizes the next launch.
+#include <hip/hip_runtime.h>
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "tmpt_path.h"
+
+namespace tmpt {
+
+// What a pixel carries through the call, 32 B (two 16-byte halves): the colour
+// sum, the luminance moments and the count it stopped at (the count so far
+// while it is active).
+struct alignas(16) AdaptState {
+    float r, g, b, m1;
+    float m2;
+    int32_t n;
+    uint32_t pad[2];
+};
+static_assert(sizeof(AdaptState) == 32, "adaptive state: two dwordx4 accesses");
+
+constexpr int kScanBlock = 1024;
+
+// One lane per pixel of the pass's list (list null: position i is slot i, the
+// first pass), 64 per block.  The pass's samples [s0, s1) of the block's
+// pixels are staged through LDS as k_resolve_px stages them -- 16 lanes read
+// one pixel's run of 16 samples, 256 contiguous bytes of the [pixel][sample]
+// buffer -- and every lane then continues its own pixel's sums in sample
+// order.  The statements of the sums and of the test are include/tmpt.h's, one
+// rounding each (the unit is built with contraction off and correctly rounded
+// division).  Bit t of mask[block] and cnt[block] say which of the block's
+// pixels stay active; none does when the pass is the last (s1 == cap).
+__global__ void __launch_bounds__(64) k_adapt_update(const float4* __restrict__ sbuf, const uint32_t* __restrict__ list,
+                                                     uint32_t n, int32_t spp, int32_t s0, int32_t s1, float lim4,
+                                                     AdaptState* __restrict__ state, uint64_t* __restrict__ mask,
+                                                     uint32_t* __restrict__ cnt)
+{
+    constexpr int kC = 16;               // samples per staged chunk
+    __shared__ float4 tile[64][kC + 1];  // +1: a lane's row starts on another bank
+    __shared__ uint32_t s_pix[64];
+    const uint32_t p0 = blockIdx.x * 64u;
+    const int t = (int)threadIdx.x;
+    const int np = (int)min(64u, n - p0);
+    const uint32_t pix = t < np ? (list ? list[p0 + t] : p0 + (uint32_t)t) : 0u;
+    s_pix[t] = pix;
+    AdaptState st{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, {0u, 0u}};
+    if (s0 > 0 && t < np) st = state[pix];
+    __syncthreads();
+    for (int32_t c0 = s0; c0 < s1; c0 += kC) {
+        const int nc = min(kC, s1 - c0);
+        for (int e = t; e < 64 * kC; e += 64) {
+            const int i = e / kC, j = e - i * kC;
+            if (i < np && j < nc) tile[i][j] = sbuf[(size_t)s_pix[i] * (size_t)spp + (size_t)(c0 + j)];
+        }
+        __syncthreads();
+        if (t < np)
+            for (int j = 0; j < nc; ++j) {
+                const float4 c = tile[t][j];
+                st.r = st.r + c.x;
+                st.g = st.g + c.y;
+                st.b = st.b + c.z;
+                const float y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+                st.m1 = st.m1 + y;
+                st.m2 = st.m2 + y * y;
+            }
+        __syncthreads();
+    }
+    bool active = false;
+    if (t < np) {
+        const float fn = (float)s1;
+        const float mean = st.m1 / fn;
+        const float var = fmaxf(0.0f, st.m2 / fn - mean * mean);
+        const float se2 = var / (fn - 1.0f);
+        const float lim = lim4 * fmaxf(mean, 1.0f / 256.0f);
+        active = s1 < spp && se2 > lim;  // a NaN compares false: the pixel stops
+        st.n = s1;
+        state[pix] = st;
+    }
+    const uint64_t m = wballot(active);
+    if (t == 0) {
+        mask[blockIdx.x] = m;
+        cnt[blockIdx.x] = (uint32_t)__popcll(m);
+    }
+}
+
+// Exclusive scan of the nb block counts, in place, by one block: every thread
+// sums a contiguous piece, the pieces' sums are scanned in LDS, and the piece
+// is walked again.  total[0] = the next list's length.
+__global__ void __launch_bounds__(kScanBlock) k_adapt_scan(uint32_t* __restrict__ cnt, uint32_t nb,
+                                                           uint32_t* __restrict__ total)
+{
+    __shared__ uint32_t s_sum[kScanBlock];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (nb + kScanBlock - 1u) / kScanBlock;
+    const uint32_t b0 = min(nb, t * per), b1 = min(nb, b0 + per);
+    uint32_t sum = 0;
+    for (uint32_t b = b0; b < b1; ++b) sum += cnt[b];
+    s_sum[t] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < kScanBlock; off <<= 1) {  // inclusive, Hillis-Steele
+        const uint32_t v = t >= off ? s_sum[t - off] : 0u;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[t] - sum;
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t c = cnt[b];
+        cnt[b] = run;
+        run += c;
+    }
+    if (t == kScanBlock - 1u) total[0] = s_sum[t];
+}
+
+// The next list: block b's active pixels, in lane order, from off[b] on --
+// positions keep their order, and the lists are ascending in the slot from the
+// first (the identity) on, with no dependence on which block ran first.
+__global__ void __launch_bounds__(64) k_adapt_scatter(const uint32_t* __restrict__ list, uint32_t n,
+                                                      const uint64_t* __restrict__ mask,
+                                                      const uint32_t* __restrict__ off, uint32_t* __restrict__ next)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const uint64_t m = mask[blockIdx.x];
+    if (i >= n || ((m >> threadIdx.x) & 1ull) == 0) return;
+    const uint32_t below = (uint32_t)__popcll(m & ((1ull << threadIdx.x) - 1ull));
+    next[off[blockIdx.x] + below] = list ? list[i] : i;
+}
+
+// The three outputs from the state (any of them may be null): the float pixel
+// {sum * (1.0f / (float)n), 1.0f} as k_radiance_scale forms it, the packed
+// pixel as every render packs its own, and n.
+__global__ void __launch_bounds__(256) k_adapt_final(const AdaptState* __restrict__ state, int64_t n,
+                                                     float4* __restrict__ o32, uint32_t* __restrict__ o8,
+                                                     int32_t* __restrict__ ospp)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const AdaptState st = state[i];
+    const float recip = 1.0f / (float)st.n;
+    const f3 sum = mk(st.r, st.g, st.b);
+    if (o32) {
+        const f3 col = sum * recip;
+        o32[i] = make_float4(col.x, col.y, col.z, 1.0f);
+    }
+    if (o8) o8[i] = pack_pixel(sum, recip);
+    if (ospp) ospp[i] = st.n;
+}
+
+static size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+// ad: the resolved descriptor (defaults applied, ranges checked by the
+// caller); d_f32 / d_u8 / d_spp: device tiles or null.
+int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
+                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count)
+{
+    RenderArgs a = make_args(cam, d);
+    s.row_render = false;
+    s.pixel_render = false;
+    if (int rc = ensure_sample_tables(s, a.spp, "tmpt_render_adaptive")) return rc;
+    a.jt = s.jt;
+    if (int rc = wait_caller_stream(s, d, "tmpt_render_adaptive")) return rc;
+    if (ensure_counters(s)) return -1;
+    a.root_check = camera_root_check(s, a.cam);
+    tmpt_adaptive_info inf;
+    memset(&inf, 0, sizeof(inf));
+    unsigned long long c[kRenderCounters] = {};
+    double extend_ms = 0.0, redo_ms = 0.0;
+    int64_t launches = 0, redo_samples = 0, redo_late = 0;
+    int32_t redo_launches = 0, tie_path = 0, cam_used = 0;
+    reset_render_stats(s);
+    hipEvent_t e0 = s.render_ev[0], e1 = s.render_ev[1];
+    TMPT_HIP(hipEventRecord(e0, s.stream));
+    if (a.slots > 0) {
+        const size_t slots = (size_t)a.slots, nb_max = (slots + 63) / 64;
+        const size_t o_list0 = align256(sizeof(AdaptState) * slots), o_list1 = o_list0 + align256(4 * slots);
+        const size_t o_mask = o_list1 + align256(4 * slots), o_cnt = o_mask + align256(8 * nb_max);
+        const size_t o_total = o_cnt + align256(4 * nb_max), need = o_total + 256;
+        if (s.adapt_bytes < need) {
+            if (s.adapt_buf) (void)hipFree(s.adapt_buf);
+            s.adapt_buf = nullptr;
+            s.adapt_bytes = 0;
+            if (hipMalloc(&s.adapt_buf, need) != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("tmpt_render_adaptive: out of device memory (the per-pixel state and lists)");
+                return -12;
+            }
+            s.adapt_bytes = need;
+        }
+        if (!s.adapt_host) TMPT_HIP(hipHostMalloc((void**)&s.adapt_host, 64, hipHostMallocDefault));
+        char* base = static_cast<char*>(s.adapt_buf);
+        AdaptState* state = reinterpret_cast<AdaptState*>(base);
+        uint32_t* lists[2] = {reinterpret_cast<uint32_t*>(base + o_list0), reinterpret_cast<uint32_t*>(base + o_list1)};
+        uint64_t* mask = reinterpret_cast<uint64_t*>(base + o_mask);
+        uint32_t* cnt = reinterpret_cast<uint32_t*>(base + o_cnt);
+        uint32_t* total = reinterpret_cast<uint32_t*>(base + o_total);
+        const float lim4 = 4.0f * (ad->threshold * ad->threshold);
+        const uint32_t* list = nullptr;  // pass 0: every slot
+        int64_t n_list = a.slots;
+        int32_t n0 = 0, n1 = ad->spp_min;
+        int rc = 0;
+        for (int k = 0;; ++k) {
+            RenderArgs ap = a;
+            ap.smp_begin = n0;
+            ap.smp_end = n1;
+            reset_render_stats(s);
+            TMPT_HIP(hipMemsetAsync(s.counters, 0, kRenderCounters * sizeof(unsigned long long), s.stream));
+            s.adapt_on = true;
+            s.adapt_list = list;
+            s.adapt_n = n_list;
+            rc = render_persistent(s, ap, d_u8, false, s.counters);
+            s.adapt_on = false;
+            s.adapt_list = nullptr;
+            s.adapt_n = 0;
+            if (rc) break;
+            const uint32_t n = (uint32_t)n_list, nb = (n + 63u) / 64u;
+            const bool last = n1 >= a.spp;
+            k_adapt_update<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, mask, cnt);
+            TMPT_HIP(hipGetLastError());
+            uint32_t* next = lists[k & 1];
+            if (!last) {
+                k_adapt_scan<<<1, kScanBlock, 0, s.stream>>>(cnt, nb, total);
+                TMPT_HIP(hipGetLastError());
+                k_adapt_scatter<<<nb, 64, 0, s.stream>>>(list, n, mask, cnt, next);
+                TMPT_HIP(hipGetLastError());
+                TMPT_HIP(hipMemcpyAsync(s.adapt_host, total, 4, hipMemcpyDeviceToHost, s.stream));
+            }
+            // the host waits here, once per pass: for the pass's counters and,
+            // unless the pass is the last, the next list's length
+            TMPT_HIP(hipMemcpyAsync(s.counters_host, s.counters, kRenderCounters * sizeof(unsigned long long),
+                                    hipMemcpyDeviceToHost, s.stream));
+            TMPT_HIP(hipStreamSynchronize(s.stream));
+            for (int i = 0; i < kRenderCounters; ++i) c[i] += s.counters_host[i];
+            float k1 = 0.0f;
+            (void)hipEventElapsedTime(&k1, s.path_ev[2], s.path_ev[3]);
+            extend_ms += k1;
+            if (s.redo_launches) {
+                float kr = 0.0f;
+                (void)hipEventElapsedTime(&kr, s.path_ev[0], s.path_ev[1]);
+                redo_ms += kr;
+            }
+            launches += s.path_launches;
+            redo_samples += s.redo_samples;
+            redo_late += s.redo_late;
+            redo_launches += s.redo_launches;
+            if (k == 0) tie_path = s.tie_path;
+            cam_used |= s.cam_rays_used;
+            inf.pass_pixels[k] = n_list;
+            inf.samples += (uint64_t)n_list * (uint64_t)(n1 - n0);
+            inf.passes = k + 1;
+            if (last) break;
+            n_list = (int64_t)s.adapt_host[0];
+            if (n_list == 0) break;
+            list = next;
+            n0 = n1;
+            n1 = std::min(n1 + ad->spp_step, a.spp);
+        }
+        if (rc) return rc;
+        k_adapt_final<<<(unsigned)((a.slots + 255) / 256), 256, 0, s.stream>>>(state, a.slots, d_f32, d_u8, d_spp);
+        TMPT_HIP(hipGetLastError());
+    }
+    TMPT_HIP(hipEventRecord(e1, s.stream));
+    TMPT_HIP(hipStreamSynchronize(s.stream));
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    reset_render_stats(s);
+    s.render_ms = ms;
+    s.extend_ms = extend_ms;
+    s.redo_ms = redo_ms;
+    s.redo_rays = c[kRedoRaysCounter];
+    s.redo_samples = redo_samples;
+    s.redo_late = redo_late;
+    s.redo_launches = redo_launches;
+    s.tie_path = tie_path;
+    s.cam_rays_used = cam_used;
+    s.tie_queries = c[kTieCounter];
+    s.root_misses = c[kTieCounter + 1];
+    s.crack_queries = c[kCrackCounter];
+    s.extend_rays = c[3];
+    s.shadow_rays = c[0] - c[3];
+    s.extend_launches = launches;
+    s.iterations = inf.passes;
+    if (info) *info = inf;
+    if (ray_count) *ray_count = c[0];
+    return 0;
+}
+
+}  // namespace tmpt

@@ -447,6 +447,8 @@ int tmpt_scene_destroy(tmpt_scene* h)
     if (s.jt) (void)hipFree(s.jt);
     if (s.sbuf) (void)hipFree(s.sbuf);
     if (s.cam_rays) (void)hipFree(s.cam_rays);
+    if (s.adapt_buf) (void)hipFree(s.adapt_buf);
+    if (s.adapt_host) (void)hipHostFree(s.adapt_host);
     if (s.redo) (void)hipFree(s.redo);
     if (s.redo_state) (void)hipFree(s.redo_state);
     if (s.jt2) (void)hipFree(s.jt2);
@@ -857,6 +859,82 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
         if (hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
             (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_render_radiance: readback failed"), -1);
+    }
+    cleanup();
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d,
+                         const tmpt_adaptive_desc* ad, float* rgba32f_out, uint8_t* rgba8_out, int32_t* spp_out,
+                         tmpt_adaptive_info* info, uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    if (!h || !cam || !d) return bad("tmpt_render_adaptive: null argument");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_adaptive: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_adaptive: invalid height");
+    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_adaptive: invalid samplesPerPixel");
+    if (d->seed_mode != TMPT_SEED_SAMPLE)
+        return bad("tmpt_render_adaptive: seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a sample is a "
+                   "function of pixel and sample)");
+    if (d->engine != TMPT_ENGINE_PERSISTENT) return bad("tmpt_render_adaptive: engine must be TMPT_ENGINE_PERSISTENT");
+    if (d->spp_begin != 0 || d->spp_count != 0)
+        return bad("tmpt_render_adaptive: spp_begin / spp_count must be 0 (the call makes its own passes)");
+    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_adaptive: TMPT_FLAG_COUNT_VISITS is not supported");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
+        return bad("tmpt_render_adaptive: invalid shard");
+    tmpt_adaptive_desc r;  // the defaults, in one place ("Adaptive sampling")
+    memset(&r, 0, sizeof(r));
+    if (ad) r = *ad;
+    else r.threshold = -1.0f;
+    if (r.spp_min == 0) r.spp_min = std::min(24, d->spp);
+    if (r.spp_step == 0) r.spp_step = 8;
+    if (!(r.threshold >= -3.0e38f) || !(r.threshold <= 3.0e38f))
+        return bad("tmpt_render_adaptive: threshold must be finite (negative = default)");
+    if (r.threshold < 0.0f) r.threshold = 0.015f;
+    if (r.spp_min < 2 || r.spp_min > d->spp)
+        return bad("tmpt_render_adaptive: spp_min outside 2 .. spp (0 = default)");
+    if (r.spp_step < 1) return bad("tmpt_render_adaptive: spp_step must not be negative (0 = default)");
+    if (1 + (d->spp - r.spp_min + r.spp_step - 1) / r.spp_step > 64)
+        return bad("tmpt_render_adaptive: spp_min / spp_step give a schedule of more than 64 passes");
+    if (!rgba32f_out && !rgba8_out && !spp_out)
+        return bad("tmpt_render_adaptive: no output (rgba32f_out, rgba8_out and spp_out are all null)");
+    const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev_out && ((reinterpret_cast<uintptr_t>(rgba32f_out) & 15u) != 0 ||
+                    ((reinterpret_cast<uintptr_t>(rgba8_out) | reinterpret_cast<uintptr_t>(spp_out)) & 3u) != 0))
+        return bad("tmpt_render_adaptive: device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
+                   "spp_out 4)");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width;
+    // host outputs are staged in device tiles of the library's own
+    float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
+    uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
+    int32_t* d_n = dev_out ? spp_out : nullptr;
+    void *own_f = nullptr, *own_8 = nullptr, *own_n = nullptr;
+    auto cleanup = [&]() {
+        if (own_f) (void)hipFree(own_f);
+        if (own_8) (void)hipFree(own_8);
+        if (own_n) (void)hipFree(own_n);
+    };
+    if (!dev_out && px &&
+        ((rgba32f_out && hipMalloc(&own_f, px * sizeof(float4)) != hipSuccess) ||
+         (rgba8_out && hipMalloc(&own_8, px * 4) != hipSuccess) ||
+         (spp_out && hipMalloc(&own_n, px * 4) != hipSuccess))) {
+        cleanup();
+        return bad("tmpt_render_adaptive: out of device memory");
+    }
+    if (own_f) d_f = static_cast<float4*>(own_f);
+    if (own_8) d_8 = static_cast<uint32_t*>(own_8);
+    if (own_n) d_n = static_cast<int32_t*>(own_n);
+    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count);
+    if (!rc) rc = check_report(s, "tmpt_render_adaptive");
+    if (!rc && !dev_out && px) {
+        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
+            (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (spp_out && hipMemcpy(spp_out, d_n, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = (set_error("tmpt_render_adaptive: readback failed"), -1);
     }
     cleanup();
     return rc;

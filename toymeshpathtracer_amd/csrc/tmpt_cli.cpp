@@ -1,6 +1,7 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
+//        [--adaptive TAU[,MIN[,STEP]]] [--spp-map OUT.png]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -13,6 +14,10 @@
 // PREFIX_depth.png.
 // --denoise OUT.png (one device, --seed sample): beside the usual output, the frame's float
 // radiance (tmpt_render_radiance) filtered by tmpt_denoise with the AOV records as guides.
+// --adaptive TAU[,MIN[,STEP]] (one device, --seed sample): the frame comes from tmpt_render_adaptive
+// with spp as the cap (MIN, STEP: spp_min, spp_step; left out or 0 = the defaults, a negative TAU
+// too); --spp-map OUT.png writes the samples each pixel got, n_p / spp, as grey.  With --denoise
+// the filter takes the adaptive radiance; the AOV pass stays at spp.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -122,12 +127,66 @@ static int write_denoised(const char* path, const float* tris, int32_t n, const 
     return tmpt_write_png(path, img.data(), w, h);
 }
 
+// --adaptive on `device` (its own scene, the octree built as for a frame): the adaptive render
+// into `image` (what --out writes), the spp map as grey uint8(n_p / spp * 255) and, with
+// `denoised`, the filter over the adaptive radiance guided by the AOV pass at spp.
+static int render_adaptive_frame(const float* tris, int32_t n, const float box[6], const tmpt_camera* cam, int w, int h,
+                                 int spp, int device, const tmpt_adaptive_desc* ad, std::vector<uint8_t>& image,
+                                 const char* spp_map, const char* denoised)
+{
+    tmpt_scene* scene = nullptr;
+    if (tmpt_scene_create(tris, n, device, &scene)) return 1;
+    const size_t P = (size_t)w * h;
+    std::vector<float> rad(P * 4);
+    std::vector<int32_t> cnt(P);
+    tmpt_render_desc desc;
+    memset(&desc, 0, sizeof(desc));
+    desc.width = w; desc.height = h; desc.spp = spp; desc.seed_mode = TMPT_SEED_SAMPLE;
+    desc.engine = TMPT_ENGINE_PERSISTENT;
+    tmpt_adaptive_info info;
+    tmpt_stats st;
+    uint64_t rays = 0;
+    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    if (!rc) rc = tmpt_render_adaptive(scene, cam, &desc, ad, rad.data(), image.data(), cnt.data(), &info, &rays);
+    if (!rc) rc = tmpt_get_stats(scene, &st);
+    if (!rc) {
+        printf("Rendered scene at %ix%i, up to %ispp, adaptively in %.3f s (%d passes)\n", w, h, spp,
+               st.render_ms / 1000.0, info.passes);
+        printf("- %llu of %llu samples traced (%.1f%%), %.1f K Rays, %.1f K Rays/s\n",
+               (unsigned long long)info.samples, (unsigned long long)P * spp, 100.0 * info.samples / ((double)P * spp),
+               rays / 1000.0, rays / 1000.0 / (st.render_ms / 1000.0));
+        if (spp_map) {
+            std::vector<uint8_t> grey(P * 4, 255);
+            for (size_t i = 0; i < P; ++i)
+                for (int c = 0; c < 3; ++c) grey[4 * i + c] = (uint8_t)((float)cnt[i] / (float)spp * 255.0f);
+            rc = tmpt_write_png(spp_map, grey.data(), w, h);
+        }
+    }
+    if (!rc && denoised) {
+        std::vector<tmpt_aov_pixel> rec(P);
+        std::vector<uint8_t> img(P * 4);
+        tmpt_denoise_desc dn;
+        memset(&dn, 0, sizeof(dn));
+        dn.width = w; dn.height = h; dn.spp = spp; dn.normal_exp = -1;
+        uint64_t aov_rays = 0;
+        rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &aov_rays);
+        if (!rc) rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
+        if (!rc) rc = tmpt_get_stats(scene, &st);
+        if (!rc) {
+            printf("Denoised adaptive frame: %.1f K AOV Rays, filter %.3f ms\n", aov_rays / 1000.0, st.render_ms);
+            rc = tmpt_write_png(denoised, img.data(), w, h);
+        }
+    }
+    if (tmpt_scene_destroy(scene) && !rc) rc = 1;
+    return rc;
+}
+
 int main(int argc, const char** argv)
 {
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
-               "[--denoise file.png]\n");
+               "[--denoise file.png] [--adaptive tau[,min[,step]]] [--spp-map file.png]\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -141,6 +200,10 @@ int main(int argc, const char** argv)
     const char* out = "output.png";
     const char* aov = nullptr;
     const char* denoised = nullptr;
+    const char* spp_map = nullptr;
+    bool adaptive = false;
+    tmpt_adaptive_desc ad;
+    memset(&ad, 0, sizeof(ad));
     for (int i = 5; i < argc; ++i) {
         if (!strcmp(argv[i], "--seed") && i + 1 < argc) {
             ++i;
@@ -157,6 +220,19 @@ int main(int argc, const char** argv)
         else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
         else if (!strcmp(argv[i], "--denoise") && i + 1 < argc) denoised = argv[++i];
+        else if (!strcmp(argv[i], "--spp-map") && i + 1 < argc) spp_map = argv[++i];
+        else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) {
+            int mn = 0, stp = 0;
+            float tau = -1.0f;
+            if (sscanf(argv[++i], "%f,%d,%d", &tau, &mn, &stp) < 1) {
+                printf("ERROR: invalid --adaptive argument '%s'\n", argv[i]);
+                return 1;
+            }
+            adaptive = true;
+            ad.threshold = tau;
+            ad.spp_min = mn;
+            ad.spp_step = stp;
+        }
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -173,6 +249,11 @@ int main(int argc, const char** argv)
         printf("ERROR: --denoise needs --seed sample (the AOV records are a sample-seeded frame's)\n");
         return 1;
     }
+    if (adaptive && (gpus > 1 || seed != TMPT_SEED_SAMPLE || engine != TMPT_ENGINE_PERSISTENT)) {
+        printf("ERROR: --adaptive needs --seed sample, the persistent engine and one device (--gpus 1)\n");
+        return 1;
+    }
+    if (spp_map && !adaptive) { printf("ERROR: --spp-map needs --adaptive\n"); return 1; }
     int ndev = tmpt_device_count();
     if (device + gpus > ndev) {
         printf("ERROR: %d GPU(s) requested from device %d, %d present\n", gpus, device, ndev);
@@ -194,13 +275,21 @@ int main(int argc, const char** argv)
     // BuildOctree(sceneMin - extra, sceneMax + extra), main.cpp:296-297, 312
     float box[6];
     tmpt_octree_bounds(bmin, bmax, box);
-    if (tmpt_render_multi(tris, n, box, &cam, &desc, devs.data(), gpus, image.data(), &total, &dt)) {
-        printf("ERROR: %s\n", tmpt_last_error());
-        return 1;
+    if (adaptive) {  // the frame, the spp map and the denoised frame from one adaptive call
+        if (render_adaptive_frame(tris, n, box, &cam, w, h, spp, device, &ad, image, spp_map, denoised)) {
+            printf("ERROR: %s\n", tmpt_last_error());
+            return 1;
+        }
+        denoised = nullptr;
+    } else {
+        if (tmpt_render_multi(tris, n, box, &cam, &desc, devs.data(), gpus, image.data(), &total, &dt)) {
+            printf("ERROR: %s\n", tmpt_last_error());
+            return 1;
+        }
+        printf("Initialized scene '%s' (%i tris) in %.3fs\n", obj, n, now_s() - t0 - dt);
+        printf("Rendered scene at %ix%i,%ispp in %.3f s\n", w, h, spp, dt);
+        printf("- %.1f K Rays, %.1f K Rays/s\n", total / 1000.0, total / 1000.0 / dt);
     }
-    printf("Initialized scene '%s' (%i tris) in %.3fs\n", obj, n, now_s() - t0 - dt);
-    printf("Rendered scene at %ix%i,%ispp in %.3f s\n", w, h, spp, dt);
-    printf("- %.1f K Rays, %.1f K Rays/s\n", total / 1000.0, total / 1000.0 / dt);
     if (tmpt_write_png(out, image.data(), w, h)) { printf("ERROR: %s\n", tmpt_last_error()); return 1; }
     if (aov && write_aovs(aov, tris, n, box, &cam, w, h, spp, device)) {
         printf("ERROR: %s\n", tmpt_last_error());

@@ -472,6 +472,18 @@ struct Scene {
     size_t rss_bytes = 0;
     uint32_t* rss_tab = nullptr;
     uint32_t* rss_host = nullptr;
+    // adaptive sampling (tmpt_adaptive.hip render_adaptive): set around each of
+    // its passes for render_persistent -- adapt_on: the pass keeps its samples
+    // in the colour buffer and resolves nothing; adapt_list / adapt_n: the
+    // pixels of a pass after the first (device list of tile slots, ascending)
+    // -- and the call's buffers (per-pixel state, the two lists, the block
+    // masks and counts), grown like sbuf, with the pinned next-list length
+    bool adapt_on = false;
+    const uint32_t* adapt_list = nullptr;
+    int64_t adapt_n = 0;
+    void* adapt_buf = nullptr;
+    size_t adapt_bytes = 0;
+    uint32_t* adapt_host = nullptr;
     int path_launches = 1;  // k_path launches of the last persistent render (pilot ordering: 2)
     hipEvent_t path_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the pilot / final k_path
     // statistics of the last render

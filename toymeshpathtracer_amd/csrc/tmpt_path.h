@@ -97,7 +97,13 @@ struct PathCtl {
     uint32_t* claim;  // nchunks words, zeroed per launch
     uint32_t nsimd, wps;
     int64_t P;
-    const uint32_t* __restrict__ order;  // rank -> pixel, or null
+    // rank -> pixel, or null (pixel seeding's cost order).  Sample seeding, a
+    // pass over a list of pixels (k_path LIST; tmpt_render_adaptive's later
+    // passes): the units are (list position, block) -- P counts them by the
+    // list's length -- and the quotient of the unit decode indexes this list of
+    // tile pixel slots; everything after the decode works on the pixel.  No
+    // other sample kernel reads it.
+    const uint32_t* __restrict__ order;
     uint32_t* __restrict__ cost_out;     // per-pixel traversal steps of this call, or null
     // dynamic issue priority (longest remaining first): each shading round the
     // wave estimates its lanes' remaining traversal steps (steps so far per
@@ -182,6 +188,7 @@ struct PathVariant {
     int ties;                       // TIES: 0 lowest index, 2 flag for the octree, 1 flag and defer
     bool sums;                      // SUMS: the float sums beside the packed pixels
     int cam;                        // CAM: 0 the camera block, 1 the pre-pass's entries (PathCtl::cam_rays)
+    bool list;                      // LIST: the unit decode's pixel is an index into PathCtl::order
 };
 
 // The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel

@@ -159,6 +159,16 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
 int render_aov(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt_aov_pixel* d_out,
                uint64_t* ray_count);
 
+// tmpt_render.hip: the persistent path engine, one pass (render() calls it for
+// a render, render_adaptive for each of its passes: Scene::adapt_on / adapt_list)
+int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count, unsigned long long* d_counters);
+
+// tmpt_adaptive.hip: adaptive sampling (tmpt_render_adaptive) of one shard; ad
+// holds the resolved spp_min, spp_step and threshold (checked by the caller),
+// the three tiles are device pointers or null
+int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
+                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count);
+
 // tmpt_denoise.hip: the a-trous filter (tmpt_denoise) over a whole frame, every
 // pointer on the device; d (checked by the caller) holds the resolved levels,
 // normal_exp and sigmas.  d_out32 or d_out8 may be null; d_out32 may be d_in.

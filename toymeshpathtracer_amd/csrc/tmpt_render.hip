@@ -450,7 +450,8 @@ __device__ void rss_chaser(const RenderArgs& a, const RsStream& S, int wave)
 
 
 template <bool COUNT, int BLOCK, int SL, int STEPS, int SHADE_MIN, int OCC = 1, int TAIL = 0, int PROF = 0,
-          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false, int CAM = 0>
+          int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false, int CAM = 0,
+          bool LIST = false>
 __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a, PathCtl pc,
                                                 uint32_t* __restrict__ out,
                                                 uint32_t* __restrict__ ovf,
@@ -476,6 +477,13 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // rejection loop, sqrt or divide here, no jump-table prefetch state, and
     // the Camera of RenderArgs is not read.
     static_assert(!CAM || (SAMP == 1 && OCC >= 5 && !COUNT && !SOA && !HELP), "CAM: the 5-wave sample kernels");
+    // LIST (sample seeding, a pass of tmpt_render_adaptive over the pixels still
+    // active): the unit decode's pixel is a position in PathCtl::order, and one
+    // load turns it into the tile pixel slot (as pixel seeding's rank and the
+    // row engines' pc.upix do); the colour buffer, the seed and the redo entries then
+    // go by the pixel as everywhere else -- the pre-pass's entries too (CAM:
+    // k_cam_rays_list leaves a listed pixel's where its slot's always are).
+    static_assert(!LIST || (SAMP == 1 && !SUMS && !COUNT && !SOA && !HELP), "LIST: the plain sample kernels");
     __shared__ uint32_t s_stack[SL * BLOCK];
     // SAMP 3, 4 (shadow-free speculation): no light terms, no pending next ray
     __shared__ float s_light[SAMP >= 3 ? 1 : kMaxDepth * BLOCK];
@@ -767,6 +775,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     } else {
                         pix = (kFull && pc.order) ? pc.order[res + k] : res + k;
                     }
+                    if (LIST) pix = pc.order[pix];  // list position -> tile pixel slot
                     psteps = 0;
                     has_pix = true;
                     const int lr = (int)fastdiv(pix, a.div_w);
@@ -1469,12 +1478,62 @@ __global__ void __launch_bounds__(64 * kCamBlockSamples) k_cam_rays(SceneView sv
     }
 }
 
-// the pre-pass of a pass (a.smp_begin .. a.smp_end) over the tile's slots, on the scene's stream
-static void launch_cam_rays(Scene& s, const RenderArgs& a, CamRay* out)
+// The same over a list of pixels (a pass of tmpt_render_adaptive over the
+// pixels still active), k_cam_rays's statements one for one: the block's 64
+// "slots" are 64 positions of the list, and position i's samples are the
+// entries of the tile pixel slot list[i] -- the buffer stays indexed by slot,
+// so k_path (CAM, LIST) reads a pixel's entries where every CAM kernel does;
+// the slots not listed are neither written nor read.  A kernel of its own, so
+// that k_cam_rays stays the code it was.
+__global__ void __launch_bounds__(64 * kCamBlockSamples) k_cam_rays_list(SceneView sv, RenderArgs a,
+                                                                         CamRay* __restrict__ out, uint32_t count,
+                                                                         const uint32_t* __restrict__ list,
+                                                                         uint32_t n_list)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t S = kCamBlockSamples;
+    __shared__ u32x4 s_e[64 * S * 2];  // [slot][sample][half]
+    const uint32_t l = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t pix0 = blockIdx.x * 64u, rel0 = blockIdx.y * S;
+    // (past the end: the last position or sample again, not stored)
+    const uint32_t pix = list[min(pix0 + l, n_list - 1u)];
+    const uint32_t smp = (uint32_t)a.smp_begin + min(rel0 + w, count - 1u);
+    const int lr = (int)fastdiv(pix, a.div_w);
+    const int x = (int)(pix - (uint32_t)lr * (uint32_t)a.W);
+    const uint32_t y = (uint32_t)tile_row_to_y_fd(a, lr);
+    const uint32_t ps = pixel_seed((uint32_t)x, y, (uint32_t)a.W);
+    uint32_t rng = sample_seed(a.jt, smp, ps);
+    f3 so, sd;
+    camera_sample(a.cam, (uint32_t)x, y, a.invW, a.invH, rng, so, sd);
+    uint32_t flags = 0;
+    if (ray_has_nan(so, sd)) flags = kCamNan;
+    else if (a.root_check && !octree_root_hit(sv, so, sd, kMinT, kMaxT)) flags = kCamRootMiss;
+    s_e[(l * S + w) * 2u] = (u32x4){__float_as_uint(so.x), __float_as_uint(so.y), __float_as_uint(so.z),
+                                    __float_as_uint(sd.x)};
+    s_e[(l * S + w) * 2u + 1u] = (u32x4){__float_as_uint(sd.y), __float_as_uint(sd.z), rng, flags};
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = threadIdx.x; h < 64u * S * 2u; h += 64u * S) {
+        const uint32_t sl = h / (2u * S), r = h % (2u * S);  // the position of the block; sample and half within it
+        const uint32_t p = pix0 + sl, rel = rel0 + (r >> 1);
+        if (p < n_list && rel < count)
+            __builtin_nontemporal_store(s_e[h],
+                                        reinterpret_cast<u32x4*>(out + ((size_t)list[p] * count + rel)) + (r & 1u));
+    }
+}
+
+// the pre-pass of a pass (a.smp_begin .. a.smp_end) over the tile's slots, or
+// over the n_list slots of `list`, on the scene's stream
+static void launch_cam_rays(Scene& s, const RenderArgs& a, CamRay* out, const uint32_t* list = nullptr,
+                            int64_t n_list = 0)
 {
     const uint32_t count = (uint32_t)(a.smp_end - a.smp_begin);
-    const dim3 grid((unsigned)((a.slots + 63) / 64), (count + kCamBlockSamples - 1) / kCamBlockSamples);
-    k_cam_rays<<<grid, 64 * kCamBlockSamples, 0, s.stream>>>(view(s), a, out, count);
+    const int64_t n = list ? n_list : a.slots;
+    const dim3 grid((unsigned)((n + 63) / 64), (count + kCamBlockSamples - 1) / kCamBlockSamples);
+    if (list)
+        k_cam_rays_list<<<grid, 64 * kCamBlockSamples, 0, s.stream>>>(view(s), a, out, count, list, (uint32_t)n_list);
+    else
+        k_cam_rays<<<grid, 64 * kCamBlockSamples, 0, s.stream>>>(view(s), a, out, count);
 }
 
 // ============================================================ k_path's variants
@@ -1486,7 +1545,7 @@ static void launch_cam_rays(Scene& s, const RenderArgs& a, CamRay* out)
 namespace {
 constexpr bool F = false, T = true;
 constexpr PathVariant kPathVariants[] = {
-    // count sl        steps         shade_min  occ prof help samp soa ties sums cam
+    // count sl        steps         shade_min  occ prof help samp soa ties sums cam list
     // ---- sample seeding (render_persistent, SAMP 1): 4 waves per SIMD ...
     {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F, 0},   // no octree (or tie_rule index)
     {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F, 0},   // the octree answers flagged ties in the main loop
@@ -1510,6 +1569,18 @@ constexpr PathVariant kPathVariants[] = {
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T, 1},
+    // ... and the passes over a list of pixels (LIST; tmpt_render_adaptive's
+    // passes after the first): 4 or 5 waves, the three tie modes, at 5 waves
+    // with the CAM twins; they read the AoS records (layout=soa too)
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F, 0, T},
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F, 0, T},
+    {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 1, F, 0, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 0, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 0, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 0, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 1, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 1, T},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1, T},
     // ---- pixel seeding (render_persistent, SAMP 0): 4 or 5 waves, with or
     // without the shadow helpers (HELP), lowest-index ties or flagged for the octree
     {F, kPathSL, kPixSteps, kShadeMin, 4, 0, 0, 0, F, 0, F, 0},
@@ -1555,7 +1626,7 @@ constexpr bool same_variant(const PathVariant& a, const PathVariant& b)
 {
     return a.count == b.count && a.sl == b.sl && a.steps == b.steps && a.shade_min == b.shade_min && a.occ == b.occ &&
            a.prof == b.prof && a.help == b.help && a.samp == b.samp && a.soa == b.soa && a.ties == b.ties &&
-           a.sums == b.sums && a.cam == b.cam;
+           a.sums == b.sums && a.cam == b.cam && a.list == b.list;
 }
 
 // line I's kernel: the table's fields in k_path's parameter order
@@ -1564,7 +1635,7 @@ constexpr PathFn variant_kernel()
 {
     constexpr PathVariant v = kPathVariants[I];
     return k_path<v.count, kBlk, v.sl, v.steps, v.shade_min, v.occ, path_tail(v.samp), v.prof, v.help, v.samp, v.soa,
-                  v.ties, v.sums, v.cam>;
+                  v.ties, v.sums, v.cam, v.list>;
 }
 
 template <size_t... I>
@@ -1591,7 +1662,7 @@ int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn)
               std::to_string(v.shade_min) + ", occ " + std::to_string(v.occ) + ", prof " + std::to_string(v.prof) +
               ", help " + std::to_string(v.help) + ", samp " + std::to_string(v.samp) + ", soa " +
               std::to_string(v.soa) + ", ties " + std::to_string(v.ties) + ", sums " + std::to_string(v.sums) +
-              ", cam " + std::to_string(v.cam));
+              ", cam " + std::to_string(v.cam) + ", list " + std::to_string(v.list));
     return -22;
 }
 
@@ -1928,7 +1999,14 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // layout=soa: the sample kernel reads the SoA planes (the A/B of DESIGN.md
     // section 3; the other engines keep the AoS records, and so do the
     // profiling kernels)
-    const bool soa = s.soa.na != nullptr;
+    // A pass of tmpt_render_adaptive (Scene::adapt_on) over the pixels still
+    // active (Scene::adapt_list; its first pass has none and is planned as a
+    // progressive pass over every slot): the units, the block size, the tail
+    // and the deferral rule go by the list's length, not by a.slots; the LIST
+    // kernels read the AoS records.
+    const bool list = s.adapt_list != nullptr;
+    const int64_t npix = list ? s.adapt_n : a.slots;  // pixels the supply hands out
+    const bool soa = s.soa.na != nullptr && !list;
     const bool soa_kernel = jt && soa && !prof;
     // TMPT_PROF=2 in sample seeding: the shading split of the 5-wave kernel the
     // product runs (its LDS layout and 96 VGPRs), unless path_waves = 4
@@ -1960,6 +2038,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         v.ties = ties;
         v.sums = sums;
         v.cam = cam;
+        v.list = list;
         return v;
     };
     // Pixel seeding's instantiations too, but only with several pixels per
@@ -2007,7 +2086,9 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // the blocks keep their alignment -- and every sample's colour goes to the
     // colour buffer; k_resolve_px adds the pass's samples, in order, to the sum
     // the previous pass left (main.cpp:218 summed across the passes).
-    const bool pass = a.jt && (a.smp_begin > 0 || a.smp_end < a.spp);
+    // (every pass of tmpt_render_adaptive is one, its last too: the update
+    // kernel reads the samples from the colour buffer)
+    const bool pass = a.jt && (a.smp_begin > 0 || a.smp_end < a.spp || s.adapt_on);
     const int64_t s0 = a.smp_begin, s1 = a.smp_end;
     if (a.jt) {
         // (15 units per 4-wave lane; with 5 waves per SIMD a quarter more lanes
@@ -2017,15 +2098,15 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         const int64_t lanes0 = (int64_t)grid * kBlk;
         blk = 1u;
         while ((int64_t)blk * 2 <= 8 && blk * 2u <= (uint32_t)(s1 - s0) &&
-               a.slots * ((s1 - s0 + blk * 2 - 1) / (blk * 2)) >= kUnitsPerLane * lanes0)
+               npix * ((s1 - s0 + blk * 2 - 1) / (blk * 2)) >= kUnitsPerLane * lanes0)
             blk *= 2u;
         if (o.sample_block > 0) blk = (uint32_t)o.sample_block;
-        while (a.slots * ((s1 - s0 + blk - 1) / blk) >= (1ll << 31)) blk *= 2u;  // 32-bit unit ids
+        while (npix * ((s1 - s0 + blk - 1) / blk) >= (1ll << 31)) blk *= 2u;  // 32-bit unit ids
         while (s0 % blk) blk /= 2u;  // a pass's first sample starts a block
         // the alignment can undo the 32-bit guard above (e.g. 4K x 1024 spp
         // from spp_begin 2: blocks of 2, ~4.2 G units): the unit ids, res and
         // nchunks are uint32, so such a pass is refused, not wrapped
-        if (a.slots * ((s1 - s0 + blk - 1) / blk) >= (1ll << 31)) {
+        if (npix * ((s1 - s0 + blk - 1) / blk) >= (1ll << 31)) {
             set_error("tmpt_render: this progressive pass (samples " + std::to_string(s0) + ".." +
                       std::to_string(s1) + " of " + std::to_string(a.slots) +
                       " pixels) needs more than 2^31 sample units at the block size its first sample allows (" +
@@ -2048,8 +2129,11 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             if (o.sbuf_max > 0.0) budget = std::min(budget, (size_t)o.sbuf_max);
             if (need > budget) {
                 if (pass) {
-                    set_error("tmpt_render: progressive passes in sample seeding need the per-sample colour buffer (" +
-                              std::to_string(need >> 20) + " MiB), which does not fit: render the frame in one call");
+                    set_error(s.adapt_on
+                                  ? "tmpt_render_adaptive: the per-sample colour buffer (" + std::to_string(need >> 20) +
+                                        " MiB) does not fit (render option sbuf_max, or 3/4 of the free device memory)"
+                                  : "tmpt_render: progressive passes in sample seeding need the per-sample colour buffer (" +
+                                        std::to_string(need >> 20) + " MiB), which does not fit: render the frame in one call");
                     return -12;
                 }
                 while (blk < (uint32_t)a.spp) blk *= 2u;
@@ -2057,7 +2141,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             }
         }
     }
-    int64_t P = a.slots * (int64_t)nblk;  // units the supply hands out
+    int64_t P = npix * (int64_t)nblk;  // units the supply hands out
     // Sample seeding's tail (option sample_tail): the last sample_tail blocks
     // per resident lane are handed out as single samples, so a lane's last
     // unit is one sample, not a block of blk, and the waves leave their main
@@ -2075,7 +2159,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // Auto (-1): a quarter of a lane's samples, at most 64, in blocks.
     int64_t tail_blocks = o.sample_tail;
     if (tail_blocks < 0) {
-        const int64_t spl = a.slots * (s1 - s0) / std::max<int64_t>(1, (int64_t)grid * kBlk);  // samples per lane
+        const int64_t spl = npix * (s1 - s0) / std::max<int64_t>(1, (int64_t)grid * kBlk);  // samples per lane
         const int64_t b = std::max<uint32_t>(1u, blk);
         tail_blocks = std::max<int64_t>(1, (std::min<int64_t>(64, spl / 4) + b - 1) / b);
     }
@@ -2145,6 +2229,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     pc.div_blk = fastdiv_make(blk);
     pc.blk0 = blk0;
     pc.ua = ua;
+    if (list) pc.order = s.adapt_list;  // (k_path LIST; sample seeding has no cost order)
     RenderArgs as = a;  // sample seeding: a lane's run of samples is its block
     if (a.jt) {
         as.bmask = nblk > 1 ? blk - 1u : 2047u;
@@ -2200,7 +2285,8 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // (profiles/r06_experiments/occ5/ab_low_rules.log)
         const bool defer = jt && !count && !prof && !soa && pc.sbuf && a.root_check == 0 && o.tie_defer != 0 &&
                            !oct_shadow &&
-                           (o.tie_defer > 0 || a.slots * (int64_t)a.spp >= (waves5 ? 48 : 192) * lanes);
+                           (o.tie_defer > 0 ||
+                            (list ? npix * (s1 - s0) : a.slots * (int64_t)a.spp) >= (waves5 ? 48 : 192) * lanes);
         bool redo = defer && oct;
         if (redo && o.redo_cap > 0 && s.redo_cap != (uint32_t)o.redo_cap) free_redo(s);  // the test hook's size
         if (redo && s.redo_cap == 0) {
@@ -2233,12 +2319,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // use, so the pre-pass runs in every such render, inside render_ms.
         const int cam_pre = o.cam_pre >= 0 ? o.cam_pre : kCamPreDefault;
         const int64_t cam_n = a.slots * (s1 - s0);
+        // (a list pass: the entries of the listed pixels only, at their slots' places)
         const bool cam_on = waves5 && !help && cam_pre != 0 && ensure_cam_rays(s, sizeof(CamRay) * (size_t)cam_n);
         if (cam_on) {
             const uint32_t cnt = (uint32_t)(s1 - s0);
             pc.cam_rays = static_cast<const CamRay*>(s.cam_rays);
             pc.cam_count = cnt;
-            launch_cam_rays(s, as, static_cast<CamRay*>(s.cam_rays));
+            launch_cam_rays(s, as, static_cast<CamRay*>(s.cam_rays), s.adapt_list, s.adapt_n);
             TMPT_HIP(hipGetLastError());
             s.cam_rays_used = 1;
         }
@@ -2302,7 +2389,8 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             }
             break;
         }
-        if (pc.sbuf) {
+        // (tmpt_render_adaptive sums the pass's samples itself, k_adapt_update)
+        if (pc.sbuf && !s.adapt_on) {
             // (a.prog: a progressive pass's carried sums, or tmpt_render_radiance's
             // float sums of a whole render; null for a plain tmpt_render)
             k_resolve_px<<<(unsigned)((a.slots + 63) / 64), 64, 0, s.stream>>>(
