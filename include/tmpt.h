@@ -300,6 +300,22 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    the image, the ray counts and every statistic are the same either way
  *   cam_pre_max      cam_pre: cap in bytes on that buffer (0 = half of the free HBM alone)
  *   cam_rays_used    read-only (tmpt_scene_get_option): 1 if the last render ran the pre-pass
+ *   shadow_split     sample seeding, where the pre-pass runs (cam_pre), a plain tmpt_render: the
+ *                    path kernel queues every shadow query (16 B) instead of tracing it and
+ *                    leaves a record per sample (64 B); a second kernel answers the queue, a
+ *                    third runs the samples' backward recurrences and packs the pixels
+ *                    (1 = the default, 0 = the fused kernel).  The fused kernel also runs where
+ *                    a shadow answer can need the octree (a triangle flat on one of its planes),
+ *                    in progressive and adaptive passes and tmpt_render_radiance, and where not
+ *                    even one sample of every pixel fits; the image, the ray counts and every
+ *                    statistic but the kernel times are the same either way (tmpt_stats:
+ *                    extend_ms the path kernel's, shadow_ms and shadow_launches the queue kernel's)
+ *   shadow_split_max shadow_split: cap in bytes on its queue and records, which are sized for
+ *                    the worst case of 10 queries per sample (0 = half of the free HBM alone);
+ *                    a render whose samples do not fit runs in several passes of samples
+ *   shadow_split_pass  shadow_split: at most this many samples of every pixel per pass (0 = what fits)
+ *   shadow_split_used  read-only: the passes of the last render that ran the split (0: fused)
+ *   shadow_split_resolve_ms  read-only: the third kernel's time in the last render
  *   pilot            pixel seeding: pilot samples of the cost-ordered supply (-1 = auto, 0 = off)
  *   help, pair       pixel seeding: shadow offload to idle lanes (-1 = auto, 0, 1)
  *                    and expensive ranks per 64-rank chunk (-1 = auto, 0..63)

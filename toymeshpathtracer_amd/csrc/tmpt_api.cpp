@@ -120,6 +120,9 @@ const OptionDef kOptions[] = {
     {"sbuf_pair", false, 0, 1, &Options::sbuf_pair, nullptr, nullptr},
     {"cam_pre", false, -1, 1, &Options::cam_pre, nullptr, nullptr},
     {"cam_pre_max", false, 0, 1e18, nullptr, nullptr, &Options::cam_pre_max},
+    {"shadow_split", false, 0, 1, &Options::shadow_split, nullptr, nullptr},
+    {"shadow_split_max", false, 0, 1e18, nullptr, nullptr, &Options::shadow_split_max},
+    {"shadow_split_pass", false, 0, 1024, &Options::shadow_split_pass, nullptr, nullptr},
     {"pilot", false, -1, 512, &Options::pilot, nullptr, nullptr},
     {"help", false, -1, 1, &Options::help, nullptr, nullptr},
     {"pair", false, -1, 63, &Options::pair, nullptr, nullptr},
@@ -447,6 +450,10 @@ int tmpt_scene_destroy(tmpt_scene* h)
     if (s.jt) (void)hipFree(s.jt);
     if (s.sbuf) (void)hipFree(s.sbuf);
     if (s.cam_rays) (void)hipFree(s.cam_rays);
+    if (s.split_buf) (void)hipFree(s.split_buf);
+    if (s.split_carry) (void)hipFree(s.split_carry);
+    for (auto& e : s.split_ev)
+        if (e) (void)hipEventDestroy(e);
     if (s.adapt_buf) (void)hipFree(s.adapt_buf);
     if (s.adapt_host) (void)hipHostFree(s.adapt_host);
     if (s.redo) (void)hipFree(s.redo);
@@ -629,6 +636,14 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
     }
     if (key && strcmp(key, "cam_rays_used") == 0) {  // read-only: the last render ran the camera pre-pass
         *value = (double)h->s.cam_rays_used;
+        return 0;
+    }
+    if (key && strcmp(key, "shadow_split_used") == 0) {  // read-only: passes of the last render the shadow split ran
+        *value = (double)h->s.split_used;
+        return 0;
+    }
+    if (key && strcmp(key, "shadow_split_resolve_ms") == 0) {  // read-only: k_split_resolve's time in that render
+        *value = h->s.split_resolve_ms;
         return 0;
     }
     return options_get(h->s.opt, key, value);

@@ -313,6 +313,7 @@ constexpr int kTieCounter = 24;       // [24] tied queries re-answered over the 
                                       // [30] crack / flat-triangle queries re-answered over it (ties[6])
 constexpr int kCrackCounter = 30;
 constexpr int kRedoRaysCounter = 31;  // rays of the k_redo launch (part of [0])
+constexpr int kSplitOverflowCounter = 47;  // shadow-split queue entries that found the queue full (none: an error)
 constexpr int kRedoCounter = 26;      // samples the deferred-tie sample kernel left to the redo pass
 
 // Per-scene options: the library's control plane in place of environment
@@ -337,6 +338,10 @@ struct Options {
     int cam_pre = -1;         // sample seeding, 5 waves: the pass's camera samples made by a pre-pass on full
                               // waves, k_path reads them (-1 = the measured default, 0 off, 1 on where it fits)
     double cam_pre_max = 0.0; // cam_pre: cap on the pre-pass's buffer, bytes (0 = half of the free HBM)
+    int shadow_split = 1;     // sample seeding, 5 waves, with the camera pre-pass: the shadow queries traced by a
+                              // kernel of their own after k_path (k_shadow), the samples resolved from records
+    double shadow_split_max = 0.0;  // shadow_split: cap on its queue and records, bytes (0 = half of the free HBM)
+    int shadow_split_pass = 0;      // shadow_split: at most this many samples of every pixel per pass (0 = what fits)
     int pilot = -1;           // pixel seeding: pilot-pass samples of the cost ordering (-1 auto, 0 off)
     int help = -1;            // pixel seeding: shadow offload to idle lanes (-1 auto, 0 off, 1 on)
     int pair = -1;            // pixel seeding: expensive ranks per 64-rank chunk with offload (-1 auto)
@@ -442,6 +447,26 @@ struct Scene {
     void* cam_rays = nullptr;
     size_t cam_bytes = 0;
     int32_t cam_rays_used = 0;
+    // the shadow split's queue (16 B per entry) and sample records (64 B per
+    // sample of a pass), kept and grown like sbuf; whether the last render ran
+    // it, its passes, and its kernels' times
+    void* split_buf = nullptr;
+    size_t split_bytes = 0;
+    int32_t split_used = 0, split_passes = 0;
+    // a shadow-split render in several passes of samples (render_split_passes):
+    // the pixels' float sums carried from pass to pass (RenderArgs::prog of
+    // its passes; non-null only while such a render runs) and the passes'
+    // summed statistics
+    float4* split_carry = nullptr;
+    size_t split_carry_slots = 0;
+    bool split_sub = false;
+    struct SplitAcc {
+        double extend_ms = 0.0, shadow_ms = 0.0, resolve_ms = 0.0, redo_ms = 0.0;
+        int64_t redo_samples = 0, redo_late = 0;
+        int32_t redo_launches = 0, launches = 0, used = 0;
+    } split_acc;
+    hipEvent_t split_ev[3] = {nullptr, nullptr, nullptr};  // before k_shadow, between, after k_split_resolve
+    double split_resolve_ms = 0.0;
     // deferred ties (PathCtl::redo): the redo list, its capacity in entries,
     // and the samples the last render left to the redo pass
     uint2* redo = nullptr;

@@ -26,8 +26,11 @@ __device__ __forceinline__ int mega_query(const SceneView& sv, f3 o, f3 d, float
 template <bool COUNT, int BLOCK, int SL, bool TOPC = false, bool CHECK_ANY = true>
 __device__ __forceinline__ f3 trace_path(const SceneView& sv, f3 o, f3 d, uint32_t& rng,
                                          uint32_t& rays, uint32_t& srays, TravStack<BLOCK, SL>& st, float* lbuf,
-                                         TravCount& cnt, bool root_check, int depth0 = 0)
+                                         TravCount& cnt, bool root_check, int depth0 = 0, int* end_depth = nullptr)
 {
+    // end_depth (the shadow split's re-trace): the path's depth goes there and
+    // its end colour is returned as it stands, lbuf[0, depth) holding the terms
+    // of the backward recurrence, which the caller's record leaves to k_split_resolve
     int depth = depth0;  // > 0: a path resumed at its depth0-th closest-hit query, lbuf[0, depth0) set
     f3 color = mk(0.0f, 0.0f, 0.0f);
     while (depth < kMaxDepth) {  // Trace, main.cpp:89-110
@@ -59,6 +62,10 @@ __device__ __forceinline__ f3 trace_path(const SceneView& sv, f3 o, f3 d, uint32
             color = sky(d);
             break;
         }
+    }
+    if (end_depth) {
+        *end_depth = depth;
+        return color;
     }
     for (int i = depth - 1; i >= 0; --i) color = backward_step(color, lbuf[i * BLOCK]);
     return color;

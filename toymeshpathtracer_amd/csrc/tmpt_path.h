@@ -172,7 +172,36 @@ struct PathCtl {
     // contiguous.  Read by the CAM kernels only.
     const CamRay* __restrict__ cam_rays;
     uint32_t cam_count;  // samples of the pass, smp_end - smp_begin
+    // The shadow split (option shadow_split; k_path SPLIT, k_shadow,
+    // k_split_resolve): a bounce whose light cosine is > 0 appends its shadow
+    // query {hit point, record << 4 | bounce} to sq instead of tracing it, and
+    // a finished sample leaves its record (SplitRec) in srec instead of a
+    // colour.  Record r = pixel slot * cam_count + (sample - smp_begin), as
+    // the pre-pass's entries.  A wave reserves kSplitChunk entries of sq per
+    // atomic on sq_ctl[0] and fills what it leaves unused with kSplitEmpty, so
+    // every entry below the counter is a query or empty.  sq_cap holds the
+    // worst case; an entry past it would not be written and counted in
+    // counters[kSplitOverflowCounter], the render call's error.
+    uint4* __restrict__ sq;
+    uint32_t* __restrict__ sq_ctl;
+    uint32_t sq_cap;
+    float4* __restrict__ srec;
 };
+
+// The shadow split's sample record, four 16-byte quarters: the path's end
+// colour (sky() of the last ray, or 0 after kMaxDepth hits) and its depth, then
+// the light cosines of its bounces -- the terms of the backward recurrence
+// (backward_step), which k_split_resolve runs once k_shadow has zeroed the
+// cosines of the occluded bounces.  A quarter past the depth is not written.
+struct alignas(16) SplitRec {
+    float end[3];
+    uint32_t depth;
+    float cosine[12];  // [0, depth); kMaxDepth <= 10
+};
+static_assert(sizeof(SplitRec) == 64 && kMaxDepth <= 12, "sample record: four dwordx4 quarters");
+constexpr uint32_t kSplitChunk = 1024u;        // queue entries a k_path wave reserves per atomic
+constexpr uint32_t kSplitEmpty = 0xFFFFFFFFu;  // .w of an entry no query was written to
+constexpr int64_t kSplitMaxRecs = 1ll << 28;   // records a queue entry's word can name (4 bits: the bounce)
 
 // ---- k_path's variants
 // What varies between k_path's instantiations, by its template parameters'
@@ -189,6 +218,7 @@ struct PathVariant {
     bool sums;                      // SUMS: the float sums beside the packed pixels
     int cam;                        // CAM: 0 the camera block, 1 the pre-pass's entries (PathCtl::cam_rays)
     bool list;                      // LIST: the unit decode's pixel is an index into PathCtl::order
+    int split;                      // SPLIT: shadow queries queued for k_shadow, sample records for k_split_resolve
 };
 
 // The LDS stack: 16 entries per lane; the 5-wave kernels of sample and pixel
@@ -271,6 +301,21 @@ uint32_t oct_shadow_check(const Scene& s);
 // k_resolve_px (beside k_path) over a whole tile's colour buffer, for the row engines
 void launch_resolve_px(hipStream_t stream, const float4* sbuf, int64_t P, int32_t spp, float spp_recip,
                        uint32_t* out);
+
+// tmpt_shadow.hip: the shadow split's two kernels after k_path SPLIT.
+// k_shadow answers the queued shadow queries (entries [0, min(*count, cap)) of
+// sq) and stores 0 into the record's cosine of an occluded bounce; `head` is
+// its fetch counter (zeroed by the caller), n_rec the records of srec, ovf the
+// lanes' stack spill areas (shadow_ovf_words() words).  k_split_resolve then runs each sample's backward
+// recurrence from its record, sums a pixel's cnt samples in sample order and
+// packs the pixel, as k_resolve_px does from the colour buffer: onto the sums
+// in carry_in where given (a pass after the first), the new sums left in
+// carry_out where given.
+size_t shadow_ovf_words(int device);
+int launch_shadow(hipStream_t stream, int device, const SceneView& sv, const uint4* sq, const uint32_t* count,
+                  uint32_t cap, uint32_t* head, float4* srec, uint32_t n_rec, uint32_t* ovf);
+void launch_split_resolve(hipStream_t stream, const float4* srec, int64_t P, int32_t cnt, float spp_recip,
+                          uint32_t* out, const float4* carry_in = nullptr, float4* carry_out = nullptr);
 
 #ifdef TMPT_EXP_WAVETIME  // timeline experiment: per wave, s_memrealtime at start / main loop end / exit
 constexpr int kWaveTimeMax = 16384;

@@ -153,11 +153,32 @@ __device__ __forceinline__ void redo_state_put(float4* ps, f3 o, f3 d, uint32_t 
         __hip_atomic_store(&w[8 + i], light[i * ls], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The shadow split's sample record (tmpt_path.h SplitRec) of a finished path:
+// its end colour and depth, and the light cosines of its bounces from the
+// lane's LDS slots (stride ls), a 16-byte quarter only where the depth reaches
+// it.  Nontemporal: the records stream through once.
+__device__ __forceinline__ void split_rec_put(float4* rec, f3 end, uint32_t depth, const float* light, uint32_t ls)
+{
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x4* q = reinterpret_cast<f32x4*>(rec);
+    __builtin_nontemporal_store((f32x4){end.x, end.y, end.z, __uint_as_float(depth)}, q);
+    if (depth > 0u)
+        __builtin_nontemporal_store((f32x4){light[0], light[ls], light[2 * ls], light[3 * ls]}, q + 1);
+    if (depth > 4u)
+        __builtin_nontemporal_store((f32x4){light[4 * ls], light[5 * ls], light[6 * ls], light[7 * ls]}, q + 2);
+    if (depth > 8u) __builtin_nontemporal_store((f32x4){light[8 * ls], light[9 * ls], 0.0f, 0.0f}, q + 3);
+}
+
+// srec (the shadow split): the re-trace leaves the sample's record there, not
+// a colour in sbuf.  The bounces before the dropped query keep the cosines the
+// drop recorded (their shadow queries are in the queue); the re-trace answers
+// the later bounces' shadow queries itself, so k_shadow and it together leave
+// the cosines the fused kernel would have used.
 template <int BLOCK, int SL>
 __device__ __forceinline__ void redo_sample(const SceneView& sv, const RenderArgs& a, uint32_t pix, uint32_t smp_depth,
                                             const float4* __restrict__ ps, float4* __restrict__ sbuf, uint32_t sb_ss,
                                             uint32_t sb_sp, uint32_t& rays_e, uint32_t& rays_s,
-                                            TravStack<BLOCK, SL>& st, float* lbuf)
+                                            TravStack<BLOCK, SL>& st, float* lbuf, float4* __restrict__ srec = nullptr)
 {
     const uint32_t smp = smp_depth & 0xFFFFu, depth = smp_depth >> 16;
     const float* w = reinterpret_cast<const float*>(ps);
@@ -168,6 +189,16 @@ __device__ __forceinline__ void redo_sample(const SceneView& sv, const RenderArg
         lbuf[i * BLOCK] = __hip_atomic_load(&w[8 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint32_t rng = __float_as_uint(h[3]);
     TravCount cnt;
+    if (srec) {
+        int end_depth = 0;
+        const f3 e = trace_path<false, BLOCK, SL, true, false>(sv, mk(h[0], h[1], h[2]), mk(h[4], h[5], h[6]), rng,
+                                                               rays_e, rays_s, st, lbuf, cnt, false, (int)depth,
+                                                               &end_depth);
+        const uint32_t cnt_smp = (uint32_t)(a.smp_end - a.smp_begin);
+        split_rec_put(srec + 4 * ((size_t)pix * cnt_smp + (smp - (uint32_t)a.smp_begin)), e, (uint32_t)end_depth, lbuf,
+                      BLOCK);
+        return;
+    }
     const f3 c = trace_path<false, BLOCK, SL, true, false>(sv, mk(h[0], h[1], h[2]), mk(h[4], h[5], h[6]), rng, rays_e,
                                                            rays_s, st, lbuf, cnt, false, (int)depth);
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -195,7 +226,8 @@ __device__ __forceinline__ void redo_mark(uint2* p)
 
 // The entries the deferring launch left untraced (its waves gave up waiting,
 // see k_path's redo phase): one lane per entry, grid-stride.
-template <int BLOCK, int SL>
+// SPLIT (the shadow split): sbuf is the sample records (PathCtl::srec).
+template <int BLOCK, int SL, bool SPLIT = false>
 __global__ void __launch_bounds__(BLOCK) k_redo(SceneView sv, RenderArgs a, uint2* __restrict__ list, uint32_t cap,
                                                 const float4* __restrict__ state, float4* __restrict__ sbuf,
                                                 uint32_t sb_ss, uint32_t sb_sp,
@@ -218,7 +250,7 @@ __global__ void __launch_bounds__(BLOCK) k_redo(SceneView sv, RenderArgs a, uint
         const uint2 e = list[i];
         if (e.x >= kRedoDone) continue;
         redo_sample<BLOCK, SL>(sv, a, e.x, e.y, state + (size_t)i * kRedoState4, sbuf, sb_ss, sb_sp, rays_e, rays_s,
-                               st, &s_light[threadIdx.x]);
+                               st, &s_light[threadIdx.x], SPLIT ? sbuf : nullptr);
     }
     const uint32_t re = wave_sum(rays_e), rs = wave_sum(rays_s);
     if (lane_id() == 0 && re + rs) {
@@ -451,7 +483,7 @@ __device__ void rss_chaser(const RenderArgs& a, const RsStream& S, int wave)
 
 template <bool COUNT, int BLOCK, int SL, int STEPS, int SHADE_MIN, int OCC = 1, int TAIL = 0, int PROF = 0,
           int HELP = 0, int SAMP = 0, bool SOA = false, int TIES = 0, bool SUMS = false, int CAM = 0,
-          bool LIST = false>
+          bool LIST = false, int SPLIT = 0>
 __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a, PathCtl pc,
                                                 uint32_t* __restrict__ out,
                                                 uint32_t* __restrict__ ovf,
@@ -484,6 +516,13 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // go by the pixel as everywhere else -- the pre-pass's entries too (CAM:
     // k_cam_rays_list leaves a listed pixel's where its slot's always are).
     static_assert(!LIST || (SAMP == 1 && !SUMS && !COUNT && !SOA && !HELP), "LIST: the plain sample kernels");
+    // SPLIT (the shadow split, CAM twins): a bounce whose light cosine is > 0
+    // counts its shadow ray, appends the query to PathCtl::sq for k_shadow and
+    // starts the scattered ray in the same shading round; the lane never
+    // traces an any-hit query, so qany is false throughout and the pending
+    // ray (s_next) and the shadow branch of the shading round are not there.
+    // A finished sample leaves its record (SplitRec) instead of a colour.
+    static_assert(!SPLIT || (CAM && !SUMS && !LIST && PROF == 0), "SPLIT: the plain CAM sample kernels");
     __shared__ uint32_t s_stack[SL * BLOCK];
     // SAMP 3, 4 (shadow-free speculation): no light terms, no pending next ray
     __shared__ float s_light[SAMP >= 3 ? 1 : kMaxDepth * BLOCK];
@@ -491,7 +530,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // ray's direction is kept while its bounce's shadow query runs -- its
     // origin is the shadow ray's (r.o)
     constexpr bool NEXT3 = OCC >= 5;
-    __shared__ float s_next[SAMP >= 3 ? 1 : (NEXT3 ? 3 : 6) * BLOCK];
+    __shared__ float s_next[SAMP >= 3 || SPLIT ? 1 : (NEXT3 ? 3 : 6) * BLOCK];
     if (SAMP == 4) {
         // The chaser role goes by arrival, not by blockIdx: the first nchase
         // blocks to START take it, so every chaser is resident by construction
@@ -541,6 +580,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     const uint64_t lt = (1ull << lane_id()) - 1ull;
     uint32_t seg = (uint32_t)(gtid >> 6) % kSeg, walked = 0;
     uint32_t res = 0, res_end = 0;
+    uint32_t q_res = 0, q_end = 0;  // SPLIT: the wave's reservation in the shadow queue
     if (SAMP == 2 || SAMP == 3) {  // the speculative row engine plans its units on the device
         pc.P = *pc.p_dev;
         pc.nchunks = (uint32_t)((pc.P + pc.chunk - 1) / pc.chunk);
@@ -848,7 +888,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 }
             }
             // ---- finished queries: shade
-            bool finish = false, want_off = false;
+            bool finish = false, want_off = false, emit = false;
             f3 color = mk(0.0f, 0.0f, 0.0f);
             if (has_pix && !in_query && !cam) {
                 if (HELP && waiting) {  // path ended, shadow answers were pending
@@ -915,7 +955,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                         f3 target = pos + nrm + rnd;
                         f3 nd = normalize(target - pos);
                         ++depth;
-                        if (SAMP < 3 && lc > 0.0f && !(SAMP == 2 && pc.rs_noshadow)) {
+                        if (SPLIT && lc > 0.0f) {  // queued for k_shadow from `so`; counted below
+                            emit = true;
+                            so = pos;  // (the kMaxDepth-th bounce starts no ray that would set it)
+                        }
+                        if (!SPLIT && SAMP < 3 && lc > 0.0f && !(SAMP == 2 && pc.rs_noshadow)) {
                             if (NEXT3) {
                                 nxt[0] = nd.x; nxt[LS] = nd.y; nxt[2 * LS] = nd.z;
                             } else {
@@ -946,7 +990,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                         if (DEFER && drop) color.x = -1.0f;
                         finish = true;
                     }
-                } else if (SAMP < 3) {  // shadow query of bounce depth-1
+                } else if (SAMP < 3 && !SPLIT) {  // shadow query of bounce depth-1
                     if (SAMP == 2 && pc.oct_shadow && octree_flag(sv, r, ts))
                         settle_any(sv, r, kMinT, kMaxT, ts);  // the row engines' serial walk (pixel, sample: above)
                     if (ts.best >= 0) light[(depth - 1) * LS] = 0.0f;
@@ -962,6 +1006,34 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     } else {
                         finish = true;  // kMaxDepth hits, colour stays 0 (main.cpp:88-89)
                     }
+                }
+            }
+            if (SPLIT) {  // append this round's shadow queries (the hit point is `so`)
+                const uint64_t em = wballot(emit);
+                if (em != 0) {
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    u32x4* q = reinterpret_cast<u32x4*>(pc.sq);
+                    const uint32_t ne = (uint32_t)__popcll(em);
+                    if (q_end - q_res < ne) {  // a new reservation; the old one's rest stays empty
+                        for (uint32_t i = q_res + (uint32_t)lane_id(); i < min(q_end, pc.sq_cap); i += 64u)
+                            __builtin_nontemporal_store((u32x4){0u, 0u, 0u, kSplitEmpty}, q + i);
+                        uint32_t b = 0;
+                        if (lane_id() == 0) b = atomicAdd(&pc.sq_ctl[0], kSplitChunk);
+                        q_res = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+                        q_end = q_res + kSplitChunk;
+                    }
+                    const uint32_t idx = q_res + (uint32_t)__popcll(em & lt);
+                    if (emit) {
+                        // the record of (pix, smp) and the bounce (depth was advanced past it)
+                        const uint32_t rec = pix * pc.cam_count + (smp - (uint32_t)a.smp_begin);
+                        if (idx < pc.sq_cap)
+                            __builtin_nontemporal_store((u32x4){__float_as_uint(so.x), __float_as_uint(so.y),
+                                                                __float_as_uint(so.z), (rec << 4) | (depth - 1u)},
+                                                        q + idx);
+                        else  // cannot happen (the queue holds the worst case): the render call's error
+                            atomicAdd(&counters[kSplitOverflowCounter], 1ull);
+                    }
+                    q_res += ne;
                 }
             }
             if (HELP) {  // pair lanes starting a shadow query with idle lanes
@@ -1005,7 +1077,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     for (int kk = 0; kk < (int)depth; ++kk) pend |= light[kk * LS] < 0.0f;
                 waiting = pend;
                 if (!pend) {
-                    if (SAMP < 3)
+                    if (SAMP < 3 && !SPLIT)
                         for (int kk = (int)depth - 1; kk >= 0; --kk)
                             color = backward_step(color, light[kk * LS]);
                     if (SAMP == 2 && pc.sbuf) {  // a chain sample traced in full: k_resolve sums in order
@@ -1033,6 +1105,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                             make_float4(SAMP == 3 ? 0.0f : color.x, SAMP == 3 ? 0.0f : color.y, SAMP == 3 ? 0.0f : color.z,
                                         __uint_as_float(draws | (nr << 23) | (ne << 28)));
                         pc.rs_end[cur_unit] = rng;
+                    } else if (SPLIT) {  // the sample's record: k_split_resolve runs the recurrence
+                        // DEFER: a dropped sample's record (x = -1) is redo_sample's
+                        if (!DEFER || !(color.x < 0.0f))
+                            split_rec_put(pc.srec + 4 * ((size_t)pix * pc.cam_count + (smp - (uint32_t)a.smp_begin)),
+                                          color, depth, light, LS);
                     } else if (SAMP && pc.sbuf) {  // sample seeding, blocks: k_resolve_px sums in sample order
                         typedef float f32x4 __attribute__((ext_vector_type(4)));
                         f32x4* dst = reinterpret_cast<f32x4*>(pc.sbuf + ((size_t)smp * pc.sb_ss + (size_t)pix * pc.sb_sp));
@@ -1125,7 +1202,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
             if (start) {
                 r = make_trav_ray(so, sd);
                 trav_init(ts, kMaxT);
-                qany = sany;
+                qany = SPLIT ? false : sany;
                 if (sany) ++rays_s; else ++rays_e;
                 in_query = sv.n > 0 && !ray_has_nan(so, sd);  // NaN ray / no triangles: a counted miss
                 // (CAM: the pre-pass made the root box test; its answer is the entry's flag)
@@ -1338,7 +1415,7 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 if (have) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the entry before its state
                     redo_sample<BLOCK, SL>(sv, a, e.x, e.y, pc.redo_state + (size_t)t * kRedoState4, pc.sbuf, pc.sb_ss,
-                                           pc.sb_sp, rays_e, rays_s, st, light);
+                                           pc.sb_sp, rays_e, rays_s, st, light, SPLIT ? pc.srec : nullptr);
                     redo_mark(pc.redo + t);
                     atomicAdd(&counters[kRedoTraced], 1ull);
                     t = (uint32_t)atomicAdd(&counters[kRedoTaken], 1ull);
@@ -1363,6 +1440,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
 #ifdef TMPT_EXP_WAVETIME
     if (lane_id() == 0 && wt_id < kWaveTimeMax) g_wavetime[3 * wt_id + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
+    if (SPLIT) {  // the rest of the wave's last reservation stays empty
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        for (uint32_t i = q_res + (uint32_t)lane_id(); i < min(q_end, pc.sq_cap); i += 64u)
+            __builtin_nontemporal_store((u32x4){0u, 0u, 0u, kSplitEmpty}, reinterpret_cast<u32x4*>(pc.sq) + i);
+    }
     if (SAMP == 4 && lane_id() == 0) {
         atomicAdd(&pc.rss.ctl[5], n_claim);
         atomicAdd(&pc.rss.ctl[6], n_miss);
@@ -1545,7 +1627,7 @@ static void launch_cam_rays(Scene& s, const RenderArgs& a, CamRay* out, const ui
 namespace {
 constexpr bool F = false, T = true;
 constexpr PathVariant kPathVariants[] = {
-    // count sl        steps         shade_min  occ prof help samp soa ties sums cam list
+    // count sl        steps         shade_min  occ prof help samp soa ties sums cam list split
     // ---- sample seeding (render_persistent, SAMP 1): 4 waves per SIMD ...
     {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 0, F, 0},   // no octree (or tie_rule index)
     {F, kPathSL, kSampleSteps, kShadeMin, 4, 0, 0, 1, F, 2, F, 0},   // the octree answers flagged ties in the main loop
@@ -1569,6 +1651,11 @@ constexpr PathVariant kPathVariants[] = {
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, T, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, T, 1},
+    // ... and the CAM twins of the shadow split (SPLIT; option shadow_split),
+    // the three tie modes
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 1, F, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 1, F, 1},
+    {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1, F, 1},
     // ... and the passes over a list of pixels (LIST; tmpt_render_adaptive's
     // passes after the first): 4 or 5 waves, the three tie modes, at 5 waves
     // with the CAM twins; they read the AoS records (layout=soa too)
@@ -1626,7 +1713,7 @@ constexpr bool same_variant(const PathVariant& a, const PathVariant& b)
 {
     return a.count == b.count && a.sl == b.sl && a.steps == b.steps && a.shade_min == b.shade_min && a.occ == b.occ &&
            a.prof == b.prof && a.help == b.help && a.samp == b.samp && a.soa == b.soa && a.ties == b.ties &&
-           a.sums == b.sums && a.cam == b.cam && a.list == b.list;
+           a.sums == b.sums && a.cam == b.cam && a.list == b.list && a.split == b.split;
 }
 
 // line I's kernel: the table's fields in k_path's parameter order
@@ -1635,7 +1722,7 @@ constexpr PathFn variant_kernel()
 {
     constexpr PathVariant v = kPathVariants[I];
     return k_path<v.count, kBlk, v.sl, v.steps, v.shade_min, v.occ, path_tail(v.samp), v.prof, v.help, v.samp, v.soa,
-                  v.ties, v.sums, v.cam, v.list>;
+                  v.ties, v.sums, v.cam, v.list, v.split>;
 }
 
 template <size_t... I>
@@ -1662,7 +1749,8 @@ int find_path_kernel(const PathVariant& v, const char* who, PathFn& fn)
               std::to_string(v.shade_min) + ", occ " + std::to_string(v.occ) + ", prof " + std::to_string(v.prof) +
               ", help " + std::to_string(v.help) + ", samp " + std::to_string(v.samp) + ", soa " +
               std::to_string(v.soa) + ", ties " + std::to_string(v.ties) + ", sums " + std::to_string(v.sums) +
-              ", cam " + std::to_string(v.cam) + ", list " + std::to_string(v.list));
+              ", cam " + std::to_string(v.cam) + ", list " + std::to_string(v.list) + ", split " +
+              std::to_string(v.split));
     return -22;
 }
 
@@ -1953,6 +2041,54 @@ constexpr int kCamPreDefault = 1;
 // cam_pre_max, or has to grow and does not fit in half of the device memory
 // still free (the colour buffer of the same call is allocated by then; the
 // buffer held counts as free), or cannot be allocated.
+// The shadow split's buffer for a pass of n samples: the control words (the
+// queue's counter and k_shadow's fetch head, a line each), a queue for the
+// worst case and the records.  Worst case: every bounce of
+// every sample queues a query (kMaxDepth each); a wave's reservation of
+// kSplitChunk entries leaves fewer than 64 unused when it takes the next one,
+// and its last one up to all of it.  False when that does not fit under option
+// shadow_split_max (or, where the buffer has to grow, in half of the device
+// memory still free), or a queue entry could not name the records.
+constexpr size_t kSplitCtlWords = 2 * kCtr;
+// the buffer's bytes for n samples (0: the entries cannot be counted or named), and the queue's entries
+static size_t split_need(int64_t n, int64_t waves, uint32_t& sq_cap)
+{
+    if (n <= 0 || n >= kSplitMaxRecs) return 0;
+    const int64_t worst = n * kMaxDepth;
+    // (a wave that queues holds a sample: no more of them than samples)
+    const int64_t cap = worst + worst / (kSplitChunk / 64 - 1) + (std::min(waves, n) + 1) * (int64_t)kSplitChunk;
+    if (cap >= (1ll << 32) - (int64_t)kSplitChunk * (waves + 1)) return 0;  // the counter is 32 bits
+    sq_cap = (uint32_t)cap;
+    return kSplitCtlWords * 4 + sizeof(uint4) * (size_t)cap + sizeof(SplitRec) * (size_t)n;
+}
+// what the buffer may take: option shadow_split_max, else half of the device
+// memory that is free or already the buffer's
+static size_t split_budget(const Scene& s)
+{
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
+    const size_t half = (fr + s.split_bytes) / 2;
+    return s.opt.shadow_split_max > 0.0 ? (size_t)std::min((double)half, s.opt.shadow_split_max) : half;
+}
+static bool ensure_split(Scene& s, int64_t n, int64_t waves, uint32_t& sq_cap)
+{
+    const size_t need = split_need(n, waves, sq_cap);
+    if (need == 0) return false;
+    if (s.opt.shadow_split_max > 0.0 && (double)need > s.opt.shadow_split_max) return false;
+    if (s.split_bytes >= need) return true;
+    if (need > split_budget(s)) return false;
+    if (s.split_buf) (void)hipFree(s.split_buf);
+    s.split_buf = nullptr;
+    s.split_bytes = 0;
+    if (hipMalloc(&s.split_buf, need) != hipSuccess) {
+        (void)hipGetLastError();
+        s.split_buf = nullptr;
+        return false;
+    }
+    s.split_bytes = need;
+    return true;
+}
+
 static bool ensure_cam_rays(Scene& s, size_t need)
 {
     if (s.opt.cam_pre_max > 0.0 && (double)need > s.opt.cam_pre_max) return false;
@@ -2208,8 +2344,10 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     const bool w5 = jt ? waves5 : waves5p;
     // stack spill areas for either kind of kernel's lanes (4 waves, 16 LDS
     // entries; 5 waves, 12)
-    const size_t ovf_words = std::max((size_t)grid4 * (kStackTotal - kPathSL),
-                                      (size_t)std::max(grid4, grid5) * (kStackTotal - kPathSL5)) * kBlk;
+    size_t ovf_words = std::max((size_t)grid4 * (kStackTotal - kPathSL),
+                                (size_t)std::max(grid4, grid5) * (kStackTotal - kPathSL5)) * kBlk;
+    // (k_shadow's lanes spill there after k_path's: more lanes, shorter LDS stacks)
+    if (jt && o.shadow_split != 0) ovf_words = std::max(ovf_words, shadow_ovf_words(s.device));
     const size_t head_words = (size_t)kSeg * kCtr;
     const size_t hist_words = ordered ? radix_sort_hist_words((int32_t)P) : 0;
     const size_t reg_words = ordered ? 2 * (size_t)kSimdKeys + 64 + (size_t)P : 0;  // + claim words
@@ -2329,9 +2467,35 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             TMPT_HIP(hipGetLastError());
             s.cam_rays_used = 1;
         }
+        // The shadow split (option shadow_split; k_path SPLIT, tmpt_shadow.hip):
+        // the CAM kernels' twins queue their shadow queries for k_shadow and
+        // leave sample records for k_split_resolve.  With the colour buffer's
+        // units only (several blocks per pixel), for a whole plain render
+        // (no progressive or adaptive pass, no float sums), and not where a
+        // shadow answer can need the octree (oct_shadow: k_shadow does not
+        // carry that check).  Taken when the records and a queue for the
+        // worst case -- every bounce of every sample queues -- fit
+        // (ensure_split); otherwise the fused kernels, with the same image.
+        uint32_t sq_cap = 0;
+        // (split_sub: a pass of render_split_passes, whose carried sums are a.prog)
+        const bool split_on = o.shadow_split != 0 && cam_on && !sums && pc.sbuf && !s.adapt_on &&
+                              (s.split_sub || (!pass && !a.prog)) && !oct_shadow &&
+                              ensure_split(s, cam_n, (int64_t)grid5 * (kBlk / 64), sq_cap);
+        if (split_on) {
+            uint32_t* ctl = static_cast<uint32_t*>(s.split_buf);
+            pc.sq_ctl = ctl;
+            pc.sq = reinterpret_cast<uint4*>(ctl + kSplitCtlWords);
+            pc.sq_cap = sq_cap;
+            pc.srec = reinterpret_cast<float4*>(pc.sq + sq_cap);
+            TMPT_HIP(hipMemsetAsync(ctl, 0, kSplitCtlWords * 4, s.stream));
+            if (!s.split_ev[0])
+                for (auto& e : s.split_ev) TMPT_HIP(hipEventCreate(&e));
+            s.split_used = 1;
+        }
         // the launch's kernel: flagged ties deferred (TIES 1) with the redo list,
         // answered in the main loop (TIES 2) without
         PathVariant v_main = variant(w5, help, flag ? (redo ? 1 : 2) : 0, sums, cam_on ? 1 : 0);
+        v_main.split = split_on ? 1 : 0;
         PathFn fn_main;
         if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
         // the launch's grid is the launched kernel's co-resident block count
@@ -2375,19 +2539,40 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                 }
                 TMPT_HIP(hipMemsetAsync(d_counters, 0, kRenderCounters * sizeof(unsigned long long), s.stream));
                 TMPT_HIP(hipMemsetAsync(heads, 0, head_words * 4, s.stream));
+                if (split_on) TMPT_HIP(hipMemsetAsync(pc.sq_ctl, 0, kSplitCtlWords * 4, s.stream));
                 continue;
             }
             s.redo_late = (int64_t)(std::min<unsigned long long>(n, s.redo_cap) - std::min(traced, n));
             if (traced < std::min<unsigned long long>(n, s.redo_cap)) {  // entries the launch left
                 TMPT_HIP(hipEventRecord(s.path_ev[0], s.stream));
-                k_redo<kBlk, kPathSL><<<grid, kBlk, 0, s.stream>>>(view(s), as, s.redo, s.redo_cap, s.redo_state,
-                                                                  pc.sbuf, pc.sb_ss, pc.sb_sp, (uint32_t*)s.ws,
-                                                                  d_counters);
+                if (split_on)
+                    k_redo<kBlk, kPathSL, true><<<grid, kBlk, 0, s.stream>>>(view(s), as, s.redo, s.redo_cap,
+                                                                            s.redo_state, pc.srec, pc.sb_ss, pc.sb_sp,
+                                                                            (uint32_t*)s.ws, d_counters);
+                else
+                    k_redo<kBlk, kPathSL><<<grid, kBlk, 0, s.stream>>>(view(s), as, s.redo, s.redo_cap, s.redo_state,
+                                                                      pc.sbuf, pc.sb_ss, pc.sb_sp, (uint32_t*)s.ws,
+                                                                      d_counters);
                 TMPT_HIP(hipGetLastError());
                 TMPT_HIP(hipEventRecord(s.path_ev[1], s.stream));
                 s.redo_launches = 1;  // timed apart from k_path (tmpt_stats.redo_ms)
             }
             break;
+        }
+        if (split_on) {
+            // after k_path (and k_redo): the queued shadow queries, then the records
+            TMPT_HIP(hipEventRecord(s.split_ev[0], s.stream));
+            if (launch_shadow(s.stream, s.device, view(s), pc.sq, pc.sq_ctl, pc.sq_cap, pc.sq_ctl + kCtr, pc.srec,
+                              (uint32_t)cam_n, (uint32_t*)s.ws)) {
+                set_error("tmpt_render: k_shadow launch failed");
+                return -1;
+            }
+            TMPT_HIP(hipEventRecord(s.split_ev[1], s.stream));
+            launch_split_resolve(s.stream, pc.srec, a.slots, (int32_t)(s1 - s0), a.out_recip, d_out,
+                                 a.smp_begin > 0 ? a.prog : nullptr, a.prog);
+            TMPT_HIP(hipGetLastError());
+            TMPT_HIP(hipEventRecord(s.split_ev[2], s.stream));
+            return 0;
         }
         // (tmpt_render_adaptive sums the pass's samples itself, k_adapt_update)
         if (pc.sbuf && !s.adapt_on) {
@@ -2627,6 +2812,9 @@ void reset_render_stats(Scene& s)
     s.redo_rays = 0;
     s.tie_path = 0;
     s.cam_rays_used = 0;
+    s.split_used = 0;
+    s.split_passes = 0;
+    s.split_resolve_ms = 0.0;
 }
 
 // tmpt_camera_rays: the camera pre-pass of desc's pass alone, with the
@@ -2657,6 +2845,113 @@ int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uin
         set_error(std::string("tmpt_camera_rays: ") + hipGetErrorString(e));
         return -1;
     }
+    return 0;
+}
+
+// The shadow split where the whole render's records and queue do not fit
+// (option shadow_split_max, the device's free memory, or the 2^28 records a
+// queue entry can name): the samples per pass that do, a multiple of the
+// largest sample block (8) where it can be, else a power of two, so every
+// pass starts on a block; 0: no split render (the option is off, or not even
+// one sample of every pixel fits), >= spp: one pass, render_persistent's own.
+static int32_t split_pass_samples(Scene& s, const RenderArgs& a)
+{
+    const Options& o = s.opt;
+    if (o.shadow_split == 0 || !a.jt || a.slots <= 0 || o.path_waves == 4 || o.cam_pre == 0 || s.soa.na != nullptr ||
+        oct_shadow_check(s))
+        return 0;
+    PathVariant probe5{};
+    probe5.sl = kPathSL5;
+    probe5.steps = kSampleSteps;
+    probe5.shade_min = kShadeMin;
+    probe5.occ = 5;
+    probe5.samp = 1;
+    probe5.ties = 1;
+    PathFn fn;
+    if (find_path_kernel(probe5, "tmpt_render", fn)) return 0;
+    const int64_t waves = (int64_t)occupancy_grid((const void*)fn, kBlk, 0, s.device) * (kBlk / 64);
+    const size_t budget = split_budget(s);
+    uint32_t cap = 0;
+    auto fits = [&](int64_t c) {
+        if (o.shadow_split_pass > 0 && c > o.shadow_split_pass) return false;
+        const size_t need = split_need(a.slots * c, waves, cap);
+        return need != 0 && need <= budget;
+    };
+    if (fits(a.spp)) return a.spp;
+    {  // several passes: each is a pass of render_persistent, which needs the colour buffer (its rule)
+        const size_t need = sizeof(float4) * (size_t)a.spp * (size_t)a.slots;
+        size_t fr = 0, tot = 0;
+        size_t sbuf_budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.sbuf_bytes;
+        if (o.sbuf_max > 0.0) sbuf_budget = std::min(sbuf_budget, (size_t)o.sbuf_max);
+        if (need > sbuf_budget) return 0;
+    }
+    int64_t c = 0;
+    for (int64_t step = 1ll << 20; step >= 8; step >>= 1)  // the largest multiple of 8 that fits
+        if (c + step < a.spp && fits(c + step)) c += step;
+    if (c == 0)
+        for (int64_t p = 4; p >= 1 && c == 0; p >>= 1)
+            if (fits(p)) c = p;
+    return (int32_t)c;
+}
+
+// ... and that render: passes of cs samples, each a pass of render_persistent
+// (its shadow split between k_path and the resolve) that adds its samples, in
+// order, to the pixels' float sums carried in Scene::split_carry, as a
+// progressive pass adds to Scene::prog -- the same additions in the same order
+// as one pass makes.  The counters add up on the device; the deferred ties'
+// (a list per launch) start at zero in every pass.  The host waits once per
+// pass, for its kernels' times.
+static int render_split_passes(Scene& s, const RenderArgs& a, int32_t cs, uint32_t* d_out,
+                               unsigned long long* d_counters)
+{
+    if (s.split_carry_slots < (size_t)a.slots) {
+        if (s.split_carry) (void)hipFree(s.split_carry);
+        s.split_carry = nullptr;
+        s.split_carry_slots = 0;
+        TMPT_HIP(hipMalloc(&s.split_carry, sizeof(float4) * (size_t)a.slots));
+        s.split_carry_slots = (size_t)a.slots;
+    }
+    Scene::SplitAcc acc;
+    int rc = 0;
+    int32_t tie_path = 0, passes = 0;
+    for (int32_t b = 0; b < a.spp && rc == 0; b += cs, ++passes) {
+        RenderArgs ap = a;
+        ap.smp_begin = b;
+        ap.smp_end = std::min(b + cs, a.spp);
+        ap.prog = s.split_carry;
+        if (b > 0) {
+            TMPT_HIP(hipMemsetAsync(d_counters + kRedoCounter, 0, 4 * sizeof(unsigned long long), s.stream));
+            reset_render_stats(s);
+        }
+        s.split_sub = true;
+        rc = render_persistent(s, ap, d_out, false, d_counters);
+        s.split_sub = false;
+        if (rc) break;
+        TMPT_HIP(hipStreamSynchronize(s.stream));
+        float k = 0.0f;
+        (void)hipEventElapsedTime(&k, s.path_ev[2], s.path_ev[3]);
+        acc.extend_ms += k;
+        if (s.redo_launches) {
+            (void)hipEventElapsedTime(&k, s.path_ev[0], s.path_ev[1]);
+            acc.redo_ms += k;
+        }
+        if (s.split_used) {
+            (void)hipEventElapsedTime(&k, s.split_ev[0], s.split_ev[1]);
+            acc.shadow_ms += k;
+            (void)hipEventElapsedTime(&k, s.split_ev[1], s.split_ev[2]);
+            acc.resolve_ms += k;
+        }
+        acc.redo_samples += s.redo_samples;
+        acc.redo_late += s.redo_late;
+        acc.redo_launches += s.redo_launches;
+        acc.launches += s.path_launches;
+        acc.used += s.split_used;
+        if (b == 0) tie_path = s.tie_path;
+    }
+    if (rc) return rc;
+    s.split_acc = acc;
+    s.split_passes = passes;
+    s.tie_path = tie_path;
     return 0;
 }
 
@@ -2743,8 +3038,12 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
     reset_render_stats(s);
     if (a.slots > 0) {
         if (wave) rc = render_wavefront(s, a, d_out, count);
-        else if (persistent) rc = render_persistent(s, a, d_out, count, d_counters);
-        else if (rowspec) {
+        else if (persistent) {
+            // (the shadow split in several passes where one pass's buffers do not fit)
+            const int32_t cs = !count && !progressive && !d_sums ? split_pass_samples(s, a) : 0;
+            rc = cs > 0 && cs < a.spp ? render_split_passes(s, a, cs, d_out, d_counters)
+                                      : render_persistent(s, a, d_out, count, d_counters);
+        } else if (rowspec) {
             // the streaming engine, or the iterated one where it does not apply
             rc = s.opt.rowspec_stream != 0 && s.opt.rowspec_noshadow != 0 ? render_rowstream(s, a, d_out, d_counters)
                                                                           : 1;
@@ -2776,6 +3075,10 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
     if (rc) return rc;
     if (se != hipSuccess) {
         set_error(std::string("render: ") + hipGetErrorString(se));
+        return -1;
+    }
+    if (c[kSplitOverflowCounter]) {
+        set_error("tmpt_render: internal: the shadow split's queue overflowed");
         return -1;
     }
     s.render_ms = ms;
@@ -2823,6 +3126,26 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
             (void)hipEventElapsedTime(&kr, s.path_ev[0], s.path_ev[1]);
             s.redo_ms = kr;
             s.redo_rays = c[kRedoRaysCounter];
+        }
+        if (s.split_passes > 1) {  // render_split_passes: its passes' sums
+            const Scene::SplitAcc& acc = s.split_acc;
+            s.extend_ms = acc.extend_ms;
+            s.shadow_ms = acc.shadow_ms;
+            s.split_resolve_ms = acc.resolve_ms;
+            s.redo_ms = acc.redo_ms;
+            s.redo_samples = acc.redo_samples;
+            s.redo_late = acc.redo_late;
+            s.redo_launches = acc.redo_launches;
+            s.redo_rays = c[kRedoRaysCounter];
+            s.path_launches = acc.launches;
+            s.shadow_launches = s.split_used = acc.used;
+        } else if (s.split_used) {  // the shadow split: k_shadow's time apart from the twin's
+            float ks = 0.0f, kr = 0.0f;
+            (void)hipEventElapsedTime(&ks, s.split_ev[0], s.split_ev[1]);
+            (void)hipEventElapsedTime(&kr, s.split_ev[1], s.split_ev[2]);
+            s.shadow_ms = ks;
+            s.split_resolve_ms = kr;
+            s.shadow_launches = 1;
         }
         s.extend_rays = c[3];
         s.shadow_rays = c[0] - c[3];
