@@ -49,7 +49,10 @@ extern "C" {
                               render option denoise_lds -- again no struct above changed;
                               still 9, additive: the check hooks tmpt_scene_dump_bvh and tmpt_radix_sort;
                               still 9, additive: tmpt_render_adaptive with tmpt_adaptive_desc and
-                              tmpt_adaptive_info (adaptive sampling) -- no struct above changed */
+                              tmpt_adaptive_info (adaptive sampling) -- no struct above changed;
+                              still 9, additive: tmpt_adaptive_desc.radius (the neighbourhood rule of
+                              adaptive sampling) in the place of reserved[0] -- size and offsets kept,
+                              0 = the rule as it was */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -539,9 +542,34 @@ int tmpt_render_radiance(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_r
  * To first order: the standard error of the packed value sqrtf(mean) exceeds tau,
  * in units of full scale.  fmaxf returns the other operand for a NaN and a NaN
  * compares false, so a pixel with a sample that is not finite stops at the count
- * where it appears; nothing is screened, as in tmpt_denoise.  The decision reads
- * the pixel's own samples only (no neighbourhood rule), so shard tiles assemble
- * into the whole frame's outputs bit for bit.
+ * where it appears; nothing is screened, as in tmpt_denoise.  With radius = 0 the
+ * decision reads the pixel's own samples only (no neighbourhood rule), so shard
+ * tiles assemble into the whole frame's outputs bit for bit, whatever band_rows.
+ *
+ * The neighbourhood rule, radius = r in 1 .. 8: only the stay-active rule changes;
+ * the schedule, the sums, m1, m2 and the test's arithmetic do not.
+ *   own_p  = the test above (n < S and se2 > lim), after the pass ending at n, for
+ *            a pixel active through that pass; false for every pixel that was not
+ *   N_r(p) = the pixels q with |q.x - p.x| <= r and |q.y - p.y| <= r (global
+ *            rows), inside the frame and in p's band: q.y / band_rows ==
+ *            p.y / band_rows (band_rows = 0: the whole height is one band);
+ *            p itself is a member
+ *   p stays active iff it was active through the pass, n < S, and own_q is true
+ *   for some q in N_r(p).  A pixel that has stopped never resumes: its samples
+ *   stay the prefix [0, n_p).
+ * What follows from it:
+ *   - per-count identity holds as before: a pixel that stopped at n is bit for
+ *     bit the pixel of tmpt_render_radiance at spp = n, and n_p is one of the
+ *     schedule's ends;
+ *   - the neighbourhood is clipped to the band, so the tiles of any shard /
+ *     num_shards with one band_rows assemble bit for bit into the num_shards = 1
+ *     result with that band_rows.  The result now depends on band_rows (with
+ *     1-row bands the reach is horizontal only); with radius = 0 it does not;
+ *   - a pixel with a sample that is not finite no longer necessarily stops where
+ *     that sample appears: its own test is false, but a neighbour can carry it
+ *     on.  Nothing is screened, as before;
+ *   - monotone in r: for r >= r' every pixel's count at r is >= its count at r'
+ *     (own_p depends on p's samples alone; by induction over the passes).
  * Result, n_p the count at which the pixel stopped:
  *   rgba32f_out = {sum.rgb * (1.0f / (float)n_p), 1.0f}
  *   rgba8_out   = that pixel packed as every render packs its own (main.cpp:224-233)
@@ -551,7 +579,8 @@ typedef struct {
     int32_t spp_min;    /* samples every pixel gets, 2 .. desc->spp; 0 = default: min(24, desc->spp) */
     int32_t spp_step;   /* samples a still-active pixel gets per further pass, >= 1; 0 = default: 8 */
     float   threshold;  /* tau >= 0 and finite; < 0 = default: 0.015f; NaN / inf: -22 */
-    int32_t reserved[5];
+    int32_t radius;     /* the neighbourhood rule's reach in pixels, 0 .. 8; 0 = none: the own test alone */
+    int32_t reserved[4];
 } tmpt_adaptive_desc;
 
 typedef struct {
@@ -568,8 +597,9 @@ typedef struct {
  * pointers (rgba32f_out 16-byte aligned, rgba8_out and spp_out 4-byte);
  * TMPT_FLAG_WAIT_STREAM as in tmpt_render.
  * *ray_count = every HitScene call of every traced sample.  tmpt_get_stats
- * afterwards: render_ms covers the whole call (the passes, the update and
- * compaction kernels, the host's wait after each pass and the final kernel);
+ * afterwards: render_ms covers the whole call (the passes, the update, the
+ * neighbourhood rule's and the compaction kernels, the host's wait after each
+ * pass and the final kernel);
  * extend_ms, redo_ms, extend_rays, shadow_rays, extend_launches, redo_launches,
  * redo_samples, redo_late, redo_rays, tie_queries, root_misses and
  * crack_queries are summed over the passes; iterations = the passes;
@@ -577,8 +607,8 @@ typedef struct {
  * TMPT_SEED_SAMPLE and the persistent engine only: -22 for another seeding or
  * engine, for spp_begin / spp_count other than 0, for TMPT_FLAG_COUNT_VISITS,
  * for spp_min outside 2 .. desc->spp (after the defaults), a negative
- * spp_step, a threshold that is NaN or infinite, a schedule of more than 64
- * passes, and a call without any output.  The call needs the per-sample colour buffer (16 B per
+ * spp_step, a threshold that is NaN or infinite, a radius outside 0 .. 8, a
+ * schedule of more than 64 passes, and a call without any output.  The call needs the per-sample colour buffer (16 B per
  * sample of the tile at the cap): -12 where that does not fit (render option
  * sbuf_max), as for a progressive pass.  It leaves the scene's progressive state
  * alone, as tmpt_render_aov does: it may run between two passes of a

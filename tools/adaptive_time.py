@@ -13,6 +13,10 @@ warm-up round, then `rounds` timed rounds; medians and the spread (max - min):
       the two are compared by k_path's time per ray as well
   (d) tmpt_render_adaptive with the defaults
   (b0), (c0): (b) and (c) with render option cam_pre = 0
+  (dR) for every radius R > 0 given: (d) with the neighbourhood rule at that
+      radius (tmpt_adaptive_desc.radius).  Different radii trace different
+      samples, so they are compared by the rest per pass and by k_path's time
+      per ray, which the table's last lines give
 
 Per variant: tmpt_stats.render_ms (for (b) the sum over its calls), the host's
 wall time around the call(s), extend_ms (the k_path launches alone) and the
@@ -26,9 +30,10 @@ For (d) also the time per pass against the pixels it traced: the call with the
 cap cut to n_k runs passes 0..k with the same pixels (the test of a pass reads
 only the samples so far), so pass k's time is the difference of two such calls.
 
-  python tools/adaptive_time.py [rounds, default 5] [cap, default 64]
+  python tools/adaptive_time.py [rounds, default 5] [cap, default 64] [radius ...]
 
-profiles/adaptive_time.log is this tool's output (DESIGN.md "Adaptive sampling")."""
+profiles/adaptive_time.log is this tool's output (DESIGN.md "Adaptive sampling"),
+profiles/adaptive_nb_time.log its output with radii 1 and 2 ("Neighbourhood rule")."""
 import os
 import sys
 import time
@@ -54,6 +59,7 @@ def med(v):
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     cap = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+    radii = [int(a) for a in sys.argv[3:]]
     w, h = 1920, 1080
     tris, bmin, bmax = tm.load_scene(gen_standin_sponza.ensure())
     cam = tm.Camera.for_scene(bmin, bmax, w, h, is_sponza=True)
@@ -101,9 +107,16 @@ def main():
             _, _, _, rays, info = sc.trace_adaptive(cam, w, h, cap, out=outs)
             return stat(), rays, info
 
+        def run_dr(radius):
+            def run():
+                _, _, _, rays, info = sc.trace_adaptive(cam, w, h, cap, out=outs, radius=radius)
+                return stat(), rays, info
+            return run
+
         variants = (("a", "tmpt_render", run_a), ("b", "progressive, 8 passes of 8", run_b),
                     ("c", "adaptive, tau 0, (8, 8)", run_c), ("d", "adaptive, defaults", run_d),
                     ("b0", "(b) with cam_pre = 0", run_b0), ("c0", "(c) with cam_pre = 0", run_c0))
+        variants += tuple((f"d{r}", f"adaptive, defaults, radius {r}", run_dr(r)) for r in radii)
         res = {k: [] for k, _, _ in variants}
         wall = {k: [] for k, _, _ in variants}
         last = {}
@@ -127,13 +140,19 @@ def main():
             wm, ws = med(wall[k])
             rays, info = last[k]
             ns = cols[1][0] * 1e6 / rays
-            print(f"  ({k:2s}) {name:28s}: render_ms {cols[0][0]:8.3f} ({cols[0][1]:6.3f})  wall {wm:8.3f} ({ws:6.3f})  "
+            print(f"  ({k:2s}) {name:30s}: render_ms {cols[0][0]:8.3f} ({cols[0][1]:6.3f})  wall {wm:8.3f} ({ws:6.3f})  "
                   f"extend_ms {cols[1][0]:8.3f} ({cols[1][1]:6.3f})  rest {cols[2][0]:7.3f} ({cols[2][1]:6.3f})  "
                   f"rays {rays} ({ns:.4f} ns of k_path per ray)" + (f"  samples {info['samples']} of {w * h * cap}" if info else ""), flush=True)
         mb, mc = med(np.array(res["b"])[:, 0]), med(np.array(res["c"])[:, 0])
         rb, rc = med(np.array(res["b"])[:, 2]), med(np.array(res["c"])[:, 2])
         print(f"  (c) - (b): render_ms {mc[0] - mb[0]:+.3f} ms; the rests differ by {rc[0] - rb[0]:+.3f} ms; spreads "
               f"{mb[1]:.3f} / {mc[1]:.3f} ms", flush=True)
+        for r in radii:  # the rest per pass against (d)'s
+            rd, rr = med(np.array(res["d"])[:, 2]), med(np.array(res[f"d{r}"])[:, 2])
+            pd, pr = last["d"][1]["passes"], last[f"d{r}"][1]["passes"]
+            print(f"  (d{r}) against (d): rest per pass {rr[0] / pr:.3f} ms ({pr} passes) against {rd[0] / pd:.3f} ms "
+                  f"({pd} passes): {rr[0] / pr - rd[0] / pd:+.3f} ms per pass; spreads of the rests {rd[1]:.3f} / "
+                  f"{rr[1]:.3f} ms; pass_pixels {last[f'd{r}'][1]['pass_pixels']}", flush=True)
         # (d) pass by pass: the cap cut to n_k
         info = last["d"][1]
         ends = [min(SPP_MIN, cap)]

@@ -108,7 +108,7 @@ class _DenoiseDesc(ctypes.Structure):
 
 class _AdaptiveDesc(ctypes.Structure):
     _fields_ = [("spp_min", ctypes.c_int32), ("spp_step", ctypes.c_int32), ("threshold", ctypes.c_float),
-                ("reserved", ctypes.c_int32 * 5)]
+                ("radius", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
 
 
 class _AdaptiveInfo(ctypes.Structure):
@@ -649,7 +649,7 @@ class Scene:
 
     def trace_adaptive(self, camera: Camera, width: int, height: int, spp: int, spp_min: int = 0, spp_step: int = 0,
                        threshold: float = -1.0, band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None,
-                       wait_stream="current"):
+                       wait_stream="current", radius: int = 0):
         """Adaptive sampling of one shard (tmpt_render_adaptive; include/tmpt.h
         states its arithmetic): sample seeding on the persistent engine, ``spp``
         the cap.  Every pixel gets ``spp_min`` samples, a pixel still active
@@ -662,7 +662,18 @@ class Scene:
         and ``pass_pixels`` (the pixels each pass traced).  ``out``: a triple of
         device pointers or None (float tile 16-byte aligned, rgba8 tile, int32
         map), at least one given; the arrays returned are then None.
-        ``wait_stream`` as in :meth:`trace_image`."""
+        ``wait_stream`` as in :meth:`trace_image`.
+
+        ``radius`` (0 .. 8; 0: none) is the neighbourhood rule: a pixel still
+        active stays active while the variance test holds for itself or for any
+        pixel within ``radius`` columns and ``radius`` rows of it, inside the
+        frame and inside its own band of ``band_rows`` rows (0: the whole
+        height is one band).  A stopped pixel never resumes, so per-count
+        identity holds as before.  The neighbourhood is clipped to the band so
+        that the tiles of any ``shard`` / ``num_shards`` assemble bit for bit
+        into the ``num_shards = 1`` result with the same ``band_rows``; with a
+        radius the result depends on ``band_rows`` (1-row bands: horizontal
+        reach only)."""
         # bound on first use, as tmpt_fastdiv is
         fn = _sig("tmpt_render_adaptive", ctypes.c_int,
                   [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
@@ -676,7 +687,7 @@ class Scene:
         d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
                   FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
         ad = _AdaptiveDesc()
-        ad.spp_min, ad.spp_step, ad.threshold = spp_min, spp_step, threshold
+        ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
         rows = int(_tile_rows(ctypes.byref(d)))
         rays = ctypes.c_uint64()
         inf = _AdaptiveInfo()

@@ -9,7 +9,10 @@
 // pixel's sums over the pass's samples, in sample order, from the colour
 // buffer, applies the test of include/tmpt.h and marks the pixels that go on;
 // k_adapt_scan and k_adapt_scatter compact them, in ascending slot order,
-// into the next pass's list.  k_adapt_final scales, packs and writes the three
+// into the next pass's list.  With a radius (the neighbourhood rule) the marks
+// come from the own tests dilated over the tile instead: k_adapt_update_own,
+// k_adapt_pack, k_adapt_dilate and k_adapt_gather below; radius 0 launches none
+// of them.  k_adapt_final scales, packs and writes the three
 // outputs.  The host reads the next list's length (one word, with the pass's
 // counters) after every pass but the last: that length sizes the next launch.
 #include <hip/hip_runtime.h>
@@ -93,6 +96,130 @@ __global__ void __launch_bounds__(64) k_adapt_update(const float4* __restrict__ 
     }
     const uint64_t m = wballot(active);
     if (t == 0) {
+        mask[blockIdx.x] = m;
+        cnt[blockIdx.x] = (uint32_t)__popcll(m);
+    }
+}
+
+// k_adapt_update for the neighbourhood rule (radius > 0): the same staging, sums
+// and test, statement for statement -- a kernel of its own, so that the radius-0
+// call keeps k_adapt_update's code as it is.  The pixel's own test goes to
+// own[slot], one byte per tile slot; mask / cnt are left to k_adapt_gather.  A
+// pixel leaves the list only at a pass where its own test failed, so the plane
+// holds false for every dropped pixel with no clearing; pass 0 lists every slot
+// and so initialises it.
+__global__ void __launch_bounds__(64) k_adapt_update_own(const float4* __restrict__ sbuf,
+                                                         const uint32_t* __restrict__ list, uint32_t n, int32_t spp,
+                                                         int32_t s0, int32_t s1, float lim4,
+                                                         AdaptState* __restrict__ state, uint8_t* __restrict__ own)
+{
+    constexpr int kC = 16;               // samples per staged chunk
+    __shared__ float4 tile[64][kC + 1];  // +1: a lane's row starts on another bank
+    __shared__ uint32_t s_pix[64];
+    const uint32_t p0 = blockIdx.x * 64u;
+    const int t = (int)threadIdx.x;
+    const int np = (int)min(64u, n - p0);
+    const uint32_t pix = t < np ? (list ? list[p0 + t] : p0 + (uint32_t)t) : 0u;
+    s_pix[t] = pix;
+    AdaptState st{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0, {0u, 0u}};
+    if (s0 > 0 && t < np) st = state[pix];
+    __syncthreads();
+    for (int32_t c0 = s0; c0 < s1; c0 += kC) {
+        const int nc = min(kC, s1 - c0);
+        for (int e = t; e < 64 * kC; e += 64) {
+            const int i = e / kC, j = e - i * kC;
+            if (i < np && j < nc) tile[i][j] = sbuf[(size_t)s_pix[i] * (size_t)spp + (size_t)(c0 + j)];
+        }
+        __syncthreads();
+        if (t < np)
+            for (int j = 0; j < nc; ++j) {
+                const float4 c = tile[t][j];
+                st.r = st.r + c.x;
+                st.g = st.g + c.y;
+                st.b = st.b + c.z;
+                const float y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+                st.m1 = st.m1 + y;
+                st.m2 = st.m2 + y * y;
+            }
+        __syncthreads();
+    }
+    if (t < np) {
+        const float fn = (float)s1;
+        const float mean = st.m1 / fn;
+        const float var = fmaxf(0.0f, st.m2 / fn - mean * mean);
+        const float se2 = var / (fn - 1.0f);
+        const float lim = lim4 * fmaxf(mean, 1.0f / 256.0f);
+        st.n = s1;
+        state[pix] = st;
+        own[pix] = s1 < spp && se2 > lim ? 1 : 0;  // a NaN compares false
+    }
+}
+
+// ---- the neighbourhood rule (radius r > 0): a listed pixel stays active iff
+// the own test held for some pixel within r columns and r rows of it, inside
+// the frame and inside its band.  The own plane is packed into one bit per
+// pixel, rows of wpr = ceil(W / 64) 64-bit words (bit b of word j = column
+// 64 j + b; the bits past W are 0), dilated word by word, and read back per
+// list position.  The tile's rows of one band are consecutive and tile row t
+// lies in the shard's band t / band_rows (only the last band may be short),
+// so the band clip is a clip of tile rows.
+
+// One wave per word of the bit plane: a ballot over 64 pixels of a row.
+__global__ void __launch_bounds__(256) k_adapt_pack(const uint8_t* __restrict__ own, int32_t W, uint32_t wpr,
+                                                    uint32_t nwords, uint64_t* __restrict__ bits)
+{
+    const uint32_t wi = blockIdx.x * 4u + (threadIdx.x >> 6);  // wave-uniform
+    if (wi >= nwords) return;
+    const uint32_t row = wi / wpr, j = wi - row * wpr;
+    const uint32_t x = j * 64u + (uint32_t)lane_id();
+    const bool on = x < (uint32_t)W && own[(size_t)row * (size_t)W + x] != 0;
+    const uint64_t m = wballot(on);
+    if (lane_id() == 0) bits[wi] = m;
+}
+
+// One lane per word: OR over the rows of the band within r (the word and its
+// two neighbours in the row), then the OR of the shifts by 1 .. r with the
+// neighbour words' bits carried in.  r <= 8 < 64: every shift count is in
+// 1 .. 63.  A word left of column 0 or right of the row's last is 0, as are
+// the last word's bits past W: the frame clips the neighbourhood.
+__global__ void __launch_bounds__(256) k_adapt_dilate(const uint64_t* __restrict__ bits, uint32_t wpr, uint32_t nwords,
+                                                      int32_t tile_rows, int32_t band_rows, int32_t r,
+                                                      uint64_t* __restrict__ dil)
+{
+    const uint32_t wi = blockIdx.x * 256u + threadIdx.x;
+    if (wi >= nwords) return;
+    const int32_t row = (int32_t)(wi / wpr);
+    const uint32_t j = wi - (uint32_t)row * wpr;
+    const int32_t b0 = (row / band_rows) * band_rows, b1 = min(tile_rows, b0 + band_rows);  // the band's rows [b0, b1)
+    const int32_t lo = max(b0, row - r), hi = min(b1 - 1, row + r);
+    uint64_t vl = 0, vc = 0, vr = 0;
+    for (int32_t t = lo; t <= hi; ++t) {
+        const uint64_t* w = bits + (size_t)t * wpr + j;
+        vc |= w[0];
+        if (j > 0) vl |= w[-1];
+        if (j + 1 < wpr) vr |= w[1];
+    }
+    uint64_t d = vc;
+    for (int32_t k = 1; k <= r; ++k) d |= (vc << k) | (vl >> (64 - k)) | (vc >> k) | (vr << (64 - k));
+    dil[wi] = d;
+}
+
+// One lane per list position, as k_adapt_update: the dilated bit at the
+// pixel's slot, balloted into the mask[block] / cnt[block] that k_adapt_scan
+// and k_adapt_scatter consume.
+__global__ void __launch_bounds__(64) k_adapt_gather(const uint32_t* __restrict__ list, uint32_t n, int32_t W,
+                                                     uint32_t wpr, const uint64_t* __restrict__ dil,
+                                                     uint64_t* __restrict__ mask, uint32_t* __restrict__ cnt)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    bool active = false;
+    if (i < n) {
+        const uint32_t pix = list ? list[i] : i;
+        const uint32_t row = pix / (uint32_t)W, x = pix - row * (uint32_t)W;
+        active = ((dil[(size_t)row * wpr + (x >> 6)] >> (x & 63u)) & 1ull) != 0;
+    }
+    const uint64_t m = wballot(active);
+    if (threadIdx.x == 0) {
         mask[blockIdx.x] = m;
         cnt[blockIdx.x] = (uint32_t)__popcll(m);
     }
@@ -189,7 +316,12 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
         const size_t slots = (size_t)a.slots, nb_max = (slots + 63) / 64;
         const size_t o_list0 = align256(sizeof(AdaptState) * slots), o_list1 = o_list0 + align256(4 * slots);
         const size_t o_mask = o_list1 + align256(4 * slots), o_cnt = o_mask + align256(8 * nb_max);
-        const size_t o_total = o_cnt + align256(4 * nb_max), need = o_total + 256;
+        const size_t o_total = o_cnt + align256(4 * nb_max);
+        // the neighbourhood rule's planes (radius > 0): own bytes, the bit plane and its dilation
+        const int32_t radius = ad->radius;
+        const uint32_t wpr = ((uint32_t)a.W + 63u) / 64u, nwords = wpr * (uint32_t)a.tile_rows;
+        const size_t o_own = o_total + 256, o_bits = o_own + align256(slots), o_dil = o_bits + align256(8 * (size_t)nwords);
+        const size_t need = radius > 0 ? o_dil + align256(8 * (size_t)nwords) : o_total + 256;
         if (s.adapt_bytes < need) {
             if (s.adapt_buf) (void)hipFree(s.adapt_buf);
             s.adapt_buf = nullptr;
@@ -208,6 +340,9 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
         uint64_t* mask = reinterpret_cast<uint64_t*>(base + o_mask);
         uint32_t* cnt = reinterpret_cast<uint32_t*>(base + o_cnt);
         uint32_t* total = reinterpret_cast<uint32_t*>(base + o_total);
+        uint8_t* own = reinterpret_cast<uint8_t*>(base + o_own);  // radius > 0 only: inside the buffer then
+        uint64_t* bits = reinterpret_cast<uint64_t*>(base + o_bits);
+        uint64_t* dil = reinterpret_cast<uint64_t*>(base + o_dil);
         const float lim4 = 4.0f * (ad->threshold * ad->threshold);
         const uint32_t* list = nullptr;  // pass 0: every slot
         int64_t n_list = a.slots;
@@ -229,9 +364,21 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
             if (rc) break;
             const uint32_t n = (uint32_t)n_list, nb = (n + 63u) / 64u;
             const bool last = n1 >= a.spp;
-            k_adapt_update<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, mask, cnt);
+            if (radius > 0)
+                k_adapt_update_own<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, own);
+            else
+                k_adapt_update<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, mask, cnt);
             TMPT_HIP(hipGetLastError());
             uint32_t* next = lists[k & 1];
+            if (!last && radius > 0) {  // the neighbourhood rule: mask / cnt from the dilated own plane
+                k_adapt_pack<<<(nwords + 3u) / 4u, 256, 0, s.stream>>>(own, a.W, wpr, nwords, bits);
+                TMPT_HIP(hipGetLastError());
+                k_adapt_dilate<<<(nwords + 255u) / 256u, 256, 0, s.stream>>>(bits, wpr, nwords, a.tile_rows, a.band_rows,
+                                                                           radius, dil);
+                TMPT_HIP(hipGetLastError());
+                k_adapt_gather<<<nb, 64, 0, s.stream>>>(list, n, a.W, wpr, dil, mask, cnt);
+                TMPT_HIP(hipGetLastError());
+            }
             if (!last) {
                 k_adapt_scan<<<1, kScanBlock, 0, s.stream>>>(cnt, nb, total);
                 TMPT_HIP(hipGetLastError());

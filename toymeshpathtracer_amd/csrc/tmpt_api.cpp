@@ -910,6 +910,7 @@ int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
     if (r.spp_min < 2 || r.spp_min > d->spp)
         return bad("tmpt_render_adaptive: spp_min outside 2 .. spp (0 = default)");
     if (r.spp_step < 1) return bad("tmpt_render_adaptive: spp_step must not be negative (0 = default)");
+    if (r.radius < 0 || r.radius > 8) return bad("tmpt_render_adaptive: radius outside 0 .. 8 (0 = no neighbourhood rule)");
     if (1 + (d->spp - r.spp_min + r.spp_step - 1) / r.spp_step > 64)
         return bad("tmpt_render_adaptive: spp_min / spp_step give a schedule of more than 64 passes");
     if (!rgba32f_out && !rgba8_out && !spp_out)

@@ -1,7 +1,7 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
-//        [--adaptive TAU[,MIN[,STEP]]] [--spp-map OUT.png]
+//        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -14,9 +14,10 @@
 // PREFIX_depth.png.
 // --denoise OUT.png (one device, --seed sample): beside the usual output, the frame's float
 // radiance (tmpt_render_radiance) filtered by tmpt_denoise with the AOV records as guides.
-// --adaptive TAU[,MIN[,STEP]] (one device, --seed sample): the frame comes from tmpt_render_adaptive
+// --adaptive TAU[,MIN[,STEP[,RADIUS]]] (one device, --seed sample): the frame comes from tmpt_render_adaptive
 // with spp as the cap (MIN, STEP: spp_min, spp_step; left out or 0 = the defaults, a negative TAU
-// too); --spp-map OUT.png writes the samples each pixel got, n_p / spp, as grey.  With --denoise
+// too; RADIUS 0..8, left out = 0: the neighbourhood rule -- a pixel goes on while the test holds for
+// any pixel within RADIUS columns and rows of it, the whole frame being one band); --spp-map OUT.png writes the samples each pixel got, n_p / spp, as grey.  With --denoise
 // the filter takes the adaptive radiance; the AOV pass stays at spp.
 #include <math.h>
 #include <stdio.h>
@@ -186,7 +187,9 @@ int main(int argc, const char** argv)
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
-               "[--denoise file.png] [--adaptive tau[,min[,step]]] [--spp-map file.png]\n");
+               "[--denoise file.png] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png]\n"
+               "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
+               "any pixel within radius columns and rows of it\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -222,9 +225,9 @@ int main(int argc, const char** argv)
         else if (!strcmp(argv[i], "--denoise") && i + 1 < argc) denoised = argv[++i];
         else if (!strcmp(argv[i], "--spp-map") && i + 1 < argc) spp_map = argv[++i];
         else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) {
-            int mn = 0, stp = 0;
+            int mn = 0, stp = 0, rad = 0;
             float tau = -1.0f;
-            if (sscanf(argv[++i], "%f,%d,%d", &tau, &mn, &stp) < 1) {
+            if (sscanf(argv[++i], "%f,%d,%d,%d", &tau, &mn, &stp, &rad) < 1) {
                 printf("ERROR: invalid --adaptive argument '%s'\n", argv[i]);
                 return 1;
             }
@@ -232,6 +235,7 @@ int main(int argc, const char** argv)
             ad.threshold = tau;
             ad.spp_min = mn;
             ad.spp_step = stp;
+            ad.radius = rad;
         }
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }

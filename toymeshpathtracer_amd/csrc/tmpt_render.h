@@ -164,7 +164,7 @@ int render_aov(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, tmpt
 int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count, unsigned long long* d_counters);
 
 // tmpt_adaptive.hip: adaptive sampling (tmpt_render_adaptive) of one shard; ad
-// holds the resolved spp_min, spp_step and threshold (checked by the caller),
+// holds the resolved spp_min, spp_step, threshold and radius (checked by the caller),
 // the three tiles are device pointers or null
 int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
                     float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count);
