@@ -84,7 +84,11 @@ enum {
 /* render flags */
 enum {
     TMPT_FLAG_OUT_DEVICE = 1,    /* rgba_out is a device pointer on the scene's device */
-    TMPT_FLAG_COUNT_VISITS = 2,  /* instrumented traversal: node visits / triangle tests */
+    TMPT_FLAG_COUNT_VISITS = 2,  /* instrumented traversal: node visits / triangle tests.  The
+                                    persistent engine's instrumented kernels keep the lowest-index
+                                    leaf: closest hits tied on t go to the lowest triangle index
+                                    even with the octree built, so on a scene whose ties decide
+                                    pixels the image is the one of tie_rule = index */
     TMPT_FLAG_WAIT_STREAM = 4,   /* the render starts after the work enqueued on desc->wait_stream */
     TMPT_FLAG_REQUIRE_RCCL = 8   /* tmpt_render_multi: fail unless the gather runs over RCCL */
 };

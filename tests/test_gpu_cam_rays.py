@@ -12,6 +12,7 @@ import pytest
 
 import oracle
 import toymeshpathtracer_amd as tm
+from cam_rays_restate import camera_samples_expect
 from conftest import data
 from test_gpu_cameras import CAMERAS, _camera
 
@@ -20,42 +21,11 @@ W, H, SPP = 24, 16, 8          # the entries' frame
 RW, RH, RSPP = 160, 90, 16     # the on / off renders
 
 
-def _step(x):
-    """xorshift32 (maths.cpp:5-13), checked against the oracle's in _expect."""
-    x ^= (x << 13) & 0xFFFFFFFF
-    x ^= x >> 17
-    x ^= (x << 15) & 0xFFFFFFFF
-    return x
-
-
 @functools.lru_cache(maxsize=None)
 def _expect(cam_name):
     """The whole 24x16x8 frame's camera samples through camera cam_name over
-    suzanne: (uint32[H, W, SPP, 7] origin, direction, RNG state after the
-    camera's draws; disk tries[H, W, SPP]), as tests/render_restate.py::aov_expect
-    makes its rays."""
-    cam = _camera("suzanne", cam_name).as_array()
-    assert _step(12345) == int(oracle.xorshift_seq(12345, 1)[0])
-    inv_w, inv_h = f32(1) / f32(W), f32(1) / f32(H)
-    out = np.zeros((H, W, SPP, 7), np.uint32)
-    tries = np.zeros((H, W, SPP), np.int32)
-    for y in range(H):
-        for x in range(W):
-            seed = oracle.pixel_seed(x, y, W)
-            for s in range(SPP):
-                st = oracle.sample_seed(seed, s)
-                r = oracle.float01_seq(st, 2)
-                state = _step(_step(st))
-                o, d, after = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
-                out[y, x, s, 0:3], out[y, x, s, 3:6], out[y, x, s, 6] = o.view(np.uint32), d.view(np.uint32), after
-                n, z = 0, state
-                while z != after:  # two draws per try of the lens disk
-                    z = _step(_step(z))
-                    n += 1
-                    assert n < 64
-                tries[y, x, s] = n
-    out.setflags(write=False)
-    return out, tries
+    suzanne (cam_rays_restate.camera_samples_expect)."""
+    return camera_samples_expect(_camera("suzanne", cam_name).as_array(), W, H, SPP)
 
 
 def _suzanne():
