@@ -11,6 +11,7 @@ import numpy as np
 import oracle
 import toymeshpathtracer_amd as tm
 from conftest import data
+from render_restate import oracle_samples
 
 f32 = np.float32
 
@@ -45,22 +46,8 @@ def camera(name, w, h):
 
 def sample_colours(osc, cam, w, h, spp):
     """(colour float32[h, w, spp, 3], rays int64[h, w, spp]) of every sample of a
-    sample-seeded frame: radiance_expect's loop, nothing summed."""
-    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
-    col = np.zeros((h, w, spp, 3), f32)
-    rays = np.zeros((h, w, spp), np.int64)
-    for y in range(h):
-        for x in range(w):
-            seed = oracle.pixel_seed(x, y, w)
-            for s in range(spp):
-                state = oracle.sample_seed(seed, s)
-                r = oracle.float01_seq(state, 2)
-                state = int(oracle.xorshift_seq(state, 2)[1])
-                o, d, state = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
-                c, state, n = osc.trace(o, d, state)
-                col[y, x, s] = c
-                rays[y, x, s] = n
-    return col, rays
+    sample-seeded frame: radiance_expect's samples, nothing summed."""
+    return oracle_samples(osc, cam, w, h, spp, tm.SEED_SAMPLE)
 
 
 @functools.lru_cache(maxsize=None)

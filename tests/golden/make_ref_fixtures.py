@@ -1,11 +1,14 @@
 """Regenerates tests/golden/ref/ from the compiled reference.
 
     make -C oracle/ref            # needs a checkout of the reference, see its Makefile
-    python tests/golden/make_ref_fixtures.py [case ...]
+    python tests/golden/make_ref_fixtures.py [hit case ... | trace]
 
-Runs oracle/_ref/ref_hits (the reference's HitScene) on every hit case of
-tests/ref_cases.py and oracle/_ref/tmpt_ref (its CLI) on every frame case, and
-writes hits_<case>.npz, frame_<case>.png, frames.json and the small OBJ exports.
+Runs oracle/_ref/ref_trace (the reference's GetRay, HitScene and Trace(), sample
+by sample) on every trace case of tests/ref_cases.py, oracle/_ref/ref_hits (its
+HitScene) on every hit case and oracle/_ref/tmpt_ref (its CLI) on every frame
+case, and writes trace_<case>.npz, hits_<case>.npz, frame_<case>.png,
+frames.json and the small OBJ exports.  The trace cases must reach the floors of
+ref_cases.TRACE_FLOORS, counted from the reference's answers, or the run fails.
 The same inputs give the same files byte for byte (ref_cases.save_npz; the PNGs
 are tmpt_ref's own output.png).
 """
@@ -16,6 +19,8 @@ import shutil
 import subprocess
 import sys
 import tempfile
+
+import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -51,10 +56,35 @@ def make_frame(name, tmp):
     return {"width": w, "height": h, "spp": spp, "krays": krays}
 
 
+def make_trace(name, tmp):
+    """trace_<name>.npz: the case's frame through ref_trace, sample seeding (every
+    field) and pixel seeding (colour, state out and ray count).  -> trace_counts."""
+    w, h, spp = C.TRACE_SIZE
+    tris, bmin, bmax, cam = C.trace_scene(name)
+    box = C.octree_box(bmin, bmax)
+    exe = os.path.join(REF_BIN, "ref_trace")
+    ch_s, ch_p = C.seed_chains(w, h, spp, True), C.seed_chains(w, h, spp, False)
+    s = C.run_ref_trace(exe, tris, box, cam, w, h, ch_s, tmp)
+    p = C.run_ref_trace(exe, tris, box, cam, w, h, ch_p, tmp)
+    fx = {"tris": tris, "bmin": bmin, "bmax": bmax, "box": box, "cam": cam, "size": np.array([w, h, spp], np.int32),
+          "chains_sample": ch_s, "chains_pixel": ch_p}
+    fx.update({"s_" + k: v for k, v in s.items()})
+    fx.update({"p_" + k: p[k] for k in ("col", "state", "rays")})
+    C.save_npz(C.trace_path(name), fx)
+    counts = C.trace_counts(fx)
+    print(f"trace_{name}: {len(tris)} triangles, {w}x{h}x{spp}, {counts}, {os.path.getsize(C.trace_path(name)) >> 10} KiB")
+    return counts
+
+
 def main(argv):
     os.makedirs(C.REF_DIR, exist_ok=True)
     only = set(argv)
     with tempfile.TemporaryDirectory() as tmp:
+        if not only or only & {"trace"}:  # "trace": the trace cases alone
+            C.check_trace_counts({name: make_trace(name, tmp) for name in C.TRACE_CASES})
+            only.discard("trace")
+            if argv and not only:
+                return
         for name in C.HIT_CASES:
             if not only or name in only:
                 make_hits(name, tmp)

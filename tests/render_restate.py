@@ -6,6 +6,7 @@ import numpy as np
 
 import oracle
 import toymeshpathtracer_amd as tm
+from ref_cases import seed_chains
 
 f32 = np.float32
 
@@ -25,6 +26,24 @@ def light_cosine(n, d):
     nl = np.where((dot(n, d) < 0)[:, None], n, -n)
     c = dot(np.broadcast_to(LIGHT, nl.shape), nl)
     return np.where(c > 0, c, f32(0)).astype(f32)
+
+
+def aov_sums(hit, nrm, t, spp=None):
+    """(normal[h, w, 3], depth[h, w], hits[h, w]) of include/tmpt.h's AOV record
+    from the samples' first hits -- hit bool[h, w, S], nrm float32[h, w, S, 3],
+    t float32[h, w, S], whatever made them (the oracle in aov_expect, the
+    reference's recorded answers in test_gpu_reference_trace.py) -- over the
+    first spp samples: float32 sums from 0 in sample order, a miss adding
+    nothing, each times 1 / spp."""
+    spp = hit.shape[2] if spp is None else spp
+    h, w = hit.shape[:2]
+    nsum, dsum = np.zeros((h, w, 3), f32), np.zeros((h, w), f32)
+    for s in range(spp):
+        nsum = np.where(hit[..., s, None], nsum + nrm[..., s, :], nsum)
+        dsum = np.where(hit[..., s], dsum + t[..., s], dsum)
+    recip = f32(1) / f32(spp)
+    assert nsum.dtype == f32 and dsum.dtype == f32
+    return nsum * recip, dsum * recip, hit[..., :spp].sum(-1)
 
 
 def aov_expect(osc, cam, w, h, spp):
@@ -50,17 +69,15 @@ def aov_expect(osc, cam, w, h, spp):
     lit = want_shadow & (sids < 0)
     shape = (h, w, spp)
     hit, lit, lc, ids = hit.reshape(shape), lit.reshape(shape), lc.reshape(shape), ids.reshape(shape)
-    nrm, t = hits[:, 3:6].reshape(shape + (3,)), hits[:, 6].reshape(shape)
     rec = np.zeros((h, w), tm.AOV_DTYPE)
-    nsum, dsum, lsum = np.zeros((h, w, 3), f32), np.zeros((h, w), f32), np.zeros((h, w), f32)
-    for s in range(spp):  # float32 sums in sample order; a miss adds nothing
-        nsum = np.where(hit[..., s, None], nsum + nrm[..., s, :], nsum)
-        dsum = np.where(hit[..., s], dsum + t[..., s], dsum)
+    rec["normal"], rec["depth"], rec["hits"] = aov_sums(hit, hits[:, 3:6].reshape(shape + (3,)),
+                                                        hits[:, 6].reshape(shape))
+    lsum = np.zeros((h, w), f32)
+    for s in range(spp):  # as aov_sums sums
         lsum = np.where(lit[..., s], lsum + lc[..., s], lsum)
-    recip = f32(1) / f32(spp)
-    rec["normal"], rec["depth"], rec["direct"] = nsum * recip, dsum * recip, lsum * recip
+    rec["direct"] = lsum * (f32(1) / f32(spp))
     rec["tri_id"] = np.where(hit[..., 0], ids[..., 0], -1)
-    rec["hits"], rec["lit"] = hit.sum(-1), lit.sum(-1)
+    rec["lit"] = lit.sum(-1)
     per_pixel = hit.sum(-1)
     counts = dict(hits=int(hit.sum()), misses=int((~hit).sum()),
                   shadowed=int((want_shadow.reshape(shape) & ~lit).sum()),
@@ -77,28 +94,52 @@ def same_records(got, want):
     assert got.tobytes() == want.tobytes()
 
 
+def chain_samples(osc, cam, w, h, chains):
+    """The oracle's pieces sample by sample over chains (k, 4) {x, y, state,
+    count} (ref_cases.seed_chains): the two jitter draws, get_ray, Scene.trace,
+    the state threaded through a chain's samples.  -> dict of ray (n, 6) float32,
+    state_ray (n,) uint32 (after get_ray), col (n, 3) float32, state (n,) uint32
+    (after trace), rays (n,) int64."""
+    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
+    n = int(np.asarray(chains)[:, 3].sum())
+    out = dict(ray=np.zeros((n, 6), f32), state_ray=np.zeros(n, np.uint32), col=np.zeros((n, 3), f32),
+               state=np.zeros(n, np.uint32), rays=np.zeros(n, np.int64))
+    i = 0
+    for x, y, state, count in (tuple(int(v) for v in c) for c in chains):
+        for _ in range(count):
+            r = oracle.float01_seq(state, 2)
+            state = int(oracle.xorshift_seq(state, 2)[1])
+            o, d, state = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
+            out["ray"][i, :3], out["ray"][i, 3:], out["state_ray"][i] = o, d, state
+            out["col"][i], state, out["rays"][i] = osc.trace(o, d, state)
+            out["state"][i] = state
+            i += 1
+    return out
+
+
+def oracle_samples(osc, cam, w, h, spp, seed_mode):
+    """(colour float32[h, w, spp, 3], rays int64[h, w, spp]) of every sample of a
+    pixel- or sample-seeded frame from the oracle's pieces; nothing summed."""
+    s = chain_samples(osc, cam, w, h, seed_chains(w, h, spp, seed_mode == tm.SEED_SAMPLE))
+    return s["col"].reshape(h, w, spp, 3), s["rays"].reshape(h, w, spp)
+
+
+def radiance_sum(col, rays, spp=None):
+    """(float32[h, w, 3] colour sum in sample order times 1/spp, rays) over the
+    first spp of the samples col[h, w, S, 3], rays[h, w, S], whatever made them
+    (oracle_samples, or the reference's recorded answers)."""
+    spp = col.shape[2] if spp is None else spp
+    acc = np.zeros(col.shape[:2] + (3,), f32)
+    for s in range(spp):
+        acc = acc + col[:, :, s]  # float32, sample order
+    assert acc.dtype == f32
+    return acc * (f32(1) / f32(spp)), int(rays[:, :, :spp].sum())
+
+
 def radiance_expect(osc, cam, w, h, spp, seed_mode):
     """(float32[h, w, 3] colour sum in sample order times 1/spp, rays) from the
     oracle's pieces: the seeds, the two jitter draws, get_ray, Scene.trace."""
-    inv_w, inv_h = f32(1) / f32(w), f32(1) / f32(h)
-    out = np.zeros((h, w, 3), f32)
-    rays = 0
-    for y in range(h):
-        for x in range(w):
-            seed = oracle.pixel_seed(x, y, w)
-            state = seed  # pixel seeding: one stream per pixel, threaded through the samples
-            col = np.zeros(3, f32)
-            for s in range(spp):
-                if seed_mode == tm.SEED_SAMPLE:
-                    state = oracle.sample_seed(seed, s)
-                r = oracle.float01_seq(state, 2)
-                state = int(oracle.xorshift_seq(state, 2)[1])
-                o, d, state = oracle.get_ray(cam, float((f32(x) + r[0]) * inv_w), float((f32(y) + r[1]) * inv_h), state)
-                c, state, n = osc.trace(o, d, state)
-                col = col + c  # float32, sample order
-                rays += n
-            out[y, x] = col * (f32(1) / f32(spp))
-    return out, rays
+    return radiance_sum(*oracle_samples(osc, cam, w, h, spp, seed_mode))
 
 
 def same_bits(got, want, what=""):
