@@ -52,7 +52,10 @@ extern "C" {
                               tmpt_adaptive_info (adaptive sampling) -- no struct above changed;
                               still 9, additive: tmpt_adaptive_desc.radius (the neighbourhood rule of
                               adaptive sampling) in the place of reserved[0] -- size and offsets kept,
-                              0 = the rule as it was */
+                              0 = the rule as it was;
+                              still 9, additive: tmpt_scene_update (a device BVH refit, or a rebuild, of a
+                              scene in place) and the read-only options update_kind, update_ms and
+                              bvh_cost -- no struct above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -391,6 +394,17 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *   pop_key_bits     read-only (tmpt_scene_get_option): the width K of that key on this scene, 31 less
  *                    the bits of a child link (the record count's and leaf_max's widths), at most 16 and
  *                    at most pop_key_cap; 0, and nothing culled, where fewer than 9 would be left
+ *   update_kind      read-only: the scene's last tmpt_scene_update -- 0 none since creation, 1 refit,
+ *                    2 rebuild
+ *   update_ms        read-only: the device time of that update, between two events on the scene's
+ *                    stream (a refit: the upload through the last kernel)
+ *   bvh_cost         read-only: the surface-area cost of the tree as it stands -- the sum over every
+ *                    valid child slot of the decoded box's area x (1 for a node, the triangle count
+ *                    for a leaf), over the area of the root's box (the union of the padded triangle
+ *                    boxes), in float64 (tests/bvh_check.py cost()); computed on demand by a
+ *                    reduction kernel and kept until the next update; 0 for the empty scene.  It
+ *                    tells when a refitted tree has degraded enough to rebuild; the library applies
+ *                    no policy of its own
  *   pop_key_cap      test hook (-1 = no cap): at most this many key bits (0..16; 0..8 give no key)
  *   redo_cap        test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown
@@ -751,6 +765,47 @@ int tmpt_camera_rays(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_rende
  *           (either neighbour where the extent is within 2^-40 relative of 255 * 2^k) */
 int tmpt_scene_dump_bvh(const tmpt_scene* scene, int32_t layout, uint32_t* nodes, uint64_t node_words,
                         uint32_t* tris, uint64_t tri_words, int32_t info[8]);
+/* Scene update: new triangles for a scene that exists, in place of tmpt_scene_destroy +
+ * tmpt_scene_create_ex.  tris holds n x 9 floats in host memory, as tmpt_scene_create takes them.
+ *
+ * TMPT_UPDATE_REFIT needs n equal to the scene's n (else -22).  The tree keeps its shape and is
+ * fitted to the new triangles: triangle i of tris takes the slot triangle i had.
+ *   unchanged   the topology and the numbering of the nodes (links, masks), the leaf ranges and the
+ *               order of the triangle records, count_shift, link_bits, pop_key_bits, and every
+ *               other word of info
+ *   recomputed  every triangle record (v0, e1, e2 with the build's roundings, [9] = 2 x index with
+ *               the flat mark cleared), every TriOrig record with its normal, and every node's
+ *               origin, exponents and quantised planes; on a layout=soa scene the planes too
+ *   contract    after a refit the dump is the one the rules of "What every build keeps" give for
+ *               the OLD links and the NEW triangles, word for word: a child's box is the union U
+ *               of the padded boxes beneath it (an exact f32 min / max, so the order of reduction
+ *               does not matter), and a node's words are a function of its children's U alone
+ *               (tests/bvh_refit_restate.py restates it in numpy).  Rules tree, order, slots,
+ *               leaves, records and boxes all still hold; only "leaves: collapse=greedy ..."
+ *               speaks of the tree's shape, which the refit does not touch.  A refit with the
+ *               scene's own triangles changes no word.
+ *   cost        one launch per triangle record and one per BVH4 level, deepest first, on the
+ *               scene's stream, no host synchronisation between them; n = 0 does nothing, n = 1
+ *               rewrites the one-leaf node.  The tree no longer follows the triangles' new
+ *               positions: option bvh_cost says by how much.
+ * TMPT_UPDATE_REBUILD takes any n >= 0 and runs the full build with the scene's build options into
+ * fresh allocations, swapped in only on success: a failed rebuild (a tree too deep for the
+ * traversal stack, out of memory) returns the build's error and leaves the scene exactly as it
+ * was.  The handle, the stream, every option, the workspace, the sample, camera pre-pass and
+ * shadow-split buffers and the jump tables are kept.
+ *
+ * Both modes synchronise the scene's stream first, replace the scene's host copy of the
+ * triangles, and DROP THE OCTREE exactly as if none had been built: the device octree is freed,
+ * tmpt_stats.octree_* read 0, tie_rule in effect is index (1), no record carries the flat mark.
+ * Call tmpt_scene_build_octree again with the new bounds (the octree is a host build over bounds
+ * only the caller knows).  The progressive state is invalidated: a render with spp_begin > 0
+ * straight after fails with -22, as after a camera change.  Like tmpt_scene_build_octree the call
+ * must not run while a call on the scene is in flight on another host thread.
+ * -22 with a message, checked in this order before any device call: an unknown mode, n < 0, null
+ * tris with n > 0, a null scene, a refit whose n is not the scene's.
+ * Read-only options afterwards (tmpt_scene_get_option): update_kind, update_ms, bvh_cost. */
+enum { TMPT_UPDATE_REFIT = 0, TMPT_UPDATE_REBUILD = 1 };
+int tmpt_scene_update(tmpt_scene* scene, const float* tris, int32_t n, int32_t mode);
 /* Check hook: the device radix sort the build (Morton keys) and the pixel-seeded renders (the
  * cost-ordered pixel supply) use, run on caller data: the n pairs (keys[i], vals[i]) (host
  * memory) are uploaded, sorted on the scene's stream and written back in place.  The scene only

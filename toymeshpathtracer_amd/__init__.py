@@ -17,6 +17,7 @@ reference                   here
 (none: float frame)         :meth:`Scene.trace_radiance` (the render's linear radiance beside its bytes)
 (none: denoiser)            :meth:`Scene.denoise` (edge-avoiding a-trous filter guided by the AOV records)
 (none: adaptive sampling)   :meth:`Scene.trace_adaptive` (per-pixel sample counts by a variance test)
+(none: scene update)        :meth:`Scene.update` (new triangles in place: a device BVH refit, or a rebuild)
 ``stbi_write_png`` :342     :func:`write_png`
 ==========================  ==============================================
 
@@ -41,6 +42,7 @@ __all__ = [
 
 SEED_ROW, SEED_PIXEL, SEED_SAMPLE = 0, 1, 2
 ENGINE_WAVEFRONT, ENGINE_MEGAKERNEL, ENGINE_PERSISTENT = 0, 1, 2
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 FLAG_OUT_DEVICE, FLAG_COUNT_VISITS, FLAG_WAIT_STREAM, FLAG_REQUIRE_RCCL = 1, 2, 4, 8
 
 #: tmpt_aov_pixel (include/tmpt.h), one record of :meth:`Scene.trace_aov`, 32 bytes
@@ -177,6 +179,14 @@ _render_radiance = _sig("tmpt_render_radiance", ctypes.c_int, [ctypes.c_void_p, 
 _denoise = _sig("tmpt_denoise", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_DenoiseDesc), ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
 _build_octree = _sig("tmpt_scene_build_octree", ctypes.c_int, [ctypes.c_void_p, _f32p, _f32p])
+
+
+def _scene_update(handle, tris, n, mode):
+    # bound on first use, as tmpt_scene_dump_bvh is: a library from before the entry point still loads
+    fn = _sig("tmpt_scene_update", ctypes.c_int, [ctypes.c_void_p, _f32p, ctypes.c_int32, ctypes.c_int32])
+    return fn(handle, tris, n, mode)
+
+
 _octree_bounds = _sig("tmpt_octree_bounds", ctypes.c_int, [_f32p, _f32p, _f32p])
 _octree_digest = _sig("tmpt_octree_digest", ctypes.c_int, [_f32p, ctypes.c_int32, _f32p, _f32p, _u64p])
 _octree_flags = _sig("tmpt_octree_flags", ctypes.c_int, [_f32p, ctypes.c_int32, _f32p, _f32p, _f32p, _f32p, _i32p,
@@ -201,7 +211,8 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_write_png", "tmpt_last_error", "tmpt_abi_version", "tmpt_unit_sincos",
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
-           "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive")
+           "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
+           "tmpt_scene_update")
 
 
 def _check(rc: int, what: str) -> None:
@@ -467,6 +478,27 @@ class Scene:
         its visit order and to apply its root box test (include/tmpt.h)."""
         lo, hi = np.asarray(box_min, np.float32), np.asarray(box_max, np.float32)
         _check(_build_octree(self._h, _fp(lo), _fp(hi)), "build_octree")
+
+    def update(self, triangles: np.ndarray, mode: str = "refit", bounds=None) -> None:
+        """New triangles for this scene (tmpt_scene_update, include/tmpt.h).
+
+        ``mode="refit"``: the same number of triangles, triangle i in the slot
+        triangle i had; the tree keeps its shape and every record, box and
+        plane is made again on the device.  ``mode="rebuild"``: any number of
+        triangles, the full build with the scene's build options; a failed
+        rebuild raises and leaves the scene as it was.  Both drop the octree:
+        ``bounds=(bmin, bmax)`` builds it again over the new bounds, as the
+        constructor does.  ``get_option("bvh_cost")`` tells how far a refitted
+        tree has degraded, ``get_option("update_ms")`` what the update took."""
+        modes = {"refit": UPDATE_REFIT, "rebuild": UPDATE_REBUILD, UPDATE_REFIT: UPDATE_REFIT,
+                 UPDATE_REBUILD: UPDATE_REBUILD}
+        if mode not in modes:
+            raise ValueError(f"Scene.update: mode is 'refit' or 'rebuild', not {mode!r}")
+        tris = np.ascontiguousarray(np.asarray(triangles, np.float32).reshape(-1, 9))
+        _check(_scene_update(self._h, _fp(tris), tris.shape[0], modes[mode]), f"update({mode})")
+        self.n = tris.shape[0]
+        if bounds is not None:
+            self.build_octree(*octree_bounds(*bounds))
 
     def set_option(self, key: str, value: float) -> None:
         """A render option (include/tmpt.h); applies to the renders after it."""

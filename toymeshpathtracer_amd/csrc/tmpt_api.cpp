@@ -477,6 +477,10 @@ int tmpt_scene_destroy(tmpt_scene* h)
         if (e) (void)hipEventDestroy(e);
     if (s.tri_pre) (void)hipFree(s.tri_pre);
     if (s.tri_orig) (void)hipFree(s.tri_orig);
+    if (s.node_box) (void)hipFree(s.node_box);
+    if (s.rec_box) (void)hipFree(s.rec_box);
+    for (auto e : s.update_ev)
+        if (e) (void)hipEventDestroy(e);
     if (s.ws) (void)hipFree(s.ws);
     for (auto e : s.path_ev)
         if (e) (void)hipEventDestroy(e);
@@ -556,6 +560,123 @@ int tmpt_scene_build_octree(tmpt_scene* h, const float bmin[3], const float bmax
         s.oct_hi[c] = bmax[c];
     }
     s.oct_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+    TMPT_GUARD_END
+}
+
+namespace {
+// the octree dropped, exactly as if none had been built (tmpt_scene_update):
+// the device copies freed, the statistics 0; the records' flat marks are the
+// caller's to clear (a refit and a rebuild both write every record anew)
+void drop_octree(Scene& s)
+{
+    if (s.oct) (void)hipFree(s.oct);
+    if (s.oct_refs) (void)hipFree(s.oct_refs);
+    if (s.oct_view) (void)hipFree(s.oct_view);
+    s.oct = nullptr;
+    s.oct_refs = nullptr;
+    s.oct_view = nullptr;
+    s.n_oct = s.oct_leaves = s.oct_depth = s.oct_flat = 0;
+    s.n_oct_refs = 0;
+    s.oct_grid = OctGrid{};
+    s.oct_build_ms = 0.0;
+    for (int c = 0; c < 3; ++c) s.oct_lo[c] = s.oct_hi[c] = 0.0f;
+}
+}  // namespace
+
+int tmpt_scene_update(tmpt_scene* h, const float* tris, int32_t n, int32_t mode)
+{
+    TMPT_GUARD_BEGIN
+    if (mode != TMPT_UPDATE_REFIT && mode != TMPT_UPDATE_REBUILD)
+        return bad("tmpt_scene_update: mode is TMPT_UPDATE_REFIT (0) or TMPT_UPDATE_REBUILD (1)");
+    if (n < 0) return bad("tmpt_scene_update: n < 0");
+    if (n > 0 && !tris) return bad("tmpt_scene_update: null triangles with n > 0");
+    if (!h) return bad("tmpt_scene_update: null scene");
+    Scene& s = h->s;
+    if (mode == TMPT_UPDATE_REFIT && n != s.n)
+        return bad("tmpt_scene_update: a refit keeps the triangle count (n differs from the scene's); rebuild instead");
+    TMPT_HIP(hipSetDevice(s.device));
+    (void)hipGetLastError();  // a failed call before this one must not fail this one's checks
+    TMPT_HIP(hipStreamSynchronize(s.stream));  // a render in flight may still read the tree
+    for (auto& e : s.update_ev)
+        if (!e) TMPT_HIP(hipEventCreate(&e));
+    const size_t bytes = sizeof(float) * 9 * (size_t)n;
+    float* d_tris = nullptr;
+    if (n > 0) {
+        if (hipMalloc(&d_tris, bytes) != hipSuccess) return (set_error("tmpt_scene_update: out of device memory"), -1);
+    }
+    auto fail = [&](int rc) {
+        if (d_tris) (void)hipFree(d_tris);
+        return rc;
+    };
+    if (hipEventRecord(s.update_ev[0], s.stream) != hipSuccess) return fail((set_error("tmpt_scene_update: event failed"), -1));
+    if (n > 0 && hipMemcpyAsync(d_tris, tris, bytes, hipMemcpyHostToDevice, s.stream) != hipSuccess)
+        return fail((set_error("tmpt_scene_update: upload failed"), -1));
+    if (mode == TMPT_UPDATE_REFIT) {
+        // every record is written anew with its flat mark clear; a failure here is a
+        // HIP error, after which the tree is whatever the launches left
+        if (int rc = refit_bvh(s, d_tris)) return fail(rc);
+    } else {
+        // the full build into fresh allocations, on the scene's stream and with
+        // its build options; swapped in only on success
+        Scene t;
+        t.opt = s.opt;
+        t.device = s.device;
+        t.stream = s.stream;
+        t.n = n;
+        const int rc = build_lbvh(t, d_tris);
+        if (rc) {
+            const std::string why = last_error();
+            (void)hipStreamSynchronize(s.stream);
+            if (t.nodes4) (void)hipFree(t.nodes4);
+            if (t.tri_pre) (void)hipFree(t.tri_pre);
+            if (t.tri_orig) (void)hipFree(t.tri_orig);
+            if (t.node_box) (void)hipFree(t.node_box);
+            if (t.soa_buf) (void)hipFree(t.soa_buf);
+            (void)hipGetLastError();
+            set_error(why);
+            return fail(rc);
+        }
+        if (s.nodes4) (void)hipFree(s.nodes4);
+        if (s.tri_pre) (void)hipFree(s.tri_pre);
+        if (s.tri_orig) (void)hipFree(s.tri_orig);
+        if (s.node_box) (void)hipFree(s.node_box);
+        if (s.rec_box) (void)hipFree(s.rec_box);
+        if (s.soa_buf) (void)hipFree(s.soa_buf);
+        s.rec_box = nullptr;
+        s.n = t.n;
+        s.n_nodes = t.n_nodes;
+        s.max_depth = t.max_depth;
+        s.nodes4 = t.nodes4;
+        s.n_nodes4 = t.n_nodes4;
+        s.depth4 = t.depth4;
+        s.leaf_max = t.leaf_max;
+        s.ploc_iters = t.ploc_iters;
+        s.count_shift = t.count_shift;
+        s.link_bits = t.link_bits;
+        s.tri_pre = t.tri_pre;
+        s.tri_orig = t.tri_orig;
+        s.node_box = t.node_box;
+        s.soa_buf = t.soa_buf;
+        s.soa = t.soa;
+        s.level_begin = std::move(t.level_begin);
+        s.build_ms = t.build_ms;
+    }
+    hipError_t e = hipEventRecord(s.update_ev[1], s.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.update_ev[0], s.update_ev[1]);
+    if (d_tris) (void)hipFree(d_tris);
+    if (e != hipSuccess) {
+        set_error(std::string("tmpt_scene_update: ") + hipGetErrorString(e));
+        return -1;
+    }
+    s.tris_host.assign(tris, tris + 9 * (size_t)n);
+    drop_octree(s);
+    s.prog_key[6] = -1;  // the carried sums belong to the old triangles: spp_begin > 0 fails next
+    s.update_kind = mode == TMPT_UPDATE_REFIT ? 1 : 2;
+    s.update_ms = (double)ms;
+    s.cost_known = false;
     return 0;
     TMPT_GUARD_END
 }
@@ -644,6 +765,24 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
     }
     if (key && strcmp(key, "shadow_split_resolve_ms") == 0) {  // read-only: k_split_resolve's time in that render
         *value = h->s.split_resolve_ms;
+        return 0;
+    }
+    if (key && strcmp(key, "update_kind") == 0) {  // read-only: 0 none since creation, 1 refit, 2 rebuild
+        *value = (double)h->s.update_kind;
+        return 0;
+    }
+    if (key && strcmp(key, "update_ms") == 0) {  // read-only: device time of the last tmpt_scene_update
+        *value = h->s.update_ms;
+        return 0;
+    }
+    if (key && strcmp(key, "bvh_cost") == 0) {  // read-only: the tree's surface-area cost, cached until an update
+        Scene& s = const_cast<tmpt_scene*>(h)->s;
+        if (!s.cost_known) {
+            TMPT_HIP(hipSetDevice(s.device));
+            if (int rc = bvh_cost(s, &s.cost)) return rc;
+            s.cost_known = true;
+        }
+        *value = s.cost;
         return 0;
     }
     return options_get(h->s.opt, key, value);

@@ -59,6 +59,47 @@ struct Soa6 {  // leaf or node boxes, structure of arrays for coalesced sweeps
     float *lx, *ly, *lz, *hx, *hy, *hz;
 };
 
+// One triangle's records from its nine floats, with the roundings the dump's
+// rules state (include/tmpt.h "What every build keeps"): the TriOrig record
+// with its normal, the f32 min / max and the padded box, and the TriPre words
+// v0, e1, e2 (maths.cpp:341-342, same roundings).  k_tri_prep and k_tri_pre
+// (the build) and k_refit_tris (tmpt_scene_update) all go through it.
+struct TriRec {
+    f3 v0, v1, v2, nrm, lo, hi;  // lo / hi: the vertices' min / max, unpadded
+    float box[6];                // the padded box
+};
+__device__ __forceinline__ TriRec tri_rec(const float* __restrict__ t)
+{
+    TriRec r;
+    r.v0 = mk(t[0], t[1], t[2]); r.v1 = mk(t[3], t[4], t[5]); r.v2 = mk(t[6], t[7], t[8]);
+    r.nrm = tri_normal(r.v0, r.v1, r.v2);
+    const f3 lo = vmin(vmin(r.v0, r.v1), r.v2), hi = vmax(vmax(r.v0, r.v1), r.v2);
+    float px = kBoxPadRel * (fmaxf(fabsf(lo.x), fabsf(hi.x)) + (hi.x - lo.x)) + 1e-30f;
+    float py = kBoxPadRel * (fmaxf(fabsf(lo.y), fabsf(hi.y)) + (hi.y - lo.y)) + 1e-30f;
+    float pz = kBoxPadRel * (fmaxf(fabsf(lo.z), fabsf(hi.z)) + (hi.z - lo.z)) + 1e-30f;
+    r.box[0] = lo.x - px; r.box[1] = lo.y - py; r.box[2] = lo.z - pz;
+    r.box[3] = hi.x + px; r.box[4] = hi.y + py; r.box[5] = hi.z + pz;
+    r.lo = lo;
+    r.hi = hi;
+    return r;
+}
+__device__ __forceinline__ void store_orig(TriOrig& o, const TriRec& r)
+{
+    o.a = f4(r.v0.x, r.v0.y, r.v0.z, r.v1.x);
+    o.b = f4(r.v1.y, r.v1.z, r.v2.x, r.v2.y);
+    o.c = f4(r.v2.z, r.nrm.x, r.nrm.y, r.nrm.z);
+}
+// the leaf-ordered record of original triangle o; the flat mark (bit 0 of the doubled index) clear
+__device__ __forceinline__ TriPre pre_rec(const TriRec& r, int o)
+{
+    const f3 e1 = r.v1 - r.v0, e2 = r.v2 - r.v0;
+    TriPre p;
+    p.a = f4(r.v0.x, r.v0.y, r.v0.z, e1.x);
+    p.b = f4(e1.y, e1.z, e2.x, e2.y);
+    p.c = f4(e2.z, __int_as_float(2 * o), 0.0f, 0.0f);  // doubled: TravState::best's tie bit is bit 0
+    return p;
+}
+
 __global__ void __launch_bounds__(kBlock) k_tri_prep(const float* __restrict__ tris9, int32_t n,
                                                      TriOrig* __restrict__ orig, Soa6 box,
                                                      float* __restrict__ cent,
@@ -69,18 +110,11 @@ __global__ void __launch_bounds__(kBlock) k_tri_prep(const float* __restrict__ t
     float c[3] = {INFINITY, INFINITY, INFINITY};
     float cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
     if (i < n) {
-        const float* t = tris9 + 9 * (int64_t)i;
-        f3 v0 = mk(t[0], t[1], t[2]), v1 = mk(t[3], t[4], t[5]), v2 = mk(t[6], t[7], t[8]);
-        f3 nrm = tri_normal(v0, v1, v2);
-        orig[i].a = f4(v0.x, v0.y, v0.z, v1.x);
-        orig[i].b = f4(v1.y, v1.z, v2.x, v2.y);
-        orig[i].c = f4(v2.z, nrm.x, nrm.y, nrm.z);
-        f3 lo = vmin(vmin(v0, v1), v2), hi = vmax(vmax(v0, v1), v2);
-        float px = kBoxPadRel * (fmaxf(fabsf(lo.x), fabsf(hi.x)) + (hi.x - lo.x)) + 1e-30f;
-        float py = kBoxPadRel * (fmaxf(fabsf(lo.y), fabsf(hi.y)) + (hi.y - lo.y)) + 1e-30f;
-        float pz = kBoxPadRel * (fmaxf(fabsf(lo.z), fabsf(hi.z)) + (hi.z - lo.z)) + 1e-30f;
-        box.lx[i] = lo.x - px; box.ly[i] = lo.y - py; box.lz[i] = lo.z - pz;
-        box.hx[i] = hi.x + px; box.hy[i] = hi.y + py; box.hz[i] = hi.z + pz;
+        const TriRec r = tri_rec(tris9 + 9 * (int64_t)i);
+        store_orig(orig[i], r);
+        const f3 lo = r.lo, hi = r.hi;
+        box.lx[i] = r.box[0]; box.ly[i] = r.box[1]; box.lz[i] = r.box[2];
+        box.hx[i] = r.box[3]; box.hy[i] = r.box[4]; box.hz[i] = r.box[5];
         float cx = 0.5f * (lo.x + hi.x), cy = 0.5f * (lo.y + hi.y), cz = 0.5f * (lo.z + hi.z);
         cent[i] = cx; cent[n + i] = cy; cent[2 * n + i] = cz;
         c[0] = cmax[0] = cx; c[1] = cmax[1] = cy; c[2] = cmax[2] = cz;
@@ -556,6 +590,59 @@ __device__ __forceinline__ int sah_expand(const int2* __restrict__ child,
     return no;
 }
 
+// A node's words a, b, c from the exact f32 boxes of its nc children (slots
+// 0..nc-1 valid): origin = their minimum, the least exponent per axis, the
+// planes quantised outward, empty slots inverted (lo 255 > hi 0).  The node's
+// own exact box goes to nbox[0..5] (the refit's input a level up, bvh_cost's
+// root area).  The collapse (k_bvh4_level) and the refit (k_refit_level4) both
+// encode through it, so a refit of unchanged triangles gives the built words.
+struct NodeWords {
+    float4 a;
+    uint4 b, c;
+};
+__device__ __forceinline__ NodeWords encode_node(const float (*bx)[6], int nc, float* __restrict__ nbox)
+{
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int k = 0; k < nc; ++k) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], bx[k][a]);
+            hi[a] = fmaxf(hi[a], bx[k][3 + a]);
+        }
+    }
+    uint32_t ebits = 0, mask = 0;
+    uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
+    double scale[3];
+    for (int a = 0; a < 3; ++a) {
+        double ext = (double)hi[a] - (double)lo[a];
+        int e = (int)ceil(log2(fmax(ext, 1e-30) / 255.0));
+        e = max(-126, min(127, e));
+        scale[a] = ldexp(1.0, e);
+        ebits |= ((uint32_t)e & 0xFFu) << (8 * a);  // signed byte: scale = 2^e (ldexp in the traversal)
+    }
+    for (int k = nc; k < 4; ++k)
+        for (int a = 0; a < 3; ++a) qlo[a] |= 255u << (8 * k);
+    for (int k = 0; k < nc; ++k) {
+        for (int a = 0; a < 3; ++a) {
+            double l = floor(((double)bx[k][a] - (double)lo[a]) / scale[a]);
+            double h = ceil(((double)bx[k][3 + a] - (double)lo[a]) / scale[a]);
+            uint32_t ql = (uint32_t)fmin(fmax(l, 0.0), 255.0);
+            uint32_t qh = (uint32_t)fmin(fmax(h, 0.0), 255.0);
+            qlo[a] |= ql << (8 * k);
+            qhi[a] |= qh << (8 * k);
+        }
+        mask |= 1u << k;
+    }
+    for (int a = 0; a < 3; ++a) {
+        nbox[a] = lo[a];
+        nbox[3 + a] = hi[a];
+    }
+    NodeWords w;
+    w.a = f4(lo[0], lo[1], lo[2], __uint_as_float(ebits | (mask << 24)));
+    w.b = make_uint4(qlo[0], qhi[0], qlo[1], qhi[1]);
+    w.c = make_uint4(qlo[2], qhi[2], 0u, 0u);
+    return w;
+}
+
 // One level of the top-down BVH2 -> BVH4Q collapse.  Each frontier entry
 // (BVH2 node, BVH4 slot) takes up to 4 children by repeatedly opening the
 // largest-area internal child; a BVH2 subtree of <= leaf_max triangles becomes
@@ -569,7 +656,7 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
                                                        uint32_t* __restrict__ counters,
                                                        Bvh4Node* __restrict__ out, int leaf_max,
                                                        int n_tris, const uint32_t* __restrict__ dec,
-                                                       int count_shift)
+                                                       int count_shift, float* __restrict__ nbox)
 {
     int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nf) return;
@@ -610,41 +697,14 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
         }
     }
     float bx[4][6];
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = 0; k < nc; ++k) {
-        node_or_leaf_box(cand[k], leaf, vals, ib, bx[k]);
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], bx[k][a]);
-            hi[a] = fmaxf(hi[a], bx[k][3 + a]);
-        }
-    }
-    uint32_t ebits = 0, mask = 0;
-    uint32_t qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-    double scale[3];
-    for (int a = 0; a < 3; ++a) {
-        double ext = (double)hi[a] - (double)lo[a];
-        int e = (int)ceil(log2(fmax(ext, 1e-30) / 255.0));
-        e = max(-126, min(127, e));
-        scale[a] = ldexp(1.0, e);
-        ebits |= ((uint32_t)e & 0xFFu) << (8 * a);  // signed byte: scale = 2^e (ldexp in the traversal)
-    }
-    // empty slots: inverted quantised box (lo 255 > hi 0) and a link to the null
-    // leaf, so a step that does not consult the mask still finds nothing there
+    for (int k = 0; k < nc; ++k) node_or_leaf_box(cand[k], leaf, vals, ib, bx[k]);
+    const NodeWords nw = encode_node(bx, nc, nbox + 6 * (size_t)dst);
+    // empty slots link to the null leaf, so a step that does not consult the
+    // mask still finds nothing there
     const int null_leaf = (int)leaf_link(1u, (uint32_t)n_tris, count_shift);
     int4 links = make_int4(null_leaf, null_leaf, null_leaf, null_leaf);
     int* lk = &links.x;
-    for (int k = nc; k < 4; ++k)
-        for (int a = 0; a < 3; ++a) qlo[a] |= 255u << (8 * k);
     for (int k = 0; k < nc; ++k) {
-        for (int a = 0; a < 3; ++a) {
-            double l = floor(((double)bx[k][a] - (double)lo[a]) / scale[a]);
-            double h = ceil(((double)bx[k][3 + a] - (double)lo[a]) / scale[a]);
-            uint32_t ql = (uint32_t)fmin(fmax(l, 0.0), 255.0);
-            uint32_t qh = (uint32_t)fmin(fmax(h, 0.0), 255.0);
-            qlo[a] |= ql << (8 * k);
-            qhi[a] |= qh << (8 * k);
-        }
-        mask |= 1u << k;
         int c = cand[k];
         if (c < 0) {  // BVH2 leaf: one triangle at sorted slot ~c
             lk[k] = (int)leaf_link(1u, (uint32_t)(~c), count_shift);
@@ -657,9 +717,9 @@ __global__ void __launch_bounds__(kBlock) k_bvh4_level(const int2* __restrict__ 
             lk[k] = (int)slot;
         }
     }
-    out[dst].a = f4(lo[0], lo[1], lo[2], __uint_as_float(ebits | (mask << 24)));
-    out[dst].b = make_uint4(qlo[0], qhi[0], qlo[1], qhi[1]);
-    out[dst].c = make_uint4(qlo[2], qhi[2], 0u, 0u);
+    out[dst].a = nw.a;
+    out[dst].b = nw.b;
+    out[dst].c = nw.c;
     out[dst].d = links;
 }
 
@@ -670,12 +730,7 @@ __global__ void __launch_bounds__(kBlock) k_tri_pre(const float* __restrict__ tr
     int k = blockIdx.x * kBlock + threadIdx.x;
     if (k >= n) return;
     int o = (int)vals[k];
-    const float* t = tris9 + 9 * (int64_t)o;
-    f3 v0 = mk(t[0], t[1], t[2]), v1 = mk(t[3], t[4], t[5]), v2 = mk(t[6], t[7], t[8]);
-    f3 e1 = v1 - v0, e2 = v2 - v0;  // maths.cpp:341-342, same roundings
-    pre[k].a = f4(v0.x, v0.y, v0.z, e1.x);
-    pre[k].b = f4(e1.y, e1.z, e2.x, e2.y);
-    pre[k].c = f4(e2.z, __int_as_float(2 * o), 0.0f, 0.0f);  // doubled: TravState::best's tie bit is bit 0
+    pre[k] = pre_rec(tri_rec(tris9 + 9 * (int64_t)o), o);
 }
 
 inline int blocks_for(int64_t n, int b) { return (int)((n + b - 1) / b); }
@@ -717,7 +772,179 @@ __global__ void __launch_bounds__(kBlock) k_mark_flat(TriPre* __restrict__ pre, 
     if (tc) tc[k].y = __int_as_float(v);
 }
 
+// ---------------------------------------------------------------- refit (tmpt_scene_update)
+// The built tree fitted to new triangles in their old slots: links, masks,
+// leaf ranges and the records' order stay; every record, box and plane is
+// made again by the build's own expressions (tri_rec, encode_node).
+//
+// One thread per leaf-ordered record k: its original index o = word [9] >> 1,
+// the records of triangle o (TriPre k with the flat mark clear, TriOrig o) and
+// the padded box of record k (rbox: 6 floats per record).
+__global__ void __launch_bounds__(kBlock) k_refit_tris(const float* __restrict__ tris9, int32_t n,
+                                                       TriPre* __restrict__ pre, TriOrig* __restrict__ orig,
+                                                       float* __restrict__ rbox, float4* __restrict__ ta,
+                                                       float4* __restrict__ tb, float2* __restrict__ tc)
+{
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    const int o = __float_as_int(pre[k].c.y) >> 1;
+    if (o < 0 || o >= n) return;  // no built record names a triangle outside [0, n)
+    const TriRec r = tri_rec(tris9 + 9 * (int64_t)o);
+    const TriPre p = pre_rec(r, o);
+    pre[k] = p;
+    store_orig(orig[o], r);
+    for (int a = 0; a < 6; ++a) rbox[6 * (size_t)k + a] = r.box[a];
+    if (ta) {  // layout=soa: the planes in place
+        ta[k] = p.a;
+        tb[k] = p.b;
+        tc[k] = make_float2(p.c.x, p.c.y);
+    }
+}
+
+// The nodes [begin, end) of one BVH4 level, after every deeper level: a valid
+// slot's box is the min / max over the record boxes of its leaf range, or the
+// stored exact box of its internal child (nbox, written by the child's own
+// launch: the kernel boundary is the only synchronisation, as in the build).
+__global__ void __launch_bounds__(kBlock) k_refit_level4(Bvh4Node* __restrict__ nodes, int32_t begin, int32_t end,
+                                                        int32_t n, int32_t n4, const float* __restrict__ rbox,
+                                                        float* __restrict__ nbox, int count_shift,
+                                                        uint4* __restrict__ na, uint4* __restrict__ nb,
+                                                        uint2* __restrict__ ncp)
+{
+    const int i = begin + blockIdx.x * kBlock + threadIdx.x;
+    if (i >= end) return;
+    const uint32_t mask = __float_as_uint(nodes[i].a.w) >> 24;
+    const int4 links = nodes[i].d;
+    const int* lk = &links.x;
+    const int nc = __popc(mask & 15u);  // valid children fill slots 0..nc-1
+    float bx[4][6];
+    for (int k = 0; k < nc; ++k) {
+        const uint32_t l = (uint32_t)lk[k];
+        if (l & 0x80000000u) {
+            const uint32_t first = leaf_first(l, count_shift);
+            uint32_t last = first + leaf_count(l, count_shift);
+            last = last < (uint32_t)n ? last : (uint32_t)n;
+            for (int a = 0; a < 3; ++a) {
+                bx[k][a] = INFINITY;
+                bx[k][3 + a] = -INFINITY;
+            }
+            for (uint32_t t = first; t < last; ++t) {
+                for (int a = 0; a < 3; ++a) {
+                    bx[k][a] = fminf(bx[k][a], rbox[6 * (size_t)t + a]);
+                    bx[k][3 + a] = fmaxf(bx[k][3 + a], rbox[6 * (size_t)t + 3 + a]);
+                }
+            }
+        } else {
+            const uint32_t c = l < (uint32_t)n4 ? l : (uint32_t)i;  // a child's index exceeds its parent's
+            for (int a = 0; a < 6; ++a) bx[k][a] = nbox[6 * (size_t)c + a];
+        }
+    }
+    const NodeWords w = encode_node(bx, nc, nbox + 6 * (size_t)i);
+    nodes[i].a = w.a;
+    nodes[i].b = w.b;
+    nodes[i].c = w.c;
+    if (na) {
+        na[i] = make_uint4(__float_as_uint(w.a.x), __float_as_uint(w.a.y), __float_as_uint(w.a.z),
+                           __float_as_uint(w.a.w));
+        nb[i] = w.b;
+        ncp[i] = make_uint2(w.c.x, w.c.y);
+    }
+}
+
+// bvh_cost: per block, the float64 sum over its nodes' valid slots of the
+// decoded box's half area x (1 for a node, the triangle count for a leaf)
+__global__ void __launch_bounds__(kBlock) k_bvh_cost(const Bvh4Node* __restrict__ nodes, int32_t n4,
+                                                     int count_shift, double* __restrict__ partial)
+{
+    __shared__ double red[kBlock];
+    double sum = 0.0;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n4; i += gridDim.x * kBlock) {
+        const Bvh4Node v = nodes[i];
+        const uint32_t w = __float_as_uint(v.a.w);
+        const uint32_t pl[6] = {v.b.x, v.b.y, v.b.z, v.b.w, v.c.x, v.c.y};
+        const double org[3] = {(double)v.a.x, (double)v.a.y, (double)v.a.z};
+        double sc[3];
+        for (int a = 0; a < 3; ++a) sc[a] = ldexp(1.0, (int)(int8_t)((w >> (8 * a)) & 255u));
+        const int* lk = &v.d.x;
+        for (int k = 0; k < 4; ++k) {
+            if (!((w >> (24 + k)) & 1u)) continue;
+            double e[3];
+            for (int a = 0; a < 3; ++a) {
+                const double lo = org[a] + (double)((pl[2 * a] >> (8 * k)) & 255u) * sc[a];
+                const double hi = org[a] + (double)((pl[2 * a + 1] >> (8 * k)) & 255u) * sc[a];
+                e[a] = hi - lo;
+            }
+            const uint32_t l = (uint32_t)lk[k];
+            const double weight = (l & 0x80000000u) ? (double)leaf_count(l, count_shift) : 1.0;
+            sum += (e[0] * e[1] + e[1] * e[2] + e[2] * e[0]) * weight;
+        }
+    }
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
 }  // namespace
+
+// tmpt_scene_update, mode refit: d_tris9 holds the scene's n new triangles.
+// All on the scene's stream, no host synchronisation between the launches.
+int refit_bvh(Scene& s, const float* d_tris9)
+{
+    const int32_t n = s.n;
+    if (n <= 0) return 0;
+    hipStream_t st = s.stream;
+    if ((int)s.level_begin.size() != s.depth4 + 1 || !s.node_box) {
+        set_error("tmpt_scene_update: the scene has no level ranges to refit over");
+        return -1;
+    }
+    if (!s.rec_box) TMPT_HIP(hipMalloc(&s.rec_box, 6 * sizeof(float) * (size_t)n));
+    k_refit_tris<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, s.tri_pre, s.tri_orig, s.rec_box,
+                                                           const_cast<float4*>(s.soa.ta),
+                                                           const_cast<float4*>(s.soa.tb),
+                                                           const_cast<float2*>(s.soa.tc));
+    for (int L = s.depth4 - 1; L >= 0; --L) {  // deepest level first
+        const int32_t b = s.level_begin[L], e = s.level_begin[L + 1];
+        if (e <= b) continue;
+        k_refit_level4<<<blocks_for(e - b, kBlock), kBlock, 0, st>>>(s.nodes4, b, e, n, s.n_nodes4, s.rec_box,
+                                                                    s.node_box, s.count_shift,
+                                                                    const_cast<uint4*>(s.soa.na),
+                                                                    const_cast<uint4*>(s.soa.nb),
+                                                                    const_cast<uint2*>(s.soa.nc));
+    }
+    TMPT_HIP(hipGetLastError());
+    return 0;
+}
+
+// Option bvh_cost: tests/bvh_check.py cost() on the device -- the slots' sum
+// over the root box's half area (the root's exact box: node_box[0..5]).
+int bvh_cost(Scene& s, double* out)
+{
+    *out = 0.0;
+    if (s.n <= 0 || s.n_nodes4 <= 0) return 0;
+    const int nb = std::min(blocks_for(s.n_nodes4, kBlock), 256);
+    double* d_part = nullptr;
+    TMPT_HIP(hipMalloc(&d_part, sizeof(double) * (size_t)nb));
+    std::vector<double> part((size_t)nb);
+    float root[6];
+    k_bvh_cost<<<nb, kBlock, 0, s.stream>>>(s.nodes4, s.n_nodes4, s.count_shift, d_part);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(root, s.node_box, sizeof(root), hipMemcpyDeviceToHost, s.stream);
+    const hipError_t e2 = hipStreamSynchronize(s.stream);
+    (void)hipFree(d_part);
+    TMPT_HIP(e);
+    TMPT_HIP(e2);
+    double sum = 0.0;
+    for (double p : part) sum += p;
+    const double r[3] = {(double)root[3] - (double)root[0], (double)root[4] - (double)root[1],
+                         (double)root[5] - (double)root[2]};
+    *out = sum / (r[0] * r[1] + r[1] * r[2] + r[2] * r[0]);
+    return 0;
+}
 
 int mark_flat_triangles(Scene& s, const std::vector<uint8_t>& flat)
 {
@@ -902,14 +1129,18 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
         hipMemcpyAsync(c4, hc, sizeof(hc), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
     int nf = 1, levels = 0;
     int2 *fa = fr0, *fb = fr1;
+    // level L's nodes are [level_begin[L], level_begin[L + 1]): the running node
+    // count after every launch (the refit runs one launch per range, deepest first)
+    s.level_begin.assign({0, 1});
     while (nf > 0) {
         k_bvh4_level<<<blocks_for(nf, kBlock), kBlock, 0, st>>>(tchild, trange, leaf, tvals, tib, fa, nf,
                                                                 fb, c4, s.nodes4, leaf_max, n, dec,
-                                                                ll.count_shift);
+                                                                ll.count_shift, s.node_box);
         ++levels;
         if (hipMemcpyAsync(hc, c4, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) return -1;
         nf = (int)hc[1];
+        if (nf > 0) s.level_begin.push_back((int32_t)hc[0]);
         hc[1] = 0;
         if (hipMemcpyAsync(c4 + 1, &hc[1], 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
         std::swap(fa, fb);
@@ -935,6 +1166,10 @@ int build_lbvh(Scene& s, const float* d_tris9)
     TMPT_HIP(hipMalloc(&s.tri_pre, sizeof(TriPre) * ((size_t)n + 1)));
     TMPT_HIP(hipMemsetAsync(s.tri_pre + n, 0, sizeof(TriPre), st));
     TMPT_HIP(hipMalloc(&s.tri_orig, sizeof(TriOrig) * (size_t)std::max(n, 1)));
+    // every node's own exact f32 box (24 B): what a refit reads of an internal
+    // child, and bvh_cost's root area
+    TMPT_HIP(hipMalloc(&s.node_box, 6 * sizeof(float) * (size_t)m));
+    s.level_begin.clear();
     if (n == 0) {
         TMPT_HIP(hipMemsetAsync(s.nodes4, 0, sizeof(Bvh4Node), st));
         s.max_depth = 0;

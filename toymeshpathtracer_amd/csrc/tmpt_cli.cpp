@@ -1,7 +1,7 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
-//        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
+//        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png] [--twist DEG,FRAMES [--rebuild]]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -19,6 +19,12 @@
 // too; RADIUS 0..8, left out = 0: the neighbourhood rule -- a pixel goes on while the test holds for
 // any pixel within RADIUS columns and rows of it, the whole frame being one band); --spp-map OUT.png writes the samples each pixel got, n_p / spp, as grey.  With --denoise
 // the filter takes the adaptive radiance; the AOV pass stays at spp.
+// --twist DEG,FRAMES [--rebuild] (one device): an animation on one scene handle.  Frame f renders the
+// mesh, floor included, twisted about the vertical (y) axis through the centre of its bounds by
+// DEG * f / (FRAMES - 1) at the top and nothing at the bottom; each frame is one tmpt_scene_update
+// (a refit; --rebuild: the full build) and the octree built again over the twisted mesh's bounds, the
+// camera staying frame 0's.  The frames go to OUT_000.png, OUT_001.png, ... (OUT: --out less its
+// .png); per frame the update's device time and the tree's bvh_cost are printed.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -182,14 +188,73 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
     return rc;
 }
 
+// --twist: see the head of this file.  tris: the n triangles of tmpt_load_obj (the last two are the floor).
+static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, const tmpt_render_desc* desc, int device,
+                        double degrees, int frames, bool rebuild, const char* out)
+{
+    tmpt_scene* scene = nullptr;
+    if (tmpt_scene_create(tris, n, device, &scene)) return 1;
+    const int w = desc->width, h = desc->height;
+    std::vector<uint8_t> image((size_t)w * h * 4, 0);
+    std::vector<float> cur((size_t)n * 9);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        for (int c = 0; c < 3; ++c) {
+            lo[c] = fmin(lo[c], (double)tris[3 * i + c]);
+            hi[c] = fmax(hi[c], (double)tris[3 * i + c]);
+        }
+    const double cx = 0.5 * (lo[0] + hi[0]), cz = 0.5 * (lo[2] + hi[2]), height = hi[1] - lo[1];
+    std::string stem(out);
+    if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".png") == 0) stem.resize(stem.size() - 4);
+    int rc = 0;
+    for (int f = 0; f < frames && !rc; ++f) {
+        const double full = degrees * (frames > 1 ? (double)f / (frames - 1) : 1.0) * 3.14159265358979323846 / 180.0;
+        float bmin[3] = {INFINITY, INFINITY, INFINITY}, bmax[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (size_t i = 0; i < (size_t)n * 3; ++i) {
+            const double x = tris[3 * i] - cx, y = tris[3 * i + 1], z = tris[3 * i + 2] - cz;
+            const double a = height > 0.0 ? full * (y - lo[1]) / height : 0.0;
+            cur[3 * i] = (float)(cx + cos(a) * x + sin(a) * z);
+            cur[3 * i + 1] = tris[3 * i + 1];
+            cur[3 * i + 2] = (float)(cz - sin(a) * x + cos(a) * z);
+            if (i + 6 < (size_t)n * 3 || n <= 2)  // the mesh's bounds: the two floor triangles come last
+                for (int c = 0; c < 3; ++c) {
+                    bmin[c] = fminf(bmin[c], cur[3 * i + c]);
+                    bmax[c] = fmaxf(bmax[c], cur[3 * i + c]);
+                }
+        }
+        float box[6];
+        double ms = 0.0, cost = 0.0;
+        uint64_t rays = 0;
+        tmpt_stats st;
+        rc = tmpt_scene_update(scene, cur.data(), n, rebuild ? TMPT_UPDATE_REBUILD : TMPT_UPDATE_REFIT);
+        if (!rc) rc = tmpt_octree_bounds(bmin, bmax, box);
+        if (!rc) rc = tmpt_scene_build_octree(scene, box, box + 3);
+        if (!rc) rc = tmpt_scene_get_option(scene, "update_ms", &ms);
+        if (!rc) rc = tmpt_scene_get_option(scene, "bvh_cost", &cost);
+        if (!rc) rc = tmpt_render(scene, cam, desc, image.data(), &rays);
+        if (!rc) rc = tmpt_get_stats(scene, &st);
+        if (rc) break;
+        char name[32];
+        snprintf(name, sizeof(name), "_%03d.png", f);
+        printf("frame %d: twist %.2f deg, %s %.3f ms, bvh_cost %.3f, %.1f K Rays in %.3f ms\n", f,
+               full * 180.0 / 3.14159265358979323846, rebuild ? "rebuild" : "refit", ms, cost, rays / 1000.0, st.render_ms);
+        rc = tmpt_write_png((stem + name).c_str(), image.data(), w, h);
+    }
+    if (tmpt_scene_destroy(scene) && !rc) rc = 1;
+    return rc;
+}
+
 int main(int argc, const char** argv)
 {
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
-               "[--denoise file.png] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png]\n"
+               "[--denoise file.png] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
+               "[--twist deg,frames [--rebuild]]\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
-               "any pixel within radius columns and rows of it\n");
+               "any pixel within radius columns and rows of it\n"
+               "  --twist: frames of the mesh twisted about y by up to deg on one scene, each a tmpt_scene_update "
+               "(a refit; --rebuild: a full build), to <out>_000.png ...\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -204,7 +269,9 @@ int main(int argc, const char** argv)
     const char* aov = nullptr;
     const char* denoised = nullptr;
     const char* spp_map = nullptr;
-    bool adaptive = false;
+    bool adaptive = false, twist = false, rebuild = false;
+    double twist_deg = 0.0;
+    int twist_frames = 0;
     tmpt_adaptive_desc ad;
     memset(&ad, 0, sizeof(ad));
     for (int i = 5; i < argc; ++i) {
@@ -237,6 +304,14 @@ int main(int argc, const char** argv)
             ad.spp_step = stp;
             ad.radius = rad;
         }
+        else if (!strcmp(argv[i], "--twist") && i + 1 < argc) {
+            if (sscanf(argv[++i], "%lf,%d", &twist_deg, &twist_frames) != 2 || twist_frames < 1 || twist_frames > 1000) {
+                printf("ERROR: invalid --twist argument '%s' (DEG,FRAMES with 1 <= FRAMES <= 1000)\n", argv[i]);
+                return 1;
+            }
+            twist = true;
+        }
+        else if (!strcmp(argv[i], "--rebuild")) rebuild = true;
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -258,6 +333,11 @@ int main(int argc, const char** argv)
         return 1;
     }
     if (spp_map && !adaptive) { printf("ERROR: --spp-map needs --adaptive\n"); return 1; }
+    if (rebuild && !twist) { printf("ERROR: --rebuild needs --twist\n"); return 1; }
+    if (twist && (gpus > 1 || adaptive || aov || denoised)) {
+        printf("ERROR: --twist runs on one device (--gpus 1), without --adaptive, --aov and --denoise\n");
+        return 1;
+    }
     int ndev = tmpt_device_count();
     if (device + gpus > ndev) {
         printf("ERROR: %d GPU(s) requested from device %d, %d present\n", gpus, device, ndev);
@@ -279,6 +359,14 @@ int main(int argc, const char** argv)
     // BuildOctree(sceneMin - extra, sceneMax + extra), main.cpp:296-297, 312
     float box[6];
     tmpt_octree_bounds(bmin, bmax, box);
+    if (twist) {  // the frames of one scene handle, each written by render_twist
+        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, out)) {
+            printf("ERROR: %s\n", tmpt_last_error());
+            return 1;
+        }
+        tmpt_free(tris);
+        return 0;
+    }
     if (adaptive) {  // the frame, the spp map and the denoised frame from one adaptive call
         if (render_adaptive_frame(tris, n, box, &cam, w, h, spp, device, &ad, image, spp_map, denoised)) {
             printf("ERROR: %s\n", tmpt_last_error());

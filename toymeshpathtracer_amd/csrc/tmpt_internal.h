@@ -401,6 +401,20 @@ struct Scene {
     void* soa_buf = nullptr;  // layout=soa: the planes of SoaScene, one allocation
     SoaScene soa;
     std::vector<float> tris_host;  // the triangles as given (Scene::Scene keeps its copy too)
+    // scene updates (tmpt_scene_update): BVH4 level L is nodes [level_begin[L],
+    // level_begin[L + 1]) (depth4 + 1 entries); every node's own exact f32 box
+    // (6 floats per node, written by the build and by every refit); the padded
+    // box of every leaf-ordered record (6 floats, a refit's scratch, allocated
+    // by the first one); the last update's kind (0 none, 1 refit, 2 rebuild) and
+    // device time; option bvh_cost's cached value (valid: cost_known)
+    std::vector<int32_t> level_begin;
+    float* node_box = nullptr;
+    float* rec_box = nullptr;
+    int32_t update_kind = 0;
+    double update_ms = 0.0;
+    double cost = 0.0;
+    bool cost_known = false;
+    hipEvent_t update_ev[2] = {nullptr, nullptr};
     // the reference's octree (tmpt_scene_build_octree), and the counter of
     // closest-hit queries answered through it in the current call
     OctNode* oct = nullptr;
@@ -537,6 +551,11 @@ const char* last_error();
 // tmpt_bvh.hip
 int build_lbvh(Scene& s, const float* d_tris9);
 int build_soa(Scene& s);  // layout=soa planes from the built AoS records
+// tmpt_scene_update's refit: the built tree fitted to the scene's n new
+// triangles (device, 9 floats each), launched on the scene's stream; and
+// option bvh_cost, tests/bvh_check.py cost() by a float64 reduction kernel
+int refit_bvh(Scene& s, const float* d_tris9);
+int bvh_cost(Scene& s, double* out);
 // the octree's flat triangles marked in the leaf-ordered records (bit 0 of the
 // doubled index), the others cleared; flat has s.n entries (empty: clear all)
 int mark_flat_triangles(Scene& s, const std::vector<uint8_t>& flat);
