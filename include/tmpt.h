@@ -55,7 +55,8 @@ extern "C" {
                               0 = the rule as it was;
                               still 9, additive: tmpt_scene_update (a device BVH refit, or a rebuild, of a
                               scene in place) and the read-only options update_kind, update_ms and
-                              bvh_cost -- no struct above changed */
+                              bvh_cost -- no struct above changed;
+                              still 9, additive: the read-only option live_device_objects */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -405,6 +406,10 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    reduction kernel and kept until the next update; 0 for the empty scene.  It
  *                    tells when a refitted tree has degraded enough to rebuild; the library applies
  *                    no policy of its own
+ *   live_device_objects  read-only, of the process, not of the scene: the device allocations, pinned
+ *                    allocations, events and streams the library holds at this moment, over every
+ *                    scene and call (csrc/tmpt_device.h); it returns to its earlier value when a
+ *                    scene is destroyed, and a call repeated with the same arguments does not move it
  *   pop_key_cap      test hook (-1 = no cap): at most this many key bits (0..16; 0..8 give no key)
  *   redo_cap        test hook (0 = auto): the capacity of tie_defer's sample list; a
  *                    frame that overflows it is rendered again with the list grown

@@ -322,19 +322,12 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
         const uint32_t wpr = ((uint32_t)a.W + 63u) / 64u, nwords = wpr * (uint32_t)a.tile_rows;
         const size_t o_own = o_total + 256, o_bits = o_own + align256(slots), o_dil = o_bits + align256(8 * (size_t)nwords);
         const size_t need = radius > 0 ? o_dil + align256(8 * (size_t)nwords) : o_total + 256;
-        if (s.adapt_bytes < need) {
-            if (s.adapt_buf) (void)hipFree(s.adapt_buf);
-            s.adapt_buf = nullptr;
-            s.adapt_bytes = 0;
-            if (hipMalloc(&s.adapt_buf, need) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("tmpt_render_adaptive: out of device memory (the per-pixel state and lists)");
-                return -12;
-            }
-            s.adapt_bytes = need;
+        if (!s.adapt_buf.reserve(need)) {
+            set_error("tmpt_render_adaptive: out of device memory (the per-pixel state and lists)");
+            return -12;
         }
-        if (!s.adapt_host) TMPT_HIP(hipHostMalloc((void**)&s.adapt_host, 64, hipHostMallocDefault));
-        char* base = static_cast<char*>(s.adapt_buf);
+        TMPT_HIP(s.adapt_host.ensure(64));
+        char* base = s.adapt_buf.as<char>();
         AdaptState* state = reinterpret_cast<AdaptState*>(base);
         uint32_t* lists[2] = {reinterpret_cast<uint32_t*>(base + o_list0), reinterpret_cast<uint32_t*>(base + o_list1)};
         uint64_t* mask = reinterpret_cast<uint64_t*>(base + o_mask);

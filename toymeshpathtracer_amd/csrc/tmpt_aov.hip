@@ -166,7 +166,7 @@ static int launch_aov(Scene& s, const RenderArgs& a, tmpt_aov_pixel* d_out)
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(resident, (a.slots * G + kBlk - 1) / kBlk));
     const size_t ovf_bytes = (size_t)grid * kBlk * (kStackTotal - kSL) * sizeof(uint32_t);
     if (ensure_ws(s, ovf_bytes)) return -1;
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a, reinterpret_cast<float4*>(d_out), (uint32_t*)s.ws, s.counters);
+    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a, reinterpret_cast<float4*>(d_out), s.ws.as<uint32_t>(), s.counters);
     TMPT_HIP(hipGetLastError());
     return 0;
 }

@@ -305,12 +305,11 @@ int tmpt_unit_sincos(int32_t device, uint32_t key0, uint32_t n, float* out)
     TMPT_HIP(hipGetDeviceCount(&ndev));
     if (device >= ndev) return bad("tmpt_unit_sincos: no such device");
     TMPT_HIP(hipSetDevice(device));
-    float2* d = nullptr;
-    TMPT_HIP(hipMalloc(&d, sizeof(float2) * (size_t)n));
-    k_unit_sincos<<<(n + 255u) / 256u, 256>>>(key0, n, d);
+    DeviceBuffer<float2> d;
+    TMPT_ALLOC(d.alloc(sizeof(float2) * (size_t)n), "tmpt_unit_sincos");
+    k_unit_sincos<<<(n + 255u) / 256u, 256>>>(key0, n, d.get());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, d, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) {
         set_error(std::string("tmpt_unit_sincos: ") + hipGetErrorString(e));
         return -1;
@@ -407,26 +406,23 @@ int tmpt_scene_create_ex(const float* tris, int32_t n, int32_t device, const cha
     Scene& s = h->s;
     s.opt = opt;
     s.device = device;
-    s.n = n;
+    s.bvh.n = n;
     auto fail = [&](int rc) {
         tmpt_scene_destroy(h);
         return rc;
     };
-    if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess)
-        return fail((set_error("hipStreamCreate failed"), -1));
-    float* d_tris = nullptr;
+    if (s.stream.ensure(hipStreamNonBlocking) != hipSuccess) return fail((set_error("tmpt_scene_create: no stream"), -1));
+    DeviceBuffer<float> d_tris;
     if (n > 0) {
-        if (hipMalloc(&d_tris, sizeof(float) * 9 * (size_t)n) != hipSuccess)
+        if (!d_tris.alloc(sizeof(float) * 9 * (size_t)n))
             return fail((set_error("tmpt_scene_create: out of device memory"), -1));
-        if (hipMemcpy(d_tris, tris, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d_tris);
+        if (hipMemcpy(d_tris, tris, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
             return fail((set_error("tmpt_scene_create: upload failed"), -1));
-        }
     }
     // Scene::Scene's copy (scene.cpp:54-57): the octree's input, and the split references'
     s.tris_host.assign(tris, tris + 9 * (size_t)n);
-    int rc = build_lbvh(s, d_tris);
-    if (d_tris) (void)hipFree(d_tris);
+    const int rc = build_lbvh(s.bvh, s.opt, s.stream, d_tris);
+    d_tris.reset();
     if (rc) return fail(rc);
     *out = h;
     return 0;
@@ -441,50 +437,6 @@ int tmpt_scene_destroy(tmpt_scene* h)
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     for (auto& st : s.rs_stream)  // the speculative row engine's group streams
         if (st) (void)hipStreamSynchronize(st);
-    if (s.nodes4) (void)hipFree(s.nodes4);
-    if (s.oct) (void)hipFree(s.oct);
-    if (s.oct_refs) (void)hipFree(s.oct_refs);
-    if (s.oct_view) (void)hipFree(s.oct_view);
-    if (s.soa_buf) (void)hipFree(s.soa_buf);
-    if (s.prog) (void)hipFree(s.prog);
-    if (s.jt) (void)hipFree(s.jt);
-    if (s.sbuf) (void)hipFree(s.sbuf);
-    if (s.cam_rays) (void)hipFree(s.cam_rays);
-    if (s.split_buf) (void)hipFree(s.split_buf);
-    if (s.split_carry) (void)hipFree(s.split_carry);
-    for (auto& e : s.split_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s.adapt_buf) (void)hipFree(s.adapt_buf);
-    if (s.adapt_host) (void)hipHostFree(s.adapt_host);
-    if (s.redo) (void)hipFree(s.redo);
-    if (s.redo_state) (void)hipFree(s.redo_state);
-    if (s.jt2) (void)hipFree(s.jt2);
-    if (s.rs_buf) (void)hipFree(s.rs_buf);
-    for (auto& st : s.rs_stream)
-        if (st) (void)hipStreamDestroy(st);
-    for (auto& ev : s.rs_event)
-        if (ev) (void)hipEventDestroy(ev);
-    if (s.rs_host) (void)hipHostFree(s.rs_host);
-    if (s.rs_list) (void)hipFree(s.rs_list);
-    if (s.rss_buf) (void)hipFree(s.rss_buf);
-    if (s.rss_tab) (void)hipFree(s.rss_tab);
-    if (s.rss_host) (void)hipHostFree(s.rss_host);
-    if (s.wait_ev) (void)hipEventDestroy(s.wait_ev);
-    if (s.counters) (void)hipFree(s.counters);
-    if (s.chk) (void)hipFree(s.chk);
-    if (s.counters_host) (void)hipHostFree(s.counters_host);
-    for (auto e : s.render_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s.tri_pre) (void)hipFree(s.tri_pre);
-    if (s.tri_orig) (void)hipFree(s.tri_orig);
-    if (s.node_box) (void)hipFree(s.node_box);
-    if (s.rec_box) (void)hipFree(s.rec_box);
-    for (auto e : s.update_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s.ws) (void)hipFree(s.ws);
-    for (auto e : s.path_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
     delete h;
     return 0;
 }
@@ -494,95 +446,50 @@ int tmpt_scene_build_octree(tmpt_scene* h, const float bmin[3], const float bmax
     TMPT_GUARD_BEGIN
     if (!h || !bmin || !bmax) return bad("tmpt_scene_build_octree: null argument");
     Scene& s = h->s;
-    if ((int64_t)s.tris_host.size() != 9 * (int64_t)s.n) return bad("tmpt_scene_build_octree: no triangle copy");
+    if ((int64_t)s.tris_host.size() != 9 * (int64_t)s.bvh.n) return bad("tmpt_scene_build_octree: no triangle copy");
     TMPT_HIP(hipSetDevice(s.device));
     const auto t0 = std::chrono::steady_clock::now();
     OctreeHost t;
-    build_octree(s.tris_host.data(), s.n, bmin, bmax, t);
+    build_octree(s.tris_host.data(), s.bvh.n, bmin, bmax, t);
     if (t.refs.size() >= (size_t)INT32_MAX || t.nodes.size() >= (size_t)INT32_MAX)
         return bad("tmpt_scene_build_octree: octree too large");
-    OctNode* d_nodes = nullptr;
-    int32_t* d_refs = nullptr;
+    Octree o;
     const size_t nb = t.nodes.size() * sizeof(OctNode), rb = std::max<size_t>(1, t.refs.size()) * sizeof(int32_t);
-    if (hipMalloc(&d_nodes, nb) != hipSuccess || hipMalloc(&d_refs, rb) != hipSuccess ||
-        hipMemcpy(d_nodes, t.nodes.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-        (t.refs.size() && hipMemcpy(d_refs, t.refs.data(), t.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice) !=
-                              hipSuccess)) {
-        if (d_nodes) (void)hipFree(d_nodes);
-        if (d_refs) (void)hipFree(d_refs);
+    if (!o.oct.alloc(nb) || !o.oct_refs.alloc(rb) || !o.oct_view.alloc(sizeof(OctView)) ||
+        hipMemcpy(o.oct, t.nodes.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+        (t.refs.size() && hipMemcpy(o.oct_refs, t.refs.data(), t.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice) !=
+                              hipSuccess))
         return (set_error("tmpt_scene_build_octree: out of device memory"), -1);
-    }
-    if (ensure_counters(s)) {
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_refs);
-        return -1;
-    }
+    if (ensure_counters(s)) return -1;
     if (s.stream) (void)hipStreamSynchronize(s.stream);  // a render in flight may still read the old one
-    if (!s.oct_view && hipMalloc(&s.oct_view, sizeof(OctView)) != hipSuccess) {
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_refs);
-        return (set_error("tmpt_scene_build_octree: out of device memory"), -1);
-    }
     // the crack grid and the flat triangles (tmpt_internal.h OctGrid), marked
     // in the BVH's triangle records so that a hit on one flags its query
-    OctGrid grid;
-    octree_grid(t, bmin, bmax, grid);
+    octree_grid(t, bmin, bmax, o.oct_grid);
     std::vector<uint8_t> flat;
-    const int32_t n_flat = octree_flat_triangles(s.tris_host.data(), s.n, grid, flat);
-    if (mark_flat_triangles(s, flat)) {
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_refs);
-        return -1;
-    }
-    const OctView ov{d_nodes, d_refs, (int32_t)t.nodes.size(), n_flat, s.ties, grid, (int64_t)t.refs.size()};
-    if (hipMemcpy(s.oct_view, &ov, sizeof(ov), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d_nodes);
-        (void)hipFree(d_refs);
+    o.oct_flat = octree_flat_triangles(s.tris_host.data(), s.bvh.n, o.oct_grid, flat);
+    if (mark_flat_triangles(s, flat)) return -1;
+    o.n_oct = (int32_t)t.nodes.size();
+    o.n_oct_refs = (int64_t)t.refs.size();
+    const OctView ov{o.oct, o.oct_refs, o.n_oct, o.oct_flat, s.ties, o.oct_grid, o.n_oct_refs};
+    if (hipMemcpy(o.oct_view, &ov, sizeof(ov), hipMemcpyHostToDevice) != hipSuccess) {
         // the previous octree (if any) stays in use: give the records back its
         // own flat marks (none without one), so marks and octree agree
-        std::vector<uint8_t> old_flat((size_t)s.n, 0);
-        if (s.oct) (void)octree_flat_triangles(s.tris_host.data(), s.n, s.oct_grid, old_flat);
+        std::vector<uint8_t> old_flat((size_t)s.bvh.n, 0);
+        if (s.octree.oct) (void)octree_flat_triangles(s.tris_host.data(), s.bvh.n, s.octree.oct_grid, old_flat);
         (void)mark_flat_triangles(s, old_flat);
         return (set_error("tmpt_scene_build_octree: upload failed"), -1);
     }
-    if (s.oct) (void)hipFree(s.oct);
-    if (s.oct_refs) (void)hipFree(s.oct_refs);
-    s.oct = d_nodes;
-    s.oct_refs = d_refs;
-    s.n_oct = (int32_t)t.nodes.size();
-    s.n_oct_refs = (int64_t)t.refs.size();
-    s.oct_leaves = t.leaves;
-    s.oct_depth = t.depth;
-    s.oct_flat = n_flat;
-    s.oct_grid = grid;
+    o.oct_leaves = t.leaves;
+    o.oct_depth = t.depth;
     for (int c = 0; c < 3; ++c) {
-        s.oct_lo[c] = bmin[c];
-        s.oct_hi[c] = bmax[c];
+        o.oct_lo[c] = bmin[c];
+        o.oct_hi[c] = bmax[c];
     }
-    s.oct_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o.oct_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s.octree = std::move(o);
     return 0;
     TMPT_GUARD_END
 }
-
-namespace {
-// the octree dropped, exactly as if none had been built (tmpt_scene_update):
-// the device copies freed, the statistics 0; the records' flat marks are the
-// caller's to clear (a refit and a rebuild both write every record anew)
-void drop_octree(Scene& s)
-{
-    if (s.oct) (void)hipFree(s.oct);
-    if (s.oct_refs) (void)hipFree(s.oct_refs);
-    if (s.oct_view) (void)hipFree(s.oct_view);
-    s.oct = nullptr;
-    s.oct_refs = nullptr;
-    s.oct_view = nullptr;
-    s.n_oct = s.oct_leaves = s.oct_depth = s.oct_flat = 0;
-    s.n_oct_refs = 0;
-    s.oct_grid = OctGrid{};
-    s.oct_build_ms = 0.0;
-    for (int c = 0; c < 3; ++c) s.oct_lo[c] = s.oct_hi[c] = 0.0f;
-}
-}  // namespace
 
 int tmpt_scene_update(tmpt_scene* h, const float* tris, int32_t n, int32_t mode)
 {
@@ -593,86 +500,49 @@ int tmpt_scene_update(tmpt_scene* h, const float* tris, int32_t n, int32_t mode)
     if (n > 0 && !tris) return bad("tmpt_scene_update: null triangles with n > 0");
     if (!h) return bad("tmpt_scene_update: null scene");
     Scene& s = h->s;
-    if (mode == TMPT_UPDATE_REFIT && n != s.n)
+    if (mode == TMPT_UPDATE_REFIT && n != s.bvh.n)
         return bad("tmpt_scene_update: a refit keeps the triangle count (n differs from the scene's); rebuild instead");
     TMPT_HIP(hipSetDevice(s.device));
     (void)hipGetLastError();  // a failed call before this one must not fail this one's checks
     TMPT_HIP(hipStreamSynchronize(s.stream));  // a render in flight may still read the tree
-    for (auto& e : s.update_ev)
-        if (!e) TMPT_HIP(hipEventCreate(&e));
+    for (auto& e : s.update_ev) TMPT_HIP(e.ensure());
     const size_t bytes = sizeof(float) * 9 * (size_t)n;
-    float* d_tris = nullptr;
-    if (n > 0) {
-        if (hipMalloc(&d_tris, bytes) != hipSuccess) return (set_error("tmpt_scene_update: out of device memory"), -1);
-    }
-    auto fail = [&](int rc) {
-        if (d_tris) (void)hipFree(d_tris);
-        return rc;
-    };
-    if (hipEventRecord(s.update_ev[0], s.stream) != hipSuccess) return fail((set_error("tmpt_scene_update: event failed"), -1));
+    DeviceBuffer<float> d_tris;
+    if (n > 0 && !d_tris.alloc(bytes)) return (set_error("tmpt_scene_update: out of device memory"), -1);
+    if (hipEventRecord(s.update_ev[0], s.stream) != hipSuccess) return (set_error("tmpt_scene_update: event failed"), -1);
     if (n > 0 && hipMemcpyAsync(d_tris, tris, bytes, hipMemcpyHostToDevice, s.stream) != hipSuccess)
-        return fail((set_error("tmpt_scene_update: upload failed"), -1));
+        return (set_error("tmpt_scene_update: upload failed"), -1);
     if (mode == TMPT_UPDATE_REFIT) {
         // every record is written anew with its flat mark clear; a failure here is a
         // HIP error, after which the tree is whatever the launches left
-        if (int rc = refit_bvh(s, d_tris)) return fail(rc);
+        if (int rc = refit_bvh(s.bvh, s.stream, d_tris)) return rc;
     } else {
         // the full build into fresh allocations, on the scene's stream and with
         // its build options; swapped in only on success
-        Scene t;
-        t.opt = s.opt;
-        t.device = s.device;
-        t.stream = s.stream;
+        Bvh t;
         t.n = n;
-        const int rc = build_lbvh(t, d_tris);
+        const int rc = build_lbvh(t, s.opt, s.stream, d_tris);
         if (rc) {
             const std::string why = last_error();
             (void)hipStreamSynchronize(s.stream);
-            if (t.nodes4) (void)hipFree(t.nodes4);
-            if (t.tri_pre) (void)hipFree(t.tri_pre);
-            if (t.tri_orig) (void)hipFree(t.tri_orig);
-            if (t.node_box) (void)hipFree(t.node_box);
-            if (t.soa_buf) (void)hipFree(t.soa_buf);
+            t = Bvh{};
             (void)hipGetLastError();
             set_error(why);
-            return fail(rc);
+            return rc;
         }
-        if (s.nodes4) (void)hipFree(s.nodes4);
-        if (s.tri_pre) (void)hipFree(s.tri_pre);
-        if (s.tri_orig) (void)hipFree(s.tri_orig);
-        if (s.node_box) (void)hipFree(s.node_box);
-        if (s.rec_box) (void)hipFree(s.rec_box);
-        if (s.soa_buf) (void)hipFree(s.soa_buf);
-        s.rec_box = nullptr;
-        s.n = t.n;
-        s.n_nodes = t.n_nodes;
-        s.max_depth = t.max_depth;
-        s.nodes4 = t.nodes4;
-        s.n_nodes4 = t.n_nodes4;
-        s.depth4 = t.depth4;
-        s.leaf_max = t.leaf_max;
-        s.ploc_iters = t.ploc_iters;
-        s.count_shift = t.count_shift;
-        s.link_bits = t.link_bits;
-        s.tri_pre = t.tri_pre;
-        s.tri_orig = t.tri_orig;
-        s.node_box = t.node_box;
-        s.soa_buf = t.soa_buf;
-        s.soa = t.soa;
-        s.level_begin = std::move(t.level_begin);
-        s.build_ms = t.build_ms;
+        s.bvh = std::move(t);
     }
     hipError_t e = hipEventRecord(s.update_ev[1], s.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
     float ms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, s.update_ev[0], s.update_ev[1]);
-    if (d_tris) (void)hipFree(d_tris);
+    d_tris.reset();
     if (e != hipSuccess) {
         set_error(std::string("tmpt_scene_update: ") + hipGetErrorString(e));
         return -1;
     }
     s.tris_host.assign(tris, tris + 9 * (size_t)n);
-    drop_octree(s);
+    s.octree = Octree{};  // exactly as if none had been built; a refit and a rebuild both wrote every record's flat mark anew
     s.prog_key[6] = -1;  // the carried sums belong to the old triangles: spp_begin > 0 fails next
     s.update_kind = mode == TMPT_UPDATE_REFIT ? 1 : 2;
     s.update_ms = (double)ms;
@@ -752,7 +622,7 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
     TMPT_GUARD_BEGIN
     if (!h || !value) return bad("tmpt_scene_get_option: null argument");
     if (key && strcmp(key, "pop_key_bits") == 0) {  // read-only: the scene's layout under pop_key_cap
-        *value = (double)pop_key_bits(h->s.link_bits, h->s.opt.pop_key_cap);
+        *value = (double)pop_key_bits(h->s.bvh.link_bits, h->s.opt.pop_key_cap);
         return 0;
     }
     if (key && strcmp(key, "cam_rays_used") == 0) {  // read-only: the last render ran the camera pre-pass
@@ -773,6 +643,10 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
     }
     if (key && strcmp(key, "update_ms") == 0) {  // read-only: device time of the last tmpt_scene_update
         *value = h->s.update_ms;
+        return 0;
+    }
+    if (key && strcmp(key, "live_device_objects") == 0) {  // read-only: the process's live tmpt_device.h owners
+        *value = (double)g_live_device_objects.load();
         return 0;
     }
     if (key && strcmp(key, "bvh_cost") == 0) {  // read-only: the tree's surface-area cost, cached until an update
@@ -799,18 +673,10 @@ int scene_hit(const tmpt_scene* hc, const float* rays, int64_t n, float tmin, fl
     const size_t rs = ranged ? 32 : 24;
     Scene& s = const_cast<tmpt_scene*>(hc)->s;
     TMPT_HIP(hipSetDevice(s.device));
-    float *d_rays = nullptr, *d_hits = nullptr;
-    int32_t* d_ids = nullptr;
-    auto cleanup = [&]() {
-        if (d_rays) (void)hipFree(d_rays);
-        if (d_hits) (void)hipFree(d_hits);
-        if (d_ids) (void)hipFree(d_ids);
-    };
-    if (hipMalloc(&d_rays, rs * (size_t)n) != hipSuccess || hipMalloc(&d_hits, 28 * (size_t)n) != hipSuccess ||
-        hipMalloc(&d_ids, 4 * (size_t)n) != hipSuccess) {
-        cleanup();
+    DeviceBuffer<float> d_rays, d_hits;
+    DeviceBuffer<int32_t> d_ids;
+    if (!d_rays.alloc(rs * (size_t)n) || !d_hits.alloc(28 * (size_t)n) || !d_ids.alloc(4 * (size_t)n))
         return bad("tmpt_scene_hit: out of device memory");
-    }
     int rc = 0;
     if (hipMemcpy(d_rays, rays, rs * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_hits, hits, 28 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
@@ -826,7 +692,6 @@ int scene_hit(const tmpt_scene* hc, const float* rays, int64_t n, float tmin, fl
         s.crack_queries = s.counters_host[kCrackCounter];
     }
     if (!rc) rc = check_report(s, "tmpt_scene_hit");
-    cleanup();
     return rc;
 }
 }  // namespace
@@ -896,16 +761,15 @@ int tmpt_render(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d
     const int32_t rows = tmpt_tile_rows(d);
     const size_t bytes = (size_t)rows * (size_t)d->width * 4;
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    uint32_t* d_out = nullptr;
-    if (dev_out) d_out = (uint32_t*)rgba_out;
-    else if (bytes && hipMalloc(&d_out, bytes) != hipSuccess) return bad("tmpt_render: out of device memory");
+    DeviceBuffer<uint32_t> own;
+    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render: out of device memory");
+    uint32_t* d_out = dev_out ? (uint32_t*)rgba_out : own.get();
     int rc = render(s, cam, d, d_out, ray_count);
     if (!rc) rc = check_report(s, "tmpt_render");
     if (!rc && !dev_out && bytes) {
         if (hipMemcpy(rgba_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
             rc = (set_error("tmpt_render: readback failed"), -1);
     }
-    if (!dev_out && d_out) (void)hipFree(d_out);
     return rc;
     TMPT_GUARD_END
 }
@@ -933,16 +797,15 @@ int tmpt_render_aov(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_des
     Scene& s = h->s;
     TMPT_HIP(hipSetDevice(s.device));
     const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * sizeof(tmpt_aov_pixel);
-    tmpt_aov_pixel* d_out = nullptr;
-    if (dev_out) d_out = out;
-    else if (bytes && hipMalloc(&d_out, bytes) != hipSuccess) return bad("tmpt_render_aov: out of device memory");
+    DeviceBuffer<tmpt_aov_pixel> own;
+    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render_aov: out of device memory");
+    tmpt_aov_pixel* d_out = dev_out ? out : own.get();
     int rc = render_aov(s, cam, d, d_out, ray_count);
     if (!rc) rc = check_report(s, "tmpt_render_aov");
     if (!rc && !dev_out && bytes) {
         if (hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
             rc = (set_error("tmpt_render_aov: readback failed"), -1);
     }
-    if (!dev_out && d_out) (void)hipFree(d_out);
     return rc;
     TMPT_GUARD_END
 }
@@ -995,18 +858,12 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
     // for host outputs and for an rgba8_out the caller does not want
     float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
     uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
-    void *own_f = nullptr, *own_8 = nullptr;
-    auto cleanup = [&]() {
-        if (own_f) (void)hipFree(own_f);
-        if (own_8) (void)hipFree(own_8);
-    };
-    if (px && ((!d_f && hipMalloc(&own_f, px * sizeof(float4)) != hipSuccess) ||
-               (!d_8 && hipMalloc(&own_8, px * 4) != hipSuccess))) {
-        cleanup();
+    DeviceBuffer<float4> own_f;
+    DeviceBuffer<uint32_t> own_8;
+    if (px && ((!d_f && !own_f.alloc(px * sizeof(float4))) || (!d_8 && !own_8.alloc(px * 4))))
         return bad("tmpt_render_radiance: out of device memory");
-    }
-    if (own_f) d_f = static_cast<float4*>(own_f);
-    if (own_8) d_8 = static_cast<uint32_t*>(own_8);
+    if (own_f) d_f = own_f;
+    if (own_8) d_8 = own_8;
     int rc = render(s, cam, d, d_8, ray_count, d_f);
     if (!rc) rc = check_report(s, "tmpt_render_radiance");
     if (!rc && !dev_out && px) {
@@ -1014,7 +871,6 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
             (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_render_radiance: readback failed"), -1);
     }
-    cleanup();
     return rc;
     TMPT_GUARD_END
 }
@@ -1067,22 +923,16 @@ int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
     float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
     uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
     int32_t* d_n = dev_out ? spp_out : nullptr;
-    void *own_f = nullptr, *own_8 = nullptr, *own_n = nullptr;
-    auto cleanup = [&]() {
-        if (own_f) (void)hipFree(own_f);
-        if (own_8) (void)hipFree(own_8);
-        if (own_n) (void)hipFree(own_n);
-    };
+    DeviceBuffer<float4> own_f;
+    DeviceBuffer<uint32_t> own_8;
+    DeviceBuffer<int32_t> own_n;
     if (!dev_out && px &&
-        ((rgba32f_out && hipMalloc(&own_f, px * sizeof(float4)) != hipSuccess) ||
-         (rgba8_out && hipMalloc(&own_8, px * 4) != hipSuccess) ||
-         (spp_out && hipMalloc(&own_n, px * 4) != hipSuccess))) {
-        cleanup();
+        ((rgba32f_out && !own_f.alloc(px * sizeof(float4))) || (rgba8_out && !own_8.alloc(px * 4)) ||
+         (spp_out && !own_n.alloc(px * 4))))
         return bad("tmpt_render_adaptive: out of device memory");
-    }
-    if (own_f) d_f = static_cast<float4*>(own_f);
-    if (own_8) d_8 = static_cast<uint32_t*>(own_8);
-    if (own_n) d_n = static_cast<int32_t*>(own_n);
+    if (own_f) d_f = own_f;
+    if (own_8) d_8 = own_8;
+    if (own_n) d_n = own_n;
     int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count);
     if (!rc) rc = check_report(s, "tmpt_render_adaptive");
     if (!rc && !dev_out && px) {
@@ -1091,7 +941,6 @@ int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
             (spp_out && hipMemcpy(spp_out, d_n, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_render_adaptive: readback failed"), -1);
     }
-    cleanup();
     return rc;
     TMPT_GUARD_END
 }
@@ -1132,28 +981,20 @@ int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f
     const tmpt_aov_pixel* d_aov = aov;
     float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
     uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
-    void *own_in = nullptr, *own_aov = nullptr, *own_8 = nullptr;
-    auto cleanup = [&]() {
-        if (own_in) (void)hipFree(own_in);
-        if (own_aov) (void)hipFree(own_aov);
-        if (own_8) (void)hipFree(own_8);
-    };
+    DeviceBuffer<float4> own_in;
+    DeviceBuffer<tmpt_aov_pixel> own_aov;
+    DeviceBuffer<uint32_t> own_8;
     if (!dev) {  // host pointers: staged on the device; the float result is filtered in place there
-        if (hipMalloc(&own_in, n * sizeof(float4)) != hipSuccess ||
-            hipMalloc(&own_aov, n * sizeof(tmpt_aov_pixel)) != hipSuccess ||
-            (rgba8_out && hipMalloc(&own_8, n * 4) != hipSuccess)) {
-            cleanup();
+        if (!own_in.alloc(n * sizeof(float4)) || !own_aov.alloc(n * sizeof(tmpt_aov_pixel)) ||
+            (rgba8_out && !own_8.alloc(n * 4)))
             return bad("tmpt_denoise: out of device memory");
-        }
         if (hipMemcpy(own_in, rgba32f_in, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess) {
-            cleanup();
+            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess)
             return (set_error("tmpt_denoise: upload failed"), -1);
-        }
-        d_in = static_cast<const float4*>(own_in);
-        d_aov = static_cast<const tmpt_aov_pixel*>(own_aov);
-        d_o32 = rgba32f_out ? static_cast<float4*>(own_in) : nullptr;
-        d_o8 = static_cast<uint32_t*>(own_8);
+        d_in = own_in;
+        d_aov = own_aov;
+        d_o32 = rgba32f_out ? own_in.get() : nullptr;
+        d_o8 = own_8;
     }
     int rc = denoise(s, &r, d_in, d_aov, d_o32, d_o8);
     if (!rc && !dev) {
@@ -1161,7 +1002,6 @@ int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f
             (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_denoise: readback failed"), -1);
     }
-    cleanup();
     return rc;
     TMPT_GUARD_END
 }
@@ -1191,12 +1031,12 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
     // gathered tiles, the frame and the summed count
     const int max_rows = (H + nd - 1) / nd;
     const size_t tile_bytes = (size_t)max_rows * (size_t)W * 4;
-    std::vector<uint8_t*> d_tile((size_t)nd, nullptr);
-    std::vector<uint64_t*> d_rays((size_t)nd, nullptr);
-    std::vector<hipStream_t> streams((size_t)nd, nullptr);
-    uint8_t* d_gather = nullptr;
-    uint32_t* d_frame = nullptr;
-    uint64_t* d_total = nullptr;
+    std::vector<DeviceBuffer<uint8_t>> d_tile((size_t)nd);
+    std::vector<DeviceBuffer<uint64_t>> d_rays((size_t)nd);
+    std::vector<Stream> streams((size_t)nd);
+    DeviceBuffer<uint8_t> d_gather;
+    DeviceBuffer<uint32_t> d_frame;
+    DeviceBuffer<uint64_t> d_total;
     std::vector<ncclComm_t> comms;
     auto cleanup = [&]() {  // touches only devices whose resources exist (a bad ordinal is never set)
         for (int g = 0; g < nd; ++g)
@@ -1209,17 +1049,20 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
         for (int g = 0; g < nd; ++g) {
             if (!streams[(size_t)g] && !d_tile[(size_t)g] && !d_rays[(size_t)g]) continue;
             (void)hipSetDevice(devices[g]);
-            if (d_tile[(size_t)g]) (void)hipFree(d_tile[(size_t)g]);
-            if (d_rays[(size_t)g]) (void)hipFree(d_rays[(size_t)g]);
-            if (streams[(size_t)g]) (void)hipStreamDestroy(streams[(size_t)g]);
+            d_tile[(size_t)g].reset();
+            d_rays[(size_t)g].reset();
+            streams[(size_t)g].reset();
         }
         if (d_gather || d_frame || d_total) {
             (void)hipSetDevice(devices[0]);
-            if (d_gather) (void)hipFree(d_gather);
-            if (d_frame) (void)hipFree(d_frame);
-            if (d_total) (void)hipFree(d_total);
+            d_gather.reset();
+            d_frame.reset();
+            d_total.reset();
         }
-        for (auto* sc : scenes) tmpt_scene_destroy(sc);
+        for (auto*& sc : scenes) {
+            tmpt_scene_destroy(sc);
+            sc = nullptr;
+        }
         (void)hipGetLastError();  // leave no sticky error behind for this thread's next call
     };
     auto fail = [&](const std::string& msg, int rc) {
@@ -1241,14 +1084,13 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
     for (int g = 0; g < nd; ++g)
         if (rcs[(size_t)g]) return fail(errs[(size_t)g], rcs[(size_t)g]);
     for (int g = 0; g < nd; ++g) {
-        if (hipSetDevice(devices[g]) != hipSuccess || hipStreamCreateWithFlags(&streams[(size_t)g], hipStreamNonBlocking) ||
-            hipMalloc(&d_tile[(size_t)g], tile_bytes) != hipSuccess ||
-            hipMalloc(&d_rays[(size_t)g], sizeof(uint64_t)) != hipSuccess ||
+        if (hipSetDevice(devices[g]) != hipSuccess || streams[(size_t)g].ensure(hipStreamNonBlocking) != hipSuccess ||
+            !d_tile[(size_t)g].alloc(tile_bytes) || !d_rays[(size_t)g].alloc(sizeof(uint64_t)) ||
             hipMemsetAsync(d_tile[(size_t)g], 0, tile_bytes, streams[(size_t)g]) != hipSuccess)
             return fail("out of device memory", -1);
     }
-    if (hipSetDevice(devices[0]) != hipSuccess || hipMalloc(&d_gather, tile_bytes * (size_t)nd) != hipSuccess ||
-        hipMalloc(&d_frame, (size_t)W * H * 4) != hipSuccess || hipMalloc(&d_total, sizeof(uint64_t)) != hipSuccess)
+    if (hipSetDevice(devices[0]) != hipSuccess || !d_gather.alloc(tile_bytes * (size_t)nd) ||
+        !d_frame.alloc((size_t)W * H * 4) || !d_total.alloc(sizeof(uint64_t)))
         return fail("out of device memory (root)", -1);
     if (use_rccl) {  // single-process form of SURVEY.md §8e: one communicator per device
         comms.assign((size_t)nd, nullptr);
@@ -1317,7 +1159,7 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
     }
     (void)hipSetDevice(devices[0]);
     k_assemble_rows<<<(unsigned)(((int64_t)W * H + 255) / 256), 256, 0, streams[0]>>>(
-        reinterpret_cast<const uint32_t*>(d_gather), nd, max_rows, W, H, d_frame);
+        reinterpret_cast<const uint32_t*>(d_gather.get()), nd, max_rows, W, H, d_frame);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(streams[0]) != hipSuccess)
         return fail("frame assembly failed", -1);
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1347,30 +1189,30 @@ int tmpt_get_stats(const tmpt_scene* h, tmpt_stats* o)
     o->tri_tests = s.tri_tests;
     o->shadow_node_visits = s.shadow_node_visits;
     o->shadow_tri_tests = s.shadow_tri_tests;
-    o->build_ms = s.build_ms;
-    o->bvh_nodes = s.n_nodes;
-    o->bvh_depth = s.max_depth;
-    o->n_tris = s.n;
+    o->build_ms = s.bvh.build_ms;
+    o->bvh_nodes = s.bvh.n_nodes;
+    o->bvh_depth = s.bvh.max_depth;
+    o->n_tris = s.bvh.n;
     o->device = s.device;
-    o->bvh4_nodes = s.n_nodes4;
-    o->bvh4_depth = s.depth4;
-    o->leaf_max = s.leaf_max;
-    o->builder_iters = s.ploc_iters;
-    o->octree_nodes = s.n_oct;
-    o->octree_leaves = s.oct_leaves;
-    o->octree_refs = s.n_oct ? s.n_oct_refs - s.oct_leaves : 0;
-    o->octree_build_ms = s.oct_build_ms;
+    o->bvh4_nodes = s.bvh.n_nodes4;
+    o->bvh4_depth = s.bvh.depth4;
+    o->leaf_max = s.bvh.leaf_max;
+    o->builder_iters = s.bvh.ploc_iters;
+    o->octree_nodes = s.octree.n_oct;
+    o->octree_leaves = s.octree.oct_leaves;
+    o->octree_refs = s.octree.n_oct ? s.octree.n_oct_refs - s.octree.oct_leaves : 0;
+    o->octree_build_ms = s.octree.oct_build_ms;
     o->tie_queries = s.tie_queries;
     o->root_misses = s.root_misses;
     o->row_engine = s.row_engine;
     o->stream_fallbacks = s.stream_fallbacks;
-    o->octree_depth = s.oct_depth;
-    o->tie_rule = s.oct && s.opt.tie_rule == 0 ? 0 : 1;
+    o->octree_depth = s.octree.oct_depth;
+    o->tie_rule = s.octree.oct && s.opt.tie_rule == 0 ? 0 : 1;
     o->chain_pixels = s.chain_pixels;
     o->redo_samples = s.redo_samples;
     o->redo_late = s.redo_late;
     o->crack_queries = s.crack_queries;
-    o->octree_flat = s.oct ? s.oct_flat : 0;
+    o->octree_flat = s.octree.oct ? s.octree.oct_flat : 0;
     o->redo_launches = s.redo_launches;
     o->redo_ms = s.redo_ms;
     o->redo_rays = s.redo_rays;
@@ -1387,11 +1229,11 @@ int tmpt_scene_dump_bvh(const tmpt_scene* hc, int32_t layout, uint32_t* nodes, u
     if (layout != 0 && layout != 1) return bad("tmpt_scene_dump_bvh: layout is 0 (aos) or 1 (soa)");
     if ((nodes == nullptr) != (tris == nullptr)) return bad("tmpt_scene_dump_bvh: give both buffers, or neither");
     Scene& s = const_cast<tmpt_scene*>(hc)->s;
-    const bool has_soa = s.soa_buf != nullptr;
+    const bool has_soa = s.bvh.soa_buf != nullptr;
     if (layout == 1 && !has_soa) return bad("tmpt_scene_dump_bvh: the scene was built without layout=soa");
-    const int32_t out[8] = {s.n, s.n_nodes4, s.depth4, s.leaf_max, s.count_shift, s.link_bits, s.ploc_iters,
+    const int32_t out[8] = {s.bvh.n, s.bvh.n_nodes4, s.bvh.depth4, s.bvh.leaf_max, s.bvh.count_shift, s.bvh.link_bits, s.bvh.ploc_iters,
                             has_soa ? 1 : 0};
-    if (nodes && (node_words < 16u * (uint64_t)s.n_nodes4 || tri_words < 12u * ((uint64_t)s.n + 1u)))
+    if (nodes && (node_words < 16u * (uint64_t)s.bvh.n_nodes4 || tri_words < 12u * ((uint64_t)s.bvh.n + 1u)))
         return bad("tmpt_scene_dump_bvh: short buffer (16 words per node, 12 per triangle record and one more)");
     memcpy(info, out, sizeof(out));
     if (!nodes) return 0;

@@ -892,28 +892,27 @@ __global__ void __launch_bounds__(kBlock) k_bvh_cost(const Bvh4Node* __restrict_
 
 // tmpt_scene_update, mode refit: d_tris9 holds the scene's n new triangles.
 // All on the scene's stream, no host synchronisation between the launches.
-int refit_bvh(Scene& s, const float* d_tris9)
+int refit_bvh(Bvh& bvh, hipStream_t st, const float* d_tris9)
 {
-    const int32_t n = s.n;
+    const int32_t n = bvh.n;
     if (n <= 0) return 0;
-    hipStream_t st = s.stream;
-    if ((int)s.level_begin.size() != s.depth4 + 1 || !s.node_box) {
+    if ((int)bvh.level_begin.size() != bvh.depth4 + 1 || !bvh.node_box) {
         set_error("tmpt_scene_update: the scene has no level ranges to refit over");
         return -1;
     }
-    if (!s.rec_box) TMPT_HIP(hipMalloc(&s.rec_box, 6 * sizeof(float) * (size_t)n));
-    k_refit_tris<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, s.tri_pre, s.tri_orig, s.rec_box,
-                                                           const_cast<float4*>(s.soa.ta),
-                                                           const_cast<float4*>(s.soa.tb),
-                                                           const_cast<float2*>(s.soa.tc));
-    for (int L = s.depth4 - 1; L >= 0; --L) {  // deepest level first
-        const int32_t b = s.level_begin[L], e = s.level_begin[L + 1];
+    if (!bvh.rec_box.reserve(6 * sizeof(float) * (size_t)n)) return (set_error("refit_bvh: out of device memory"), -1);
+    k_refit_tris<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, bvh.tri_pre, bvh.tri_orig, bvh.rec_box,
+                                                           const_cast<float4*>(bvh.soa.ta),
+                                                           const_cast<float4*>(bvh.soa.tb),
+                                                           const_cast<float2*>(bvh.soa.tc));
+    for (int L = bvh.depth4 - 1; L >= 0; --L) {  // deepest level first
+        const int32_t b = bvh.level_begin[L], e = bvh.level_begin[L + 1];
         if (e <= b) continue;
-        k_refit_level4<<<blocks_for(e - b, kBlock), kBlock, 0, st>>>(s.nodes4, b, e, n, s.n_nodes4, s.rec_box,
-                                                                    s.node_box, s.count_shift,
-                                                                    const_cast<uint4*>(s.soa.na),
-                                                                    const_cast<uint4*>(s.soa.nb),
-                                                                    const_cast<uint2*>(s.soa.nc));
+        k_refit_level4<<<blocks_for(e - b, kBlock), kBlock, 0, st>>>(bvh.nodes4, b, e, n, bvh.n_nodes4, bvh.rec_box,
+                                                                    bvh.node_box, bvh.count_shift,
+                                                                    const_cast<uint4*>(bvh.soa.na),
+                                                                    const_cast<uint4*>(bvh.soa.nb),
+                                                                    const_cast<uint2*>(bvh.soa.nc));
     }
     TMPT_HIP(hipGetLastError());
     return 0;
@@ -924,18 +923,17 @@ int refit_bvh(Scene& s, const float* d_tris9)
 int bvh_cost(Scene& s, double* out)
 {
     *out = 0.0;
-    if (s.n <= 0 || s.n_nodes4 <= 0) return 0;
-    const int nb = std::min(blocks_for(s.n_nodes4, kBlock), 256);
-    double* d_part = nullptr;
-    TMPT_HIP(hipMalloc(&d_part, sizeof(double) * (size_t)nb));
+    if (s.bvh.n <= 0 || s.bvh.n_nodes4 <= 0) return 0;
+    const int nb = std::min(blocks_for(s.bvh.n_nodes4, kBlock), 256);
+    DeviceBuffer<double> d_part;
+    if (!d_part.alloc(sizeof(double) * (size_t)nb)) return (set_error("bvh_cost: out of device memory"), -1);
     std::vector<double> part((size_t)nb);
     float root[6];
-    k_bvh_cost<<<nb, kBlock, 0, s.stream>>>(s.nodes4, s.n_nodes4, s.count_shift, d_part);
+    k_bvh_cost<<<nb, kBlock, 0, s.stream>>>(s.bvh.nodes4, s.bvh.n_nodes4, s.bvh.count_shift, d_part);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, s.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(root, s.node_box, sizeof(root), hipMemcpyDeviceToHost, s.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(root, s.bvh.node_box, sizeof(root), hipMemcpyDeviceToHost, s.stream);
     const hipError_t e2 = hipStreamSynchronize(s.stream);
-    (void)hipFree(d_part);
     TMPT_HIP(e);
     TMPT_HIP(e2);
     double sum = 0.0;
@@ -948,37 +946,34 @@ int bvh_cost(Scene& s, double* out)
 
 int mark_flat_triangles(Scene& s, const std::vector<uint8_t>& flat)
 {
-    if (s.n <= 0) return 0;
-    uint8_t* d = nullptr;
+    if (s.bvh.n <= 0) return 0;
+    DeviceBuffer<uint8_t> d;
     const bool any = std::find(flat.begin(), flat.end(), (uint8_t)1) != flat.end();
     if (any) {
-        TMPT_HIP(hipMalloc(&d, (size_t)s.n));
-        if (hipMemcpy(d, flat.data(), (size_t)s.n, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
+        if (!d.alloc((size_t)s.bvh.n)) return (set_error("mark_flat_triangles: out of device memory"), -1);
+        if (hipMemcpy(d, flat.data(), (size_t)s.bvh.n, hipMemcpyHostToDevice) != hipSuccess) {
             set_error("mark_flat_triangles: upload failed");
             return -1;
         }
     }
-    k_mark_flat<<<blocks_for(s.n, kBlock), kBlock, 0, s.stream>>>(s.tri_pre, const_cast<float2*>(s.soa.tc), s.n, d);
+    k_mark_flat<<<blocks_for(s.bvh.n, kBlock), kBlock, 0, s.stream>>>(s.bvh.tri_pre, const_cast<float2*>(s.bvh.soa.tc), s.bvh.n,
+                                                                          d.get());
     const hipError_t e = hipGetLastError();
     const hipError_t e2 = hipStreamSynchronize(s.stream);
-    if (d) (void)hipFree(d);
     TMPT_HIP(e);
     TMPT_HIP(e2);
     return 0;
 }
 
-int build_soa(Scene& s)
+int build_soa(Bvh& bvh, hipStream_t st)
 {
-    const size_t n4 = (size_t)std::max(s.n_nodes4, 1), n1 = (size_t)s.n + 1;
+    const size_t n4 = (size_t)std::max(bvh.n_nodes4, 1), n1 = (size_t)bvh.n + 1;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_nb = al(16 * n4), o_nc = o_nb + al(16 * n4), o_nd = o_nc + al(8 * n4), o_ta = o_nd + al(16 * n4),
                  o_tb = o_ta + al(16 * n1), o_tc = o_tb + al(16 * n1), total = o_tc + al(8 * n1);
-    if (s.soa_buf) (void)hipFree(s.soa_buf);
-    s.soa_buf = nullptr;
-    s.soa = SoaScene();
-    TMPT_HIP(hipMalloc(&s.soa_buf, total));
-    char* b = static_cast<char*>(s.soa_buf);
+    bvh.soa = SoaScene();
+    if (!bvh.soa_buf.alloc(total)) return (set_error("build_soa: out of device memory"), -1);
+    char* b = static_cast<char*>(bvh.soa_buf.get());
     uint4* na = reinterpret_cast<uint4*>(b);
     uint4* nb = reinterpret_cast<uint4*>(b + o_nb);
     uint2* nc = reinterpret_cast<uint2*>(b + o_nc);
@@ -986,11 +981,11 @@ int build_soa(Scene& s)
     float4* ta = reinterpret_cast<float4*>(b + o_ta);
     float4* tb = reinterpret_cast<float4*>(b + o_tb);
     float2* tc = reinterpret_cast<float2*>(b + o_tc);
-    k_soa_planes<<<blocks_for((int64_t)std::max(n4, n1), kBlock), kBlock, 0, s.stream>>>(
-        s.nodes4, s.n_nodes4, s.tri_pre, (int32_t)n1, na, nb, nc, nd, ta, tb, tc);
+    k_soa_planes<<<blocks_for((int64_t)std::max(n4, n1), kBlock), kBlock, 0, st>>>(
+        bvh.nodes4, bvh.n_nodes4, bvh.tri_pre, (int32_t)n1, na, nb, nc, nd, ta, tb, tc);
     TMPT_HIP(hipGetLastError());
-    TMPT_HIP(hipStreamSynchronize(s.stream));
-    s.soa = SoaScene{na, nb, nc, nd, ta, tb, tc};
+    TMPT_HIP(hipStreamSynchronize(st));
+    bvh.soa = SoaScene{na, nb, nc, nd, ta, tb, tc};
     return 0;
 }
 
@@ -1024,10 +1019,10 @@ size_t radix_sort_hist_words(int32_t n) { return 256 * (size_t)std::max(1, block
 int dump_bvh(Scene& s, bool soa, uint32_t* nodes, uint32_t* tris)
 {
     TMPT_HIP(hipStreamSynchronize(s.stream));
-    const size_t n4 = (size_t)s.n_nodes4, n1 = (size_t)s.n + 1;
+    const size_t n4 = (size_t)s.bvh.n_nodes4, n1 = (size_t)s.bvh.n + 1;
     if (!soa) {
-        if (n4) TMPT_HIP(hipMemcpy(nodes, s.nodes4, sizeof(Bvh4Node) * n4, hipMemcpyDeviceToHost));
-        TMPT_HIP(hipMemcpy(tris, s.tri_pre, sizeof(TriPre) * n1, hipMemcpyDeviceToHost));
+        if (n4) TMPT_HIP(hipMemcpy(nodes, s.bvh.nodes4, sizeof(Bvh4Node) * n4, hipMemcpyDeviceToHost));
+        TMPT_HIP(hipMemcpy(tris, s.bvh.tri_pre, sizeof(TriPre) * n1, hipMemcpyDeviceToHost));
         return 0;
     }
     std::vector<uint32_t> p4(4 * std::max(n4, n1)), p2(2 * std::max(n4, n1));
@@ -1041,10 +1036,10 @@ int dump_bvh(Scene& s, bool soa, uint32_t* nodes, uint32_t* tris)
     };
     for (size_t k = 0; k < n4; ++k) nodes[16 * k + 10] = nodes[16 * k + 11] = 0u;
     for (size_t k = 0; k < n1; ++k) tris[12 * k + 10] = tris[12 * k + 11] = 0u;
-    if (plane(s.soa.na, n4, 4, 0, nodes, 16) || plane(s.soa.nb, n4, 4, 4, nodes, 16) ||
-        plane(s.soa.nc, n4, 2, 8, nodes, 16) || plane(s.soa.nd, n4, 4, 12, nodes, 16) ||
-        plane(s.soa.ta, n1, 4, 0, tris, 12) || plane(s.soa.tb, n1, 4, 4, tris, 12) ||
-        plane(s.soa.tc, n1, 2, 8, tris, 12))
+    if (plane(s.bvh.soa.na, n4, 4, 0, nodes, 16) || plane(s.bvh.soa.nb, n4, 4, 4, nodes, 16) ||
+        plane(s.bvh.soa.nc, n4, 2, 8, nodes, 16) || plane(s.bvh.soa.nd, n4, 4, 12, nodes, 16) ||
+        plane(s.bvh.soa.ta, n1, 4, 0, tris, 12) || plane(s.bvh.soa.tb, n1, 4, 4, tris, 12) ||
+        plane(s.bvh.soa.tc, n1, 2, 8, tris, 12))
         return -1;
     return 0;
 }
@@ -1054,8 +1049,8 @@ int dump_bvh(Scene& s, bool soa, uint32_t* nodes, uint32_t* tris)
 int radix_sort_host(Scene& s, uint32_t* keys, uint32_t* vals, int32_t n, int bits)
 {
     const size_t nb = 4 * (size_t)n, hw = radix_sort_hist_words(n);
-    uint32_t* buf = nullptr;  // keys, vals, tkeys, tvals, hist
-    TMPT_HIP(hipMalloc(&buf, 4 * nb + 4 * hw));
+    DeviceBuffer<uint32_t> buf;  // keys, vals, tkeys, tvals, hist
+    if (!buf.alloc(4 * nb + 4 * hw)) return (set_error("tmpt_radix_sort: out of device memory"), -1);
     uint32_t* d[4] = {buf, buf + n, buf + 2 * (size_t)n, buf + 3 * (size_t)n};
     hipError_t e = hipMemcpyAsync(d[0], keys, nb, hipMemcpyHostToDevice, s.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d[1], vals, nb, hipMemcpyHostToDevice, s.stream);
@@ -1066,7 +1061,6 @@ int radix_sort_host(Scene& s, uint32_t* keys, uint32_t* vals, int32_t n, int bit
         if (e == hipSuccess) e = hipMemcpyAsync(vals, d[2 * which + 1], nb, hipMemcpyDeviceToHost, s.stream);
     }
     const hipError_t e2 = hipStreamSynchronize(s.stream);
-    (void)hipFree(buf);
     TMPT_HIP(e);
     TMPT_HIP(e2);
     return 0;
@@ -1075,19 +1069,19 @@ int radix_sort_host(Scene& s, uint32_t* keys, uint32_t* vals, int32_t n, int bit
 namespace {
 
 // Leaf-ordered triangle records and the top-down collapse of one binary tree
-// (Karras or PLOC) to the BVH4Q in s.nodes4, one launch per level.  Returns 0,
+// (Karras or PLOC) to the BVH4Q in bvh.nodes4, one launch per level.  Returns 0,
 // -1 (HIP or memory error), or 1: the tree is too deep for the traversal stack
 // (the levels stop as soon as that is known, so a chain of n nodes costs
 // kStackTotal / 3 launches, not n / 3).
 template <class Alloc>
-int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2* trange, Soa6 leaf,
-                  const uint32_t* tvals, Soa6 tib, int troot, int2* fr0, int2* fr1, uint32_t* c4, Alloc& alloc)
+int collapse_bvh4(Bvh& bvh, const Options& opt, hipStream_t st, const float* d_tris9, const int2* tchild,
+                  const int2* trange, Soa6 leaf, const uint32_t* tvals, Soa6 tib, int troot, int2* fr0, int2* fr1,
+                  uint32_t* c4, Alloc& alloc)
 {
-    const int32_t n = s.n, m = s.n_nodes;
-    hipStream_t st = s.stream;
-    k_tri_pre<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, tvals, s.tri_pre);
-    const int leaf_max = s.opt.leaf_max;
-    s.leaf_max = leaf_max;
+    const int32_t n = bvh.n, m = bvh.n_nodes;
+    k_tri_pre<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, tvals, bvh.tri_pre);
+    const int leaf_max = opt.leaf_max;
+    bvh.leaf_max = leaf_max;
     // the links' layout (tmpt_internal.h link_layout): the leaf fields as wide as
     // this scene needs; a node index never needs more (n_nodes4 <= m < n)
     const LinkLayout ll = link_layout((uint32_t)n, leaf_max, (uint32_t)m);
@@ -1095,15 +1089,15 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
         set_error("build_lbvh: too many triangles for a 32-bit child link");
         return -1;
     }
-    s.count_shift = ll.count_shift;
-    s.link_bits = ll.link_bits;
+    bvh.count_shift = ll.count_shift;
+    bvh.link_bits = ll.link_bits;
     // collapse=1: SAH-optimal collapse (fewer, fuller nodes: 13.2k vs 16.7k
     // on the sponza stand-in, but measured ~2% slower there); default greedy
     // largest-area opening
-    const bool sah = s.opt.collapse == 1 && n >= 2;
+    const bool sah = opt.collapse == 1 && n >= 2;
     uint32_t* dec = nullptr;
     if (sah) {
-        const SahCost cost{1.0f, s.opt.sah_c_leaf, s.opt.sah_c_tri};
+        const SahCost cost{1.0f, opt.sah_c_leaf, opt.sah_c_tri};
         int32_t* ord = (int32_t*)alloc((size_t)m * 4);
         float4* Fc = (float4*)alloc((size_t)m * sizeof(float4));
         dec = (uint32_t*)alloc((size_t)m * 4);
@@ -1131,21 +1125,21 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
     int2 *fa = fr0, *fb = fr1;
     // level L's nodes are [level_begin[L], level_begin[L + 1]): the running node
     // count after every launch (the refit runs one launch per range, deepest first)
-    s.level_begin.assign({0, 1});
+    bvh.level_begin.assign({0, 1});
     while (nf > 0) {
         k_bvh4_level<<<blocks_for(nf, kBlock), kBlock, 0, st>>>(tchild, trange, leaf, tvals, tib, fa, nf,
-                                                                fb, c4, s.nodes4, leaf_max, n, dec,
-                                                                ll.count_shift, s.node_box);
+                                                                fb, c4, bvh.nodes4, leaf_max, n, dec,
+                                                                ll.count_shift, bvh.node_box);
         ++levels;
         if (hipMemcpyAsync(hc, c4, sizeof(hc), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) return -1;
         nf = (int)hc[1];
-        if (nf > 0) s.level_begin.push_back((int32_t)hc[0]);
+        if (nf > 0) bvh.level_begin.push_back((int32_t)hc[0]);
         hc[1] = 0;
         if (hipMemcpyAsync(c4 + 1, &hc[1], 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
         std::swap(fa, fb);
-        s.n_nodes4 = (int32_t)hc[0];
-        s.depth4 = levels;
+        bvh.n_nodes4 = (int32_t)hc[0];
+        bvh.depth4 = levels;
         if (3 * levels + 1 > kStackTotal) return 1;
     }
     return 0;
@@ -1153,41 +1147,37 @@ int collapse_bvh4(Scene& s, const float* d_tris9, const int2* tchild, const int2
 
 }  // namespace
 
-int build_lbvh(Scene& s, const float* d_tris9)
+int build_lbvh(Bvh& bvh, const Options& opt, hipStream_t st, const float* d_tris9)
 {
-    const int32_t n = s.n;
-    hipStream_t st = s.stream;
+    const int32_t n = bvh.n;
     auto t0 = std::chrono::steady_clock::now();
     const int32_t m = n >= 2 ? n - 1 : 1;  // internal nodes
-    s.n_nodes = m;
-    TMPT_HIP(hipMalloc(&s.nodes4, sizeof(Bvh4Node) * (size_t)m));
+    bvh.n_nodes = m;
+    const auto oom = []() { return (set_error("build_lbvh: out of device memory"), -1); };
+    if (!bvh.nodes4.alloc(sizeof(Bvh4Node) * (size_t)m)) return oom();
     // one extra slot: the null triangle (all zero: det = 0, never accepted) that
     // empty BVH4 child slots link to
-    TMPT_HIP(hipMalloc(&s.tri_pre, sizeof(TriPre) * ((size_t)n + 1)));
-    TMPT_HIP(hipMemsetAsync(s.tri_pre + n, 0, sizeof(TriPre), st));
-    TMPT_HIP(hipMalloc(&s.tri_orig, sizeof(TriOrig) * (size_t)std::max(n, 1)));
+    if (!bvh.tri_pre.alloc(sizeof(TriPre) * ((size_t)n + 1))) return oom();
+    TMPT_HIP(hipMemsetAsync(bvh.tri_pre + n, 0, sizeof(TriPre), st));
+    if (!bvh.tri_orig.alloc(sizeof(TriOrig) * (size_t)std::max(n, 1))) return oom();
     // every node's own exact f32 box (24 B): what a refit reads of an internal
     // child, and bvh_cost's root area
-    TMPT_HIP(hipMalloc(&s.node_box, 6 * sizeof(float) * (size_t)m));
-    s.level_begin.clear();
+    if (!bvh.node_box.alloc(6 * sizeof(float) * (size_t)m)) return oom();
+    bvh.level_begin.clear();
     if (n == 0) {
-        TMPT_HIP(hipMemsetAsync(s.nodes4, 0, sizeof(Bvh4Node), st));
-        s.max_depth = 0;
+        TMPT_HIP(hipMemsetAsync(bvh.nodes4, 0, sizeof(Bvh4Node), st));
+        bvh.max_depth = 0;
         return 0;
     }
     // scratch
     const int nb_sort = blocks_for(n, kSortTile);
     size_t nn = (size_t)n;
-    std::vector<void*> tmp;
+    std::vector<DeviceBuffer<>> tmp;  // freed below before the SoA planes are made, and on every early return
     auto alloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        tmp.push_back(p);
-        return p;
-    };
-    auto free_all = [&]() {
-        for (void* p : tmp) (void)hipFree(p);
-        tmp.clear();
+        DeviceBuffer<> b;
+        if (!b.alloc(std::max<size_t>(bytes, 16))) return nullptr;
+        tmp.push_back(std::move(b));
+        return tmp.back().get();
     };
     float* leafbuf = (float*)alloc(6 * nn * sizeof(float));
     float* ibbuf = (float*)alloc(6 * (size_t)m * sizeof(float));
@@ -1209,9 +1199,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
     int32_t* maxd = (int32_t*)alloc(4);
     if (!leafbuf || !ibbuf || !cent || !cb || !k0 || !v0 || !k1 || !v1 || !hist || !child ||
         !range || !fr0 || !fr1 || !c4 || !pint || !pleaf || !depth || !maxd) {
-        free_all();
-        set_error("build_lbvh: out of device memory");
-        return -1;
+        return oom();
     }
     Soa6 leaf{leafbuf, leafbuf + nn, leafbuf + 2 * nn, leafbuf + 3 * nn, leafbuf + 4 * nn,
               leafbuf + 5 * nn};
@@ -1222,7 +1210,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
     do {
         if (hipMemcpyAsync(cb, init, sizeof(init), hipMemcpyHostToDevice, st) != hipSuccess) { rc = -1; break; }
         if (hipMemsetAsync(maxd, 0, 4, st) != hipSuccess) { rc = -1; break; }
-        k_tri_prep<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, s.tri_orig, leaf, cent, cb);
+        k_tri_prep<<<blocks_for(n, kBlock), kBlock, 0, st>>>(d_tris9, n, bvh.tri_orig, leaf, cent, cb);
         k_morton<<<blocks_for(n, kBlock), kBlock, 0, st>>>(cent, n, cb, k0, v0);
         uint32_t *ki = k0, *vi = v0, *ko = k1, *vo = v1;
         for (int pass = 0; pass < 4; ++pass) {
@@ -1233,16 +1221,16 @@ int build_lbvh(Scene& s, const float* d_tris9)
             std::swap(vi, vo);
         }
         // sorted (ki, vi)
-        const bool ploc = s.opt.builder == 0 && n > 1;
+        const bool ploc = opt.builder == 0 && n > 1;
         if (n == 1) {
-            s.max_depth = 0;
+            bvh.max_depth = 0;
         } else {
             k_karras<<<blocks_for(m, kBlock), kBlock, 0, st>>>(ki, n, child, range, pint, pleaf);
         k_depth<<<blocks_for(m, kBlock), kBlock, 0, st>>>(pint, m, depth, maxd);
         int32_t hmax = 0;
         if (hipMemcpyAsync(&hmax, maxd, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) { rc = -1; break; }
-        s.max_depth = hmax;
+        bvh.max_depth = hmax;
         if (hmax + 2 > kStackTotal) {
             set_error("build_lbvh: tree depth " + std::to_string(hmax) + " exceeds the traversal stack");
             rc = -2;
@@ -1259,7 +1247,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
         int troot = n == 1 ? ~0 : 0;
         std::function<int(int)> run_ploc;
         if (ploc) {
-            const int r = s.opt.ploc_radius;  // search radius; node visits vs r measured in DESIGN.md
+            const int r = opt.ploc_radius;  // search radius; node visits vs r measured in DESIGN.md
             int32_t* cidA = (int32_t*)alloc(nn * 4);
             int32_t* cidB = (int32_t*)alloc(nn * 4);
             float* cbAb = (float*)alloc(6 * nn * 4);
@@ -1286,7 +1274,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
             Soa6 cbA = soa(cbAb, nn), cbB = soa(cbBb, nn), pib = soa(pibb, mm);
             // one PLOC build over the sorted leaves into pchild / prange / pib /
             // pvals; pair: k_ploc_nn's rule for equal areas
-            run_ploc = [=, &s](int pair) mutable -> int {
+            run_ploc = [=, &bvh](int pair) mutable -> int {
                 if (hipMemsetAsync(pcounter, 0, 4, st) != hipSuccess || hipMemsetAsync(poff, 0, mm * 4, st) != hipSuccess)
                     return -1;
                 k_ploc_init<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, leaf, vi, cidA, cbA);
@@ -1313,7 +1301,7 @@ int build_lbvh(Scene& s, const float* d_tris9)
                     k_ploc_offsets<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, k, piter, pchild, psize, poff, new_slot);
                 k_ploc_relabel<<<blocks_for(m, kBlock), kBlock, 0, st>>>(m, pchild, poff, psize, prange, new_slot);
                 k_ploc_vals<<<blocks_for(n, kBlock), kBlock, 0, st>>>(n, new_slot, vi, pvals);
-                s.ploc_iters = it;
+                bvh.ploc_iters = it;
                 return 0;
             };
             rc = run_ploc(0);
@@ -1333,31 +1321,31 @@ int build_lbvh(Scene& s, const float* d_tris9)
         // larger boxes around one point) chain under either rule: then the
         // Karras tree, already built and bounded in depth by the key and index
         // bits, is collapsed instead, and builder_iters = 0 says so.
-        int crc = collapse_bvh4(s, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
+        int crc = collapse_bvh4(bvh, opt, st, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
         if (crc == 1 && ploc) {
             crc = run_ploc(1);
-            if (crc == 0) crc = collapse_bvh4(s, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
+            if (crc == 0) crc = collapse_bvh4(bvh, opt, st, d_tris9, tchild, trange, leaf, tvals, tib, troot, fr0, fr1, c4, alloc);
         }
         if (crc == 1 && ploc) {
-            s.ploc_iters = 0;
-            crc = collapse_bvh4(s, d_tris9, child, range, leaf, vi, ib, 0, fr0, fr1, c4, alloc);
+            bvh.ploc_iters = 0;
+            crc = collapse_bvh4(bvh, opt, st, d_tris9, child, range, leaf, vi, ib, 0, fr0, fr1, c4, alloc);
         }
         if (crc == 1) {
-            set_error("build_lbvh: BVH4 depth exceeds the traversal stack (" + std::to_string(s.depth4) + " levels)");
+            set_error("build_lbvh: BVH4 depth exceeds the traversal stack (" + std::to_string(bvh.depth4) + " levels)");
             crc = -2;
         }
         rc = crc;
     } while (0);
     hipError_t e = hipGetLastError();
     hipError_t e2 = hipStreamSynchronize(st);
-    free_all();
+    tmp.clear();
     if (rc == -1 || e != hipSuccess || e2 != hipSuccess) {
         set_error(std::string("build_lbvh: ") + hipGetErrorString(e != hipSuccess ? e : e2));
         return -1;
     }
     if (rc) return rc;
-    if (s.opt.layout == 1 && build_soa(s)) return -1;
-    s.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (opt.layout == 1 && build_soa(bvh, st)) return -1;
+    bvh.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 

@@ -185,9 +185,9 @@ int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt
     // workspace: two colour planes, then the guide planes
     const size_t plane = sizeof(float4) * (size_t)n;
     if (ensure_ws(s, 3 * plane + sizeof(float) * (size_t)n)) return -1;
-    float4* pl[2] = {reinterpret_cast<float4*>(s.ws), reinterpret_cast<float4*>((char*)s.ws + plane)};
-    float4* g0 = reinterpret_cast<float4*>((char*)s.ws + 2 * plane);
-    float* g1 = reinterpret_cast<float*>((char*)s.ws + 3 * plane);
+    float4* pl[2] = {s.ws.as<float4>(), reinterpret_cast<float4*>(s.ws.as<char>() + plane)};
+    float4* g0 = reinterpret_cast<float4*>(s.ws.as<char>() + 2 * plane);
+    float* g1 = reinterpret_cast<float*>(s.ws.as<char>() + 3 * plane);
     tmpt_render_desc wd{};
     wd.flags = d->flags;
     wd.wait_stream = d->wait_stream;

@@ -60,7 +60,7 @@ int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float 
     if (ensure_counters(s)) return -1;
     TMPT_HIP(hipMemsetAsync(s.ties, 0, 2 * sizeof(unsigned long long), s.stream));
     TMPT_HIP(hipMemsetAsync(s.counters + kCrackCounter, 0, sizeof(unsigned long long), s.stream));
-    const bool soa = s.soa.na != nullptr;
+    const bool soa = s.bvh.soa.na != nullptr;
     // one range starting behind the origin takes the NEG slack too
     const bool neg1 = !ranged && tmin < 0.0f;
     auto fn = soa ? (ranged ? (any ? k_intersect<true, true, kBlk, kSL, true> : k_intersect<false, true, kBlk, kSL, true>)
@@ -75,7 +75,7 @@ int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float 
     grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (n + kBlk - 1) / kBlk));
     size_t ovf_bytes = (size_t)grid * kBlk * (kStackTotal - kSL) * sizeof(uint32_t);
     if (ensure_ws(s, ovf_bytes)) return -1;
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), d_rays, n, tmin, tmax, d_hits, d_ids, (uint32_t*)s.ws);
+    fn<<<grid, kBlk, 0, s.stream>>>(view(s), d_rays, n, tmin, tmax, d_hits, d_ids, s.ws.as<uint32_t>());
     TMPT_HIP(hipGetLastError());
     TMPT_HIP(hipMemcpyAsync(s.counters_host + kTieCounter, s.ties, 2 * sizeof(unsigned long long),
                             hipMemcpyDeviceToHost, s.stream));

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "tmpt_device.h"
 #include "tmpt_math.h"
 
 namespace tmpt {
@@ -388,45 +389,64 @@ int options_parse(Options& o, const char* text, bool allow_build);
 int options_set(Options& o, const char* key, double value, bool allow_build);
 int options_get(const Options& o, const char* key, double* value);
 
-struct Scene {
-    int device = 0;
+// What a BVH build makes (build_lbvh, build_soa) and a refit rewrites: built
+// into a local one and moved into the scene on success (tmpt_scene_update).
+struct Bvh {
     int32_t n = 0;          // triangles incl. the floor
     int32_t n_nodes = 0;    // internal nodes of the binary tree the BVH4 is collapsed from
     int32_t max_depth = 0;  // of the LBVH (Karras builder)
-    Bvh4Node* nodes4 = nullptr;
+    DeviceBuffer<Bvh4Node> nodes4;
     int32_t n_nodes4 = 0, depth4 = 0, leaf_max = 0, ploc_iters = 0;
     int32_t count_shift = 0, link_bits = 31;  // the links' layout (link_layout), fixed by the build
-    TriPre* tri_pre = nullptr;
-    TriOrig* tri_orig = nullptr;
-    void* soa_buf = nullptr;  // layout=soa: the planes of SoaScene, one allocation
+    DeviceBuffer<TriPre> tri_pre;
+    DeviceBuffer<TriOrig> tri_orig;
+    DeviceBuffer<> soa_buf;  // layout=soa: the planes of SoaScene, one allocation
     SoaScene soa;
-    std::vector<float> tris_host;  // the triangles as given (Scene::Scene keeps its copy too)
     // scene updates (tmpt_scene_update): BVH4 level L is nodes [level_begin[L],
     // level_begin[L + 1]) (depth4 + 1 entries); every node's own exact f32 box
     // (6 floats per node, written by the build and by every refit); the padded
     // box of every leaf-ordered record (6 floats, a refit's scratch, allocated
-    // by the first one); the last update's kind (0 none, 1 refit, 2 rebuild) and
-    // device time; option bvh_cost's cached value (valid: cost_known)
+    // by the first one)
     std::vector<int32_t> level_begin;
-    float* node_box = nullptr;
-    float* rec_box = nullptr;
-    int32_t update_kind = 0;
-    double update_ms = 0.0;
-    double cost = 0.0;
-    bool cost_known = false;
-    hipEvent_t update_ev[2] = {nullptr, nullptr};
-    // the reference's octree (tmpt_scene_build_octree), and the counter of
-    // closest-hit queries answered through it in the current call
-    OctNode* oct = nullptr;
-    int32_t* oct_refs = nullptr;
-    OctView* oct_view = nullptr;  // device copy of {oct, oct_refs, n_oct, ties}
+    DeviceBuffer<float> node_box;
+    DeviceBuffer<float> rec_box;
+    double build_ms = 0.0;
+};
+
+// The reference's octree on the device (tmpt_scene_build_octree): built into a
+// local one and moved into the scene on success; Octree{} drops it.
+struct Octree {
+    DeviceBuffer<OctNode> oct;
+    DeviceBuffer<int32_t> oct_refs;
+    DeviceBuffer<OctView> oct_view;  // device copy of {oct, oct_refs, n_oct, ties}
     int32_t n_oct = 0, oct_leaves = 0, oct_depth = 0;
     int32_t oct_flat = 0;  // triangles flat on one of the octree's planes (OctView::flat)
     OctGrid oct_grid{};    // its crack grid (OctView::grid)
     int64_t n_oct_refs = 0;
     double oct_build_ms = 0.0;
     float oct_lo[3] = {0, 0, 0}, oct_hi[3] = {0, 0, 0};
-    unsigned long long* ties = nullptr;  // [0] re-answered ties, [1] root-box misses
+};
+
+// Every buffer, event and stream below is an owner (tmpt_device.h): deleting
+// the scene releases them, in reverse order of declaration -- the streams,
+// declared first, last.  DESIGN.md "Owners" lists the kept buffers' budgets.
+struct Scene {
+    int device = 0;
+    Stream stream;
+    Stream rs_stream[kRowSpecMaxGroups];  // speculative row seeding: one per row group
+    Bvh bvh;
+    std::vector<float> tris_host;  // the triangles as given (Scene::Scene keeps its copy too)
+    // the last update's kind (0 none, 1 refit, 2 rebuild) and device time;
+    // option bvh_cost's cached value (valid: cost_known)
+    int32_t update_kind = 0;
+    double update_ms = 0.0;
+    double cost = 0.0;
+    bool cost_known = false;
+    Event update_ev[2];
+    // the reference's octree, and the counter of closest-hit queries answered
+    // through it in the current call
+    Octree octree;
+    unsigned long long* ties = nullptr;  // [0] re-answered ties, [1] root-box misses (inside counters)
     uint64_t tie_queries = 0, root_misses = 0, crack_queries = 0;
     // row seeding: the engine of the last render (0 none, 1 one lane per row,
     // 2 iterated speculative, 3 streaming) and whether the streaming engine's
@@ -434,58 +454,49 @@ struct Scene {
     int32_t row_engine = 0, stream_fallbacks = 0;
     int64_t chain_pixels = 0;  // pixel seeding: pixels of the last render run as speculative chains
     Options opt;  // build and render options (tmpt_scene_create_ex / tmpt_scene_set_option)
-    hipEvent_t wait_ev = nullptr;  // TMPT_FLAG_WAIT_STREAM: reused across renders
-    unsigned long long* counters = nullptr;       // a render's ray / visit counters (device)
-    unsigned long long* counters_host = nullptr;  // their pinned host copy
-    uint32_t* chk = nullptr;  // the checked build's device word triple (kChk* codes), else unused
-    hipEvent_t render_ev[2] = {nullptr, nullptr}; // first / last kernel of a render
-    hipStream_t stream = nullptr;
-    double build_ms = 0.0;
-    // render workspace (grown on demand, reused across calls)
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
-    // progressive spp: per-pixel {colour sum xyz, rng} of the last pass, and the
-    // shard it belongs to (width, height, spp, band_rows, shard, num_shards, next sample)
-    float4* prog = nullptr;
-    size_t prog_slots = 0;
+    Event wait_ev;  // TMPT_FLAG_WAIT_STREAM: reused across renders
+    DeviceBuffer<unsigned long long> counters;       // a render's ray / visit counters (device)
+    PinnedBuffer<unsigned long long> counters_host;  // their pinned host copy
+    DeviceBuffer<uint32_t> chk;  // the checked build's device word triple (kChk* codes), else unused
+    Event render_ev[2];          // first / last kernel of a render
+    DeviceBuffer<> ws;           // render workspace, kept and grown on demand
+    // progressive spp: per-pixel {colour sum xyz, rng} of the last pass (kept,
+    // grown), and the shard it belongs to (width, height, spp, band_rows,
+    // shard, num_shards, next sample)
+    DeviceBuffer<float4> prog;
     int32_t prog_key[7] = {0, 0, 0, 0, 0, 0, -1};
     uint64_t prog_cam = 0;  // FNV-1a of the camera (and seed mode) of that pass
     // sample seeding: sample_seed's jump tables for samples [0, jt_spp), and the
-    // per-sample colour buffer of block-split pixels (tmpt_render.hip k_resolve)
-    uint32_t* jt = nullptr;
+    // per-sample colour buffer of block-split pixels (tmpt_render.hip k_resolve; kept, grown)
+    DeviceBuffer<uint32_t> jt;
     int32_t jt_spp = 0;
-    float4* sbuf = nullptr;
-    size_t sbuf_bytes = 0;
+    DeviceBuffer<float4> sbuf;
     // the camera pre-pass's entries (tmpt_render.hip k_cam_rays; 32 B per sample
-    // of a pass), kept and grown like sbuf, and whether the last render ran it
-    void* cam_rays = nullptr;
-    size_t cam_bytes = 0;
+    // of a pass; kept, grown), and whether the last render ran it
+    DeviceBuffer<> cam_rays;
     int32_t cam_rays_used = 0;
     // the shadow split's queue (16 B per entry) and sample records (64 B per
-    // sample of a pass), kept and grown like sbuf; whether the last render ran
-    // it, its passes, and its kernels' times
-    void* split_buf = nullptr;
-    size_t split_bytes = 0;
+    // sample of a pass; kept, grown); whether the last render ran it, its
+    // passes, and its kernels' times
+    DeviceBuffer<> split_buf;
     int32_t split_used = 0, split_passes = 0;
     // a shadow-split render in several passes of samples (render_split_passes):
     // the pixels' float sums carried from pass to pass (RenderArgs::prog of
-    // its passes; non-null only while such a render runs) and the passes'
-    // summed statistics
-    float4* split_carry = nullptr;
-    size_t split_carry_slots = 0;
+    // its passes; kept, grown) and the passes' summed statistics
+    DeviceBuffer<float4> split_carry;
     bool split_sub = false;
     struct SplitAcc {
         double extend_ms = 0.0, shadow_ms = 0.0, resolve_ms = 0.0, redo_ms = 0.0;
         int64_t redo_samples = 0, redo_late = 0;
         int32_t redo_launches = 0, launches = 0, used = 0;
     } split_acc;
-    hipEvent_t split_ev[3] = {nullptr, nullptr, nullptr};  // before k_shadow, between, after k_split_resolve
+    Event split_ev[3];  // before k_shadow, between, after k_split_resolve
     double split_resolve_ms = 0.0;
     // deferred ties (PathCtl::redo): the redo list, its capacity in entries,
     // and the samples the last render left to the redo pass
-    uint2* redo = nullptr;
+    DeviceBuffer<uint2> redo;
     uint32_t redo_cap = 0;
-    float4* redo_state = nullptr;  // per redo slot: where its path stopped (tmpt_render.hip kRedoState4)
+    DeviceBuffer<float4> redo_state;  // per redo slot: where its path stopped (tmpt_render.hip kRedoState4)
     int64_t redo_samples = 0;
     int64_t redo_late = 0;   // of them, left by the launch's tail to the k_redo launch
     int32_t redo_launches = 0;  // k_redo launches of the last render
@@ -495,36 +506,33 @@ struct Scene {
     double redo_ms = 0.0;       // and their time (not in extend_ms)
     uint64_t redo_rays = 0;     // and their rays (in the render's count)
     // speculative row seeding (tmpt_rows.hip render_rowspec): jump tables
-    // M^(2j) for j in [0, jt2_n), and its row/unit buffers
-    uint32_t* jt2 = nullptr;
+    // M^(2j) for j in [0, jt2_n), and its row/unit buffers (kept, grown)
+    DeviceBuffer<uint32_t> jt2;
     int32_t jt2_n = 0;
-    void* rs_buf = nullptr;
-    size_t rs_bytes = 0;
-    hipStream_t rs_stream[kRowSpecMaxGroups] = {};      // one per row group
-    hipEvent_t rs_event[kRowSpecMaxGroups + 1] = {};    // group ends; [max]: the start
-    uint32_t* rs_host = nullptr;                        // pinned: each group's last unit count
-    void* rs_list = nullptr;                            // no-shadow speculation: the chain list
-    size_t rs_list_bytes = 0;
-    // streaming row engine (render_rowstream): rings, windows, anchors; its
-    // jump tables (M^(2c), M^(256b), M^(2^15 a0), M^(2^20 a1)); pinned control words
-    void* rss_buf = nullptr;
-    size_t rss_bytes = 0;
-    uint32_t* rss_tab = nullptr;
-    uint32_t* rss_host = nullptr;
+    DeviceBuffer<> rs_buf;
+    Event rs_event[kRowSpecMaxGroups + 1];  // group ends; [max]: the start
+    PinnedBuffer<uint32_t> rs_host;         // each group's last unit count
+    DeviceBuffer<> rs_list;                 // no-shadow speculation: the chain list (kept, grown)
+    // streaming row engine (render_rowstream): rings, windows, anchors (kept,
+    // grown); its jump tables (M^(2c), M^(256b), M^(2^15 a0), M^(2^20 a1));
+    // pinned control words
+    DeviceBuffer<> rss_buf;
+    DeviceBuffer<uint32_t> rss_tab;
+    PinnedBuffer<uint32_t> rss_host;
     // adaptive sampling (tmpt_adaptive.hip render_adaptive): set around each of
     // its passes for render_persistent -- adapt_on: the pass keeps its samples
     // in the colour buffer and resolves nothing; adapt_list / adapt_n: the
-    // pixels of a pass after the first (device list of tile slots, ascending)
-    // -- and the call's buffers (per-pixel state, the two lists, the block
-    // masks and counts), grown like sbuf, with the pinned next-list length
+    // pixels of a pass after the first (device list of tile slots, ascending,
+    // inside adapt_buf) -- and the call's buffers (per-pixel state, the two
+    // lists, the block masks and counts; kept, grown), with the pinned
+    // next-list length
     bool adapt_on = false;
     const uint32_t* adapt_list = nullptr;
     int64_t adapt_n = 0;
-    void* adapt_buf = nullptr;
-    size_t adapt_bytes = 0;
-    uint32_t* adapt_host = nullptr;
+    DeviceBuffer<> adapt_buf;
+    PinnedBuffer<uint32_t> adapt_host;
     int path_launches = 1;  // k_path launches of the last persistent render (pilot ordering: 2)
-    hipEvent_t path_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the pilot / final k_path
+    Event path_ev[4];       // around the pilot / final k_path
     // statistics of the last render
     double render_ms = 0.0;
     double extend_ms = 0.0;
@@ -548,13 +556,24 @@ const char* last_error();
         }                                                                               \
     } while (0)
 
+// an owner's alloc / reserve (tmpt_device.h) that must succeed
+#define TMPT_ALLOC(ok, what)                                                            \
+    do {                                                                                \
+        if (!(ok)) {                                                                    \
+            ::tmpt::set_error(std::string(what) + ": out of device memory");            \
+            return -1;                                                                  \
+        }                                                                               \
+    } while (0)
+
 // tmpt_bvh.hip
-int build_lbvh(Scene& s, const float* d_tris9);
-int build_soa(Scene& s);  // layout=soa planes from the built AoS records
-// tmpt_scene_update's refit: the built tree fitted to the scene's n new
-// triangles (device, 9 floats each), launched on the scene's stream; and
-// option bvh_cost, tests/bvh_check.py cost() by a float64 reduction kernel
-int refit_bvh(Scene& s, const float* d_tris9);
+// the build of bvh.n triangles (device, 9 floats each) into an empty Bvh, on a
+// stream the caller owns
+int build_lbvh(Bvh& bvh, const Options& opt, hipStream_t st, const float* d_tris9);
+int build_soa(Bvh& bvh, hipStream_t st);  // layout=soa planes from the built AoS records
+// tmpt_scene_update's refit: the built tree fitted to its n new triangles
+// (device, 9 floats each), launched on st; and option bvh_cost,
+// tests/bvh_check.py cost() by a float64 reduction kernel
+int refit_bvh(Bvh& bvh, hipStream_t st, const float* d_tris9);
 int bvh_cost(Scene& s, double* out);
 // the octree's flat triangles marked in the leaf-ordered records (bit 0 of the
 // doubled index), the others cleared; flat has s.n entries (empty: clear all)

@@ -70,7 +70,7 @@ int launch_mega(Scene& s, const RenderArgs& a, uint32_t* out, unsigned long long
     grid = std::max(grid, 1);
     size_t ovf_bytes = (size_t)grid * kBlk * (kStackTotal - kSL) * sizeof(uint32_t);
     if (ensure_ws(s, ovf_bytes)) return -1;
-    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a, out, (uint32_t*)s.ws, counters);
+    fn<<<grid, kBlk, 0, s.stream>>>(view(s), a, out, s.ws.as<uint32_t>(), counters);
     TMPT_HIP(hipGetLastError());
     return 0;
 }

@@ -133,6 +133,8 @@ SceneView view(const Scene& s);
 RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d);
 // sample_seed's jump tables on the device for samples [0, spp) (Scene::jt, grown, never shrunk)
 int ensure_sample_tables(Scene& s, int32_t spp, const char* what);
+// a jump table uploaded into a new buffer that replaces dst's on success
+int upload_tables(DeviceBuffer<uint32_t>& dst, const std::vector<uint32_t>& tab, const char* what);
 // TMPT_FLAG_WAIT_STREAM: the scene's stream waits for the work enqueued on d->wait_stream
 int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what);
 // RenderArgs::root_check of a camera: 1 unless no octree answers (none built,

@@ -263,18 +263,15 @@ __global__ void __launch_bounds__(BLOCK) k_redo(SceneView sv, RenderArgs a, uint
 // the deferred-tie list and its per-slot state (freed together)
 static void free_redo(Scene& s)
 {
-    if (s.redo) (void)hipFree(s.redo);
-    if (s.redo_state) (void)hipFree(s.redo_state);
-    s.redo = nullptr;
-    s.redo_state = nullptr;
+    s.redo.reset();
+    s.redo_state.reset();
     s.redo_cap = 0;
 }
 static bool alloc_redo(Scene& s, int64_t cap)
 {
     free_redo(s);
-    if (hipMalloc(&s.redo, sizeof(uint2) * (size_t)cap) != hipSuccess ||
-        hipMalloc(&s.redo_state, sizeof(float4) * kRedoState4 * (size_t)cap) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!s.redo.alloc(sizeof(uint2) * (size_t)cap) ||
+        !s.redo_state.alloc(sizeof(float4) * kRedoState4 * (size_t)cap)) {
         free_redo(s);
         return false;
     }
@@ -1856,13 +1853,9 @@ int occupancy_grid(const void* fn, int block, size_t dyn_lds, int device)
 
 int ensure_ws(Scene& s, size_t bytes)
 {
-    if (s.ws_bytes >= bytes) return 0;
-    if (s.ws) (void)hipFree(s.ws);
-    s.ws = nullptr;
-    s.ws_bytes = 0;
-    TMPT_HIP(hipMalloc(&s.ws, bytes));
-    s.ws_bytes = bytes;
-    return 0;
+    if (s.ws.reserve(bytes)) return 0;
+    set_error("render: out of device memory (workspace)");
+    return -1;
 }
 
 // SceneView::any_w from option shadow_order: the weight of a child's exit
@@ -1889,11 +1882,11 @@ static bool pop_cull_on(const Scene& s)
 
 SceneView view(const Scene& s)
 {
-    SceneView v{s.nodes4, s.tri_pre, s.tri_orig, s.n, s.n_nodes4};
-    v.soa = s.soa;
+    SceneView v{s.bvh.nodes4, s.bvh.tri_pre, s.bvh.tri_orig, s.bvh.n, s.bvh.n_nodes4};
+    v.soa = s.bvh.soa;
     v.any_w = shadow_order_weight(s.opt, s.row_render);
-    v.count_shift = (uint32_t)s.count_shift;
-    v.key_mask = pop_cull_on(s) ? pop_key_mask(pop_key_bits(s.link_bits, s.opt.pop_key_cap)) : 0u;
+    v.count_shift = (uint32_t)s.bvh.count_shift;
+    v.key_mask = pop_cull_on(s) ? pop_key_mask(pop_key_bits(s.bvh.link_bits, s.opt.pop_key_cap)) : 0u;
 #ifdef TMPT_CHECK
     v.chk = s.chk;
     // TMPT_CHECK_SELFTEST=1 (the report's own test, tests/test_gpu_check.py):
@@ -1902,9 +1895,9 @@ SceneView view(const Scene& s)
     if (const char* e = getenv("TMPT_CHECK_SELFTEST"))
         if (atoi(e) == 1) v.n_nodes4 = std::min(v.n_nodes4, 1);
 #endif
-    if (s.oct && s.opt.tie_rule == 0) {  // the reference's visit order for ties
-        v.oct = s.oct_view;
-        const OctGrid& g = s.oct_grid;
+    if (s.octree.oct && s.opt.tie_rule == 0) {  // the reference's visit order for ties
+        v.oct = s.octree.oct_view;
+        const OctGrid& g = s.octree.oct_grid;
         v.crack = make_float4(g.reach, g.drift[0], g.drift[1], g.drift[2]);
     }
     return v;
@@ -2022,12 +2015,12 @@ uint32_t top_walk_cap(const Options& o, int seeding)
 // the test is the device's own.
 uint32_t oct_shadow_check(const Scene& s)
 {
-    if (!s.oct_view || s.opt.tie_rule != 0) return 0u;
-    if (s.oct_flat > 0) return 1u;
+    if (!s.octree.oct_view || s.opt.tie_rule != 0) return 0u;
+    if (s.octree.oct_flat > 0) return 1u;
     const f3 ld = light_dir();
     const float l[3] = {fabsf(ld.x), fabsf(ld.y), fabsf(ld.z)};
     for (int k = 0; k < 3; ++k)
-        if (l[k] * fminf(kMinT, s.oct_grid.reach) <= s.oct_grid.drift[k]) return 1u;
+        if (l[k] * fminf(kMinT, s.octree.oct_grid.reach) <= s.octree.oct_grid.drift[k]) return 1u;
     return 0u;
 }
 
@@ -2065,9 +2058,7 @@ static size_t split_need(int64_t n, int64_t waves, uint32_t& sq_cap)
 // memory that is free or already the buffer's
 static size_t split_budget(const Scene& s)
 {
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-    const size_t half = (fr + s.split_bytes) / 2;
+    const size_t half = free_budget(1, 1, s.split_buf.bytes()) / 2;
     return s.opt.shadow_split_max > 0.0 ? (size_t)std::min((double)half, s.opt.shadow_split_max) : half;
 }
 static bool ensure_split(Scene& s, int64_t n, int64_t waves, uint32_t& sq_cap)
@@ -2075,37 +2066,17 @@ static bool ensure_split(Scene& s, int64_t n, int64_t waves, uint32_t& sq_cap)
     const size_t need = split_need(n, waves, sq_cap);
     if (need == 0) return false;
     if (s.opt.shadow_split_max > 0.0 && (double)need > s.opt.shadow_split_max) return false;
-    if (s.split_bytes >= need) return true;
+    if (s.split_buf.bytes() >= need) return true;
     if (need > split_budget(s)) return false;
-    if (s.split_buf) (void)hipFree(s.split_buf);
-    s.split_buf = nullptr;
-    s.split_bytes = 0;
-    if (hipMalloc(&s.split_buf, need) != hipSuccess) {
-        (void)hipGetLastError();
-        s.split_buf = nullptr;
-        return false;
-    }
-    s.split_bytes = need;
-    return true;
+    return s.split_buf.alloc(need);
 }
 
 static bool ensure_cam_rays(Scene& s, size_t need)
 {
     if (s.opt.cam_pre_max > 0.0 && (double)need > s.opt.cam_pre_max) return false;
-    if (s.cam_bytes >= need) return true;
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-    if (need > (fr + s.cam_bytes) / 2) return false;
-    if (s.cam_rays) (void)hipFree(s.cam_rays);
-    s.cam_rays = nullptr;
-    s.cam_bytes = 0;
-    if (hipMalloc(&s.cam_rays, need) != hipSuccess) {
-        (void)hipGetLastError();
-        s.cam_rays = nullptr;
-        return false;
-    }
-    s.cam_bytes = need;
-    return true;
+    if (s.cam_rays.bytes() >= need) return true;
+    if (need > free_budget(1, 1, s.cam_rays.bytes()) / 2) return false;
+    return s.cam_rays.alloc(need);
 }
 
 // Persistent path engine: one launch per frame (shard).
@@ -2115,14 +2086,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     const Options& o = s.opt;
     // HIP events around each k_path launch (pilot: 0-1, final: 2-3) on the
     // stream it runs on: the dominant kernel's own time for the roofline
-    if (!s.path_ev[0])
-        for (auto& e : s.path_ev) TMPT_HIP(hipEventCreate(&e));
+    for (auto& e : s.path_ev) TMPT_HIP(e.ensure());
     // Which k_path: the facts first, then one variant (PathVariant) from them.
     // Pixel seeding, and sample seeding (its own instantiations: the pixel-mode
     // kernel keeps its register allocation).
     const bool jt = a.jt != nullptr;
     // the reference's octree answers ties (tie_rule visit)
-    const bool oct = s.oct_view && o.tie_rule == 0;
+    const bool oct = s.octree.oct_view && o.tie_rule == 0;
     int prof = 0;
 #ifdef TMPT_DIAG
     // diagnostic build only: TMPT_PROF=1 s_memtime split of wave time (shading /
@@ -2142,7 +2112,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     // kernels read the AoS records.
     const bool list = s.adapt_list != nullptr;
     const int64_t npix = list ? s.adapt_n : a.slots;  // pixels the supply hands out
-    const bool soa = s.soa.na != nullptr && !list;
+    const bool soa = s.bvh.soa.na != nullptr && !list;
     const bool soa_kernel = jt && soa && !prof;
     // TMPT_PROF=2 in sample seeding: the shading split of the 5-wave kernel the
     // product runs (its LDS layout and 96 VGPRs), unless path_waves = 4
@@ -2259,9 +2229,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // progressive pass needs the buffer whatever its block count.
         if (nblk > 1 || pass) {
             const size_t need = sizeof(float4) * (size_t)a.spp * (size_t)a.slots;
-            size_t fr = 0, tot = 0;
-            size_t budget = hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0;
-            budget += s.sbuf_bytes;  // the buffer already held is free for this call
+            size_t budget = free_budget(3, 4, s.sbuf.bytes());  // the buffer already held is free for this call
             if (o.sbuf_max > 0.0) budget = std::min(budget, (size_t)o.sbuf_max);
             if (need > budget) {
                 if (pass) {
@@ -2353,7 +2321,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     const size_t reg_words = ordered ? 2 * (size_t)kSimdKeys + 64 + (size_t)P : 0;  // + claim words
     const size_t extra_words = ordered ? (size_t)P * (4 + 5) + hist_words + reg_words : 0;
     if (ensure_ws(s, (ovf_words + head_words + extra_words) * 4)) return -1;
-    uint32_t* heads = (uint32_t*)s.ws + ovf_words;
+    uint32_t* heads = s.ws.as<uint32_t>() + ovf_words;
     TMPT_HIP(hipMemsetAsync(heads, 0, head_words * 4, s.stream));
     PathCtl pc;
     memset(&pc, 0, sizeof(pc));
@@ -2373,13 +2341,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         as.bmask = nblk > 1 ? blk - 1u : 2047u;
         if (nblk > 1 || pass) {
             const size_t need = sizeof(float4) * (size_t)a.spp * (size_t)a.slots;
-            if (s.sbuf_bytes < need) {
-                if (s.sbuf) (void)hipFree(s.sbuf);
-                s.sbuf = nullptr;
-                s.sbuf_bytes = 0;
-                TMPT_HIP(hipMalloc(&s.sbuf, need));
-                s.sbuf_bytes = need;
-            }
+            TMPT_ALLOC(s.sbuf.reserve(need), "tmpt_render: the per-sample colour buffer");
             pc.sbuf = s.sbuf;
         }
     }
@@ -2461,9 +2423,9 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         const bool cam_on = waves5 && !help && cam_pre != 0 && ensure_cam_rays(s, sizeof(CamRay) * (size_t)cam_n);
         if (cam_on) {
             const uint32_t cnt = (uint32_t)(s1 - s0);
-            pc.cam_rays = static_cast<const CamRay*>(s.cam_rays);
+            pc.cam_rays = s.cam_rays.as<CamRay>();
             pc.cam_count = cnt;
-            launch_cam_rays(s, as, static_cast<CamRay*>(s.cam_rays), s.adapt_list, s.adapt_n);
+            launch_cam_rays(s, as, s.cam_rays.as<CamRay>(), s.adapt_list, s.adapt_n);
             TMPT_HIP(hipGetLastError());
             s.cam_rays_used = 1;
         }
@@ -2482,14 +2444,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                               (s.split_sub || (!pass && !a.prog)) && !oct_shadow &&
                               ensure_split(s, cam_n, (int64_t)grid5 * (kBlk / 64), sq_cap);
         if (split_on) {
-            uint32_t* ctl = static_cast<uint32_t*>(s.split_buf);
+            uint32_t* ctl = s.split_buf.as<uint32_t>();
             pc.sq_ctl = ctl;
             pc.sq = reinterpret_cast<uint4*>(ctl + kSplitCtlWords);
             pc.sq_cap = sq_cap;
             pc.srec = reinterpret_cast<float4*>(pc.sq + sq_cap);
             TMPT_HIP(hipMemsetAsync(ctl, 0, kSplitCtlWords * 4, s.stream));
-            if (!s.split_ev[0])
-                for (auto& e : s.split_ev) TMPT_HIP(hipEventCreate(&e));
+            for (auto& e : s.split_ev) TMPT_HIP(e.ensure());
             s.split_used = 1;
         }
         // the launch's kernel: flagged ties deferred (TIES 1) with the redo list,
@@ -2515,7 +2476,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             pc.redo_lanes = (uint32_t)std::max(1, std::min(64, o.redo_lanes));
             if (redo) TMPT_HIP(hipMemsetAsync(s.redo, 0xFF, sizeof(uint2) * (size_t)s.redo_cap, s.stream));
             TMPT_HIP(hipEventRecord(s.path_ev[2], s.stream));
-            fn_main<<<grid_main, kBlk, 0, s.stream>>>(view(s), as, pc, d_out, (uint32_t*)s.ws, d_counters);
+            fn_main<<<grid_main, kBlk, 0, s.stream>>>(view(s), as, pc, d_out, s.ws.as<uint32_t>(), d_counters);
             TMPT_HIP(hipGetLastError());
             TMPT_HIP(hipEventRecord(s.path_ev[3], s.stream));
             if (!redo) break;
@@ -2548,10 +2509,10 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                 if (split_on)
                     k_redo<kBlk, kPathSL, true><<<grid, kBlk, 0, s.stream>>>(view(s), as, s.redo, s.redo_cap,
                                                                             s.redo_state, pc.srec, pc.sb_ss, pc.sb_sp,
-                                                                            (uint32_t*)s.ws, d_counters);
+                                                                            s.ws.as<uint32_t>(), d_counters);
                 else
                     k_redo<kBlk, kPathSL><<<grid, kBlk, 0, s.stream>>>(view(s), as, s.redo, s.redo_cap, s.redo_state,
-                                                                      pc.sbuf, pc.sb_ss, pc.sb_sp, (uint32_t*)s.ws,
+                                                                      pc.sbuf, pc.sb_ss, pc.sb_sp, s.ws.as<uint32_t>(),
                                                                       d_counters);
                 TMPT_HIP(hipGetLastError());
                 TMPT_HIP(hipEventRecord(s.path_ev[1], s.stream));
@@ -2563,7 +2524,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
             // after k_path (and k_redo): the queued shadow queries, then the records
             TMPT_HIP(hipEventRecord(s.split_ev[0], s.stream));
             if (launch_shadow(s.stream, s.device, view(s), pc.sq, pc.sq_ctl, pc.sq_cap, pc.sq_ctl + kCtr, pc.srec,
-                              (uint32_t)cam_n, (uint32_t*)s.ws)) {
+                              (uint32_t)cam_n, s.ws.as<uint32_t>())) {
                 set_error("tmpt_render: k_shadow launch failed");
                 return -1;
             }
@@ -2610,7 +2571,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     a1.prog = state;
     pc.cost_out = cost;
     TMPT_HIP(hipEventRecord(s.path_ev[0], s.stream));
-    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a1, pc, d_out, (uint32_t*)s.ws, d_counters);
+    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a1, pc, d_out, s.ws.as<uint32_t>(), d_counters);
     TMPT_HIP(hipGetLastError());
     TMPT_HIP(hipEventRecord(s.path_ev[1], s.stream));
     k_order_keys<<<(unsigned)((P + 255) / 256), 256, 0, s.stream>>>(cost, a.W, a.tile_rows, keys, vals);
@@ -2689,7 +2650,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         pc.dprio_cost = cost;
     }
     TMPT_HIP(hipEventRecord(s.path_ev[2], s.stream));
-    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a2, pc, d_out, (uint32_t*)s.ws, d_counters);
+    fn<<<grid_px, kBlk, 0, s.stream>>>(view(s), a2, pc, d_out, s.ws.as<uint32_t>(), d_counters);
     TMPT_HIP(hipGetLastError());
     TMPT_HIP(hipEventRecord(s.path_ev[3], s.stream));
     s.path_launches = 2;
@@ -2707,14 +2668,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
 int ensure_counters(Scene& s)
 {
     if (s.counters) return 0;
-    TMPT_HIP(hipMalloc(&s.counters, kRenderCounters * sizeof(unsigned long long)));
+    TMPT_ALLOC(s.counters.alloc(kRenderCounters * sizeof(unsigned long long)), "render counters");
     TMPT_HIP(hipMemset(s.counters, 0, kRenderCounters * sizeof(unsigned long long)));
-    TMPT_HIP(hipHostMalloc((void**)&s.counters_host, kRenderCounters * sizeof(unsigned long long),
-                           hipHostMallocDefault));
-    for (auto& e : s.render_ev) TMPT_HIP(hipEventCreate(&e));
+    TMPT_HIP(s.counters_host.ensure(kRenderCounters * sizeof(unsigned long long)));
+    for (auto& e : s.render_ev) TMPT_HIP(e.ensure());
     s.ties = s.counters + kTieCounter;
 #ifdef TMPT_CHECK
-    TMPT_HIP(hipMalloc(&s.chk, 4 * sizeof(uint32_t)));
+    TMPT_ALLOC(s.chk.alloc(4 * sizeof(uint32_t)), "check words");
     TMPT_HIP(hipMemset(s.chk, 0, 4 * sizeof(uint32_t)));
 #endif
     return 0;
@@ -2748,20 +2708,24 @@ int check_report(Scene& s, const char* what)
 #endif
 }
 
+int upload_tables(DeviceBuffer<uint32_t>& dst, const std::vector<uint32_t>& tab, const char* what)
+{
+    DeviceBuffer<uint32_t> nt;
+    TMPT_ALLOC(nt.alloc(tab.size() * sizeof(uint32_t)), what);
+    if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error(std::string(what) + ": jump table upload failed");
+        return -1;
+    }
+    dst = std::move(nt);
+    return 0;
+}
+
 int ensure_sample_tables(Scene& s, int32_t spp, const char* what)
 {
     if (s.jt_spp >= spp) return 0;
     std::vector<uint32_t> tab;
     sample_jump_tables(spp, tab);
-    uint32_t* nt = nullptr;
-    TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-    if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(nt);
-        set_error(std::string(what) + ": jump table upload failed");
-        return -1;
-    }
-    if (s.jt) (void)hipFree(s.jt);
-    s.jt = nt;
+    if (int rc = upload_tables(s.jt, tab, what)) return rc;
     s.jt_spp = spp;
     return 0;
 }
@@ -2769,7 +2733,7 @@ int ensure_sample_tables(Scene& s, int32_t spp, const char* what)
 int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what)
 {
     if (!(d->flags & TMPT_FLAG_WAIT_STREAM)) return 0;  // order after the caller's stream (tmpt.h)
-    if (!s.wait_ev) TMPT_HIP(hipEventCreateWithFlags(&s.wait_ev, hipEventDisableTiming));
+    TMPT_HIP(s.wait_ev.ensure(hipEventDisableTiming));
     hipError_t e = hipEventRecord(s.wait_ev, reinterpret_cast<hipStream_t>(static_cast<uintptr_t>(d->wait_stream)));
     if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, s.wait_ev, 0);
     if (e != hipSuccess) {
@@ -2784,14 +2748,14 @@ int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what)
 // than tMin and a rounding margin: a ray from inside always passes it
 int32_t camera_root_check(const Scene& s, const Camera& cam)
 {
-    if (!(s.oct && s.opt.tie_rule == 0)) return 0;
+    if (!(s.octree.oct && s.opt.tie_rule == 0)) return 0;
     const float o[3] = {cam.origin.x, cam.origin.y, cam.origin.z};
     const float uu[3] = {cam.u.x, cam.u.y, cam.u.z}, vv[3] = {cam.v.x, cam.v.y, cam.v.z};
     bool inside = true;
     for (int c = 0; c < 3; ++c) {
         const double r = (double)cam.lens_radius * (std::fabs((double)uu[c]) + std::fabs((double)vv[c]));
-        const double m = 2.0 * kMinT + 1e-4 * ((double)s.oct_hi[c] - (double)s.oct_lo[c]);
-        inside = inside && (double)o[c] - r > (double)s.oct_lo[c] + m && (double)o[c] + r < (double)s.oct_hi[c] - m;
+        const double m = 2.0 * kMinT + 1e-4 * ((double)s.octree.oct_hi[c] - (double)s.octree.oct_lo[c]);
+        inside = inside && (double)o[c] - r > (double)s.octree.oct_lo[c] + m && (double)o[c] + r < (double)s.octree.oct_hi[c] - m;
     }
     return inside ? 0 : 1;
 }
@@ -2830,9 +2794,8 @@ int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uin
     const uint32_t cnt = (uint32_t)(a.smp_end - a.smp_begin);
     const int64_t n = a.slots * (int64_t)cnt;
     if (n <= 0) return 0;
-    CamRay* buf = nullptr;
-    if (hipMalloc(&buf, sizeof(CamRay) * (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
+    DeviceBuffer<CamRay> buf;
+    if (!buf.alloc(sizeof(CamRay) * (size_t)n)) {
         set_error("tmpt_camera_rays: out of device memory");
         return -12;
     }
@@ -2840,7 +2803,6 @@ int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uin
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
     if (e == hipSuccess) e = hipMemcpy(out, buf, sizeof(CamRay) * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) {
         set_error(std::string("tmpt_camera_rays: ") + hipGetErrorString(e));
         return -1;
@@ -2857,7 +2819,7 @@ int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uin
 static int32_t split_pass_samples(Scene& s, const RenderArgs& a)
 {
     const Options& o = s.opt;
-    if (o.shadow_split == 0 || !a.jt || a.slots <= 0 || o.path_waves == 4 || o.cam_pre == 0 || s.soa.na != nullptr ||
+    if (o.shadow_split == 0 || !a.jt || a.slots <= 0 || o.path_waves == 4 || o.cam_pre == 0 || s.bvh.soa.na != nullptr ||
         oct_shadow_check(s))
         return 0;
     PathVariant probe5{};
@@ -2880,8 +2842,7 @@ static int32_t split_pass_samples(Scene& s, const RenderArgs& a)
     if (fits(a.spp)) return a.spp;
     {  // several passes: each is a pass of render_persistent, which needs the colour buffer (its rule)
         const size_t need = sizeof(float4) * (size_t)a.spp * (size_t)a.slots;
-        size_t fr = 0, tot = 0;
-        size_t sbuf_budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.sbuf_bytes;
+        size_t sbuf_budget = free_budget(3, 4, s.sbuf.bytes());
         if (o.sbuf_max > 0.0) sbuf_budget = std::min(sbuf_budget, (size_t)o.sbuf_max);
         if (need > sbuf_budget) return 0;
     }
@@ -2904,13 +2865,7 @@ static int32_t split_pass_samples(Scene& s, const RenderArgs& a)
 static int render_split_passes(Scene& s, const RenderArgs& a, int32_t cs, uint32_t* d_out,
                                unsigned long long* d_counters)
 {
-    if (s.split_carry_slots < (size_t)a.slots) {
-        if (s.split_carry) (void)hipFree(s.split_carry);
-        s.split_carry = nullptr;
-        s.split_carry_slots = 0;
-        TMPT_HIP(hipMalloc(&s.split_carry, sizeof(float4) * (size_t)a.slots));
-        s.split_carry_slots = (size_t)a.slots;
-    }
+    TMPT_ALLOC(s.split_carry.reserve(sizeof(float4) * (size_t)a.slots), "tmpt_render: the shadow split's carried sums");
     Scene::SplitAcc acc;
     int rc = 0;
     int32_t tie_path = 0, passes = 0;
@@ -2999,13 +2954,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
             return -22;
         }
         s.prog_cam = cam_key;
-        if (s.prog_slots < (size_t)a.slots) {
-            if (s.prog) (void)hipFree(s.prog);
-            s.prog = nullptr;
-            s.prog_slots = 0;
-            TMPT_HIP(hipMalloc(&s.prog, sizeof(float4) * (size_t)a.slots));
-            s.prog_slots = (size_t)a.slots;
-        }
+        TMPT_ALLOC(s.prog.reserve(sizeof(float4) * (size_t)a.slots), "tmpt_render: the progressive sums");
         a.prog = s.prog;
         memcpy(s.prog_key, key, sizeof(key));
         s.prog_key[6] = -1;  // valid again only once this pass completes
@@ -3188,7 +3137,7 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
                     "k_path walk: %d key bits, culling %s; per closest-hit query %.3f node visits, %.3f triangle "
                     "tests; stale pops discarded %llu (%.4f of closest-hit node visits and discards), followed by another "
                     "stale entry %.4f\n",
-                    pop_key_bits(s.link_bits, s.opt.pop_key_cap), sv.key_mask ? "on" : "off",
+                    pop_key_bits(s.bvh.link_bits, s.opt.pop_key_cap), sv.key_mask ? "on" : "off",
                     c[3] ? (double)c[1] / c[3] : 0.0, c[3] ? (double)c[2] / c[3] : 0.0, w[0],
                     c[1] + w[0] ? (double)w[0] / (double)(c[1] + w[0]) : 0.0,
                     w[0] ? (double)w[1] / w[0] : 0.0);

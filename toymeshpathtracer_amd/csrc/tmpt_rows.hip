@@ -409,7 +409,7 @@ int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned lo
     // flag a tie and keep the first triangle met (TIES 2): the flagged query's
     // answer comes from the octree either way, so the lowest-index bookkeeping
     // is not needed (option row_flag_leaves 0 keeps it, for A/B)
-    const bool flag = s.oct_view && o.tie_rule == 0 && o.row_flag_leaves;
+    const bool flag = s.octree.oct_view && o.tie_rule == 0 && o.row_flag_leaves;
     const int ties = flag ? 2 : 0;
     // the chain's full re-trace at 5 waves per SIMD (option path_waves, as the
     // sample kernels: the 30-KB LDS layout of OCC 5)
@@ -482,37 +482,11 @@ int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned lo
     const size_t zero_bytes = b_res + b_slots + b_pos + b_rays + b_lo + b_ctl + b_ctr;
     const size_t need = zero_bytes + b_anch + b_ovf;
     const size_t lneed = lcap * sizeof(uint32_t), sneed = lcap * sizeof(float4);
-    {
-        size_t fr = 0, tot = 0;
-        const size_t budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.rss_bytes +
-                              s.rs_list_bytes + s.sbuf_bytes;
-        if (need + lneed + sneed > budget) return 1;
-    }
-    auto grow = [](void*& p, size_t& have, size_t want) -> int {
-        if (have >= want) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        have = 0;
-        if (hipMalloc(&p, want) != hipSuccess) return -1;
-        have = want;
-        return 0;
-    };
+    if (need + lneed + sneed > free_budget(3, 4, s.rss_buf.bytes() + s.rs_list.bytes() + s.sbuf.bytes())) return 1;
     // HBM short after the budget check (another allocation raced it): the
     // iterated engine may still fit, so fall back rather than fail the frame
-    // (grow() has freed the old buffer; the failed hipMalloc's error is cleared)
-    if (grow(s.rss_buf, s.rss_bytes, need) || grow(s.rs_list, s.rs_list_bytes, lneed)) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    {
-        void* sb = s.sbuf;
-        const int g = grow(sb, s.sbuf_bytes, sneed);
-        s.sbuf = static_cast<float4*>(sb);
-        if (g) {
-            (void)hipGetLastError();
-            return 1;
-        }
-    }
+    // (reserve() has freed the old buffer and cleared the failed allocation's error)
+    if (!s.rss_buf.reserve(need) || !s.rs_list.reserve(lneed) || !s.sbuf.reserve(sneed)) return 1;
     if (!s.rss_tab) {  // M^(2c) and M^(256b) for c, b < 128; M^(2^15 a0), M^(2^20 a1) for a0, a1 < 32
         std::vector<uint32_t> tab, t;
         jump_tables(2, 128, t);
@@ -523,17 +497,10 @@ int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned lo
         tab.insert(tab.end(), t.begin(), t.end());
         jump_tables(1ull << 20, 32, t);
         tab.insert(tab.end(), t.begin(), t.end());
-        uint32_t* nt = nullptr;
-        TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-        if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
-            set_error("render_rowstream: jump table upload failed");
-            return -1;
-        }
-        s.rss_tab = nt;
+        if (int rc = upload_tables(s.rss_tab, tab, "render_rowstream")) return rc;
     }
-    if (!s.rss_host) TMPT_HIP(hipHostMalloc((void**)&s.rss_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
-    char* p = static_cast<char*>(s.rss_buf);
+    TMPT_HIP(s.rss_host.ensure(16 * sizeof(uint32_t)));
+    char* p = s.rss_buf.as<char>();
     RsStream S;
     memset(&S, 0, sizeof(S));
     S.res = reinterpret_cast<unsigned long long*>(p);
@@ -554,7 +521,7 @@ int render_rowstream(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned lo
     p += b_anch;
     uint32_t* ovf = reinterpret_cast<uint32_t*>(p);
     uint32_t* heads = ovf + ovf_words;
-    S.list = static_cast<uint32_t*>(s.rs_list);
+    S.list = s.rs_list.as<uint32_t>();
     S.t1 = s.rss_tab;
     S.t2 = s.rss_tab + 128 * 1024;
     S.na = na;
@@ -745,26 +712,13 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
     if (noshadow) {
         const size_t lneed = lcap * 3 * sizeof(uint32_t) + (size_t)rows * scap * sizeof(uint2) + 256;
         const size_t sneed = (size_t)a.slots * (size_t)a.spp * sizeof(float4);
-        size_t fr = 0, tot = 0;
-        const size_t budget = (hipMemGetInfo(&fr, &tot) == hipSuccess ? fr / 4 * 3 : 0) + s.rs_list_bytes + s.sbuf_bytes;
+        const size_t budget = free_budget(3, 4, s.rs_list.bytes() + s.sbuf.bytes());
         if (lcap >= (1ull << 32) || lneed + sneed > budget) {
             if (ch) return 1;  // pixel chains need the re-trace: the caller renders them in pass 2
             noshadow = false;  // does not fit: the colours come from the speculative pass
         } else {
-            if (s.rs_list_bytes < lneed) {
-                if (s.rs_list) (void)hipFree(s.rs_list);
-                s.rs_list = nullptr;
-                s.rs_list_bytes = 0;
-                TMPT_HIP(hipMalloc(&s.rs_list, lneed));
-                s.rs_list_bytes = lneed;
-            }
-            if (s.sbuf_bytes < sneed) {
-                if (s.sbuf) (void)hipFree(s.sbuf);
-                s.sbuf = nullptr;
-                s.sbuf_bytes = 0;
-                TMPT_HIP(hipMalloc(&s.sbuf, sneed));
-                s.sbuf_bytes = sneed;
-            }
+            TMPT_ALLOC(s.rs_list.reserve(lneed), "tmpt_render: the chain list");
+            TMPT_ALLOC(s.sbuf.reserve(sneed), "tmpt_render: the colour buffer");
         }
     }
     uint32_t* lpix = nullptr;
@@ -773,8 +727,8 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
     uint32_t* lcount = nullptr;
     uint2* scratch = nullptr;
     if (noshadow) {
-        lcount = static_cast<uint32_t*>(s.rs_list);
-        scratch = reinterpret_cast<uint2*>(static_cast<char*>(s.rs_list) + 256);
+        lcount = s.rs_list.as<uint32_t>();
+        scratch = reinterpret_cast<uint2*>(s.rs_list.as<char>() + 256);
         lpix = reinterpret_cast<uint32_t*>(scratch + (size_t)rows * scap);
         lstate = lpix + lcap;
         lslot = lstate + lcap;
@@ -782,15 +736,7 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
     if (s.jt2_n < (int32_t)jmax) {  // J_j = M^(2j): the state 2j draws on
         std::vector<uint32_t> tab;
         jump_tables(2, (int32_t)jmax, tab);
-        uint32_t* nt = nullptr;
-        TMPT_HIP(hipMalloc(&nt, tab.size() * sizeof(uint32_t)));
-        if (hipMemcpy(nt, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(nt);
-            set_error("tmpt_render: jump table upload failed");
-            return -1;
-        }
-        if (s.jt2) (void)hipFree(s.jt2);
-        s.jt2 = nt;
+        if (int rc = upload_tables(s.jt2, tab, "tmpt_render")) return rc;
         s.jt2_n = (int32_t)jmax;
     }
     const size_t ovf_words = (size_t)std::max(pgrid, pgrid3) * kBlk * (kStackTotal - kPathSL);
@@ -805,21 +751,14 @@ int render_rowspec(Scene& s, const RenderArgs& a, uint32_t* d_out, unsigned long
     };
     size_t need = al(24 * sizeof(unsigned long long));
     for (int g = 0; g < G; ++g) need += group_bytes(g);
-    if (s.rs_bytes < need) {
-        if (s.rs_buf) (void)hipFree(s.rs_buf);
-        s.rs_buf = nullptr;
-        s.rs_bytes = 0;
-        TMPT_HIP(hipMalloc(&s.rs_buf, need));
-        s.rs_bytes = need;
+    TMPT_ALLOC(s.rs_buf.reserve(need), "tmpt_render: the row engine's buffers");
+    TMPT_HIP(s.rs_host.ensure(kRowSpecMaxGroups * sizeof(uint32_t)));
+    for (int g = 0; g < G; ++g) {
+        TMPT_HIP(s.rs_stream[g].ensure(hipStreamNonBlocking));
+        TMPT_HIP(s.rs_event[g].ensure(hipEventDisableTiming));
     }
-    if (!s.rs_host) TMPT_HIP(hipHostMalloc((void**)&s.rs_host, kRowSpecMaxGroups * sizeof(uint32_t)));
-    for (int g = 0; g < G; ++g)
-        if (!s.rs_stream[g]) {
-            TMPT_HIP(hipStreamCreateWithFlags(&s.rs_stream[g], hipStreamNonBlocking));
-            TMPT_HIP(hipEventCreateWithFlags(&s.rs_event[g], hipEventDisableTiming));
-        }
-    if (!s.rs_event[kRowSpecMaxGroups]) TMPT_HIP(hipEventCreateWithFlags(&s.rs_event[kRowSpecMaxGroups], hipEventDisableTiming));
-    char* p = static_cast<char*>(s.rs_buf);
+    TMPT_HIP(s.rs_event[kRowSpecMaxGroups].ensure(hipEventDisableTiming));
+    char* p = s.rs_buf.as<char>();
     unsigned long long* spec_ctr = reinterpret_cast<unsigned long long*>(p);  // every traced unit's rays
     p += al(24 * sizeof(unsigned long long));
     struct Group {

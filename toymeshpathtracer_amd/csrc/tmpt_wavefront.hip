@@ -396,7 +396,7 @@ int render_wavefront(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count)
     const int64_t max_log = (int64_t)a.spp * (kMaxDepth + 2) + 64 + 16;
     size_t o_log = log_iters ? take(2 * (size_t)max_log) : 0;
     if (ensure_ws(s, words * 4)) return -1;
-    uint32_t* w = (uint32_t*)s.ws;
+    uint32_t* w = s.ws.as<uint32_t>();
     WfState st;
     st.rng = w + o_rng;
     st.smp = w + o_smp;
@@ -434,16 +434,15 @@ int render_wavefront(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count)
     k_wf_generate<kBlk><<<(int)((std::max<int64_t>(P, kSeg) + kBlk - 1) / kBlk), kBlk, 0, str>>>(a, st);
 
     // per-launch timing of the traversal kernels
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     auto new_ev = [&]() {
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        ev.push_back(e);
-        return e;
+        ev.emplace_back();
+        (void)ev.back().ensure();
+        return ev.back().get();
     };
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ext_ev, sh_ev;
-    uint32_t* h_cnt = nullptr;
-    TMPT_HIP(hipHostMalloc((void**)&h_cnt, 16, hipHostMallocDefault));
+    PinnedBuffer<uint32_t> h_cnt;
+    TMPT_HIP(h_cnt.ensure(16));
     const int kCheck = 8;
     int parity = 0;
     int64_t it = 0;
@@ -488,8 +487,6 @@ int render_wavefront(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count)
     double ems = 0, sms = 0;
     for (auto& pr : ext_ev) { float ms = 0; (void)hipEventElapsedTime(&ms, pr.first, pr.second); ems += ms; }
     for (auto& pr : sh_ev) { float ms = 0; (void)hipEventElapsedTime(&ms, pr.first, pr.second); sms += ms; }
-    for (auto e : ev) (void)hipEventDestroy(e);
-    (void)hipHostFree(h_cnt);
     if (rc) {
         if (rc == -1) set_error("wavefront: HIP error");
         return rc;
