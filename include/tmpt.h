@@ -56,7 +56,11 @@ extern "C" {
                               still 9, additive: tmpt_scene_update (a device BVH refit, or a rebuild, of a
                               scene in place) and the read-only options update_kind, update_ms and
                               bvh_cost -- no struct above changed;
-                              still 9, additive: the read-only option live_device_objects */
+                              still 9, additive: the read-only option live_device_objects;
+                              still 9, additive: temporal accumulation -- the render option sample_base,
+                              tmpt_render_motion with tmpt_motion_pixel (the motion pass) and
+                              tmpt_temporal with tmpt_temporal_desc (the reprojected history) -- no
+                              struct above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -293,7 +297,18 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *   ploc_radius  PLOC search radius, 1..256 (default 32)
  *   sah_c_leaf, sah_c_tri  SAH collapse costs (defaults 0.7, 0.5; inner node 1)
  * Render options (tmpt_scene_set_option; apply to later renders on the scene):
- *   sample_block     sample seeding: samples per work unit, power of two (0 = auto)
+ *   sample_base      sample seeding: an integer B, 0 .. 64512 (default 0).  Sample s of every
+ *                    sample-seeded call on the scene (tmpt_render, tmpt_render_radiance,
+ *                    tmpt_render_aov, tmpt_render_adaptive, tmpt_camera_rays) starts
+ *                    2^16 (s + B) xorshift steps into the pixel's stream instead of 2^16 s:
+ *                    a call at spp = n traces samples [B, B + n) of the stream, summed from
+ *                    zero, so frame f of a sequence at B = f * spp draws numbers no earlier
+ *                    frame drew (B + 1024 <= 65536 keeps the windows inside the period).
+ *                    Host only: the jump tables hold J_(s + B).  A new value drops the tables
+ *                    and invalidates the progressive state as a camera change does (a render
+ *                    with spp_begin > 0 straight after fails with -22).  Row and pixel
+ *                    seeding and tmpt_render_motion (which draws nothing) do not read it.
+ *   sample_block    sample seeding: samples per work unit, power of two (0 = auto)
  *   sample_tail      sample seeding: the frame's last sample_tail x (resident lanes) blocks run
  *                    as single-sample units, so the frame ends on one sample, not one block
  *                    (-1 = auto: a quarter of a lane's samples, at most 64; 0 = off)
@@ -421,7 +436,10 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *   denoise_lds      tmpt_denoise: how a level reads its taps -- 1: the levels of stride 1 and 2 stage
  *                    their block's tile and halo (colour and guides) in LDS, the wider strides read
  *                    global memory directly; 0: every level reads directly; -1 (default): the measured
- *                    choice per stride; the output is the same for every value */
+ *                    choice per stride; the output is the same for every value
+ *   motion_tile      tmpt_render_motion: the 64 pixels a wave takes at a time -- 1: an 8 x 8 block,
+ *                    0: 64 consecutive pixels of a row, -1 (default): the measured choice (the row); the
+ *                    records are the same for every value */
 int tmpt_scene_create_ex(const float* tris, int32_t n, int32_t device, const char* options, tmpt_scene** out);
 int tmpt_scene_set_option(tmpt_scene* scene, const char* key, double value);
 int tmpt_scene_get_option(const tmpt_scene* scene, const char* key, double* value);
@@ -653,6 +671,130 @@ int tmpt_render_adaptive(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_r
  * (guide preparation and the levels); the other fields keep the last render's. */
 int tmpt_denoise(tmpt_scene* scene, const tmpt_denoise_desc* desc, const float* rgba32f_in,
                  const tmpt_aov_pixel* aov, float* rgba32f_out, uint8_t* rgba8_out);
+
+/* ---- Temporal accumulation: the motion pass and the reprojected history.
+ * Everything below is float32 arithmetic that rounds once per operation and is
+ * not contracted; '/' and sqrtf are correctly rounded; operations happen in the
+ * order written; dot(a, b) = (ax*bx + ay*by) + az*bz.  This statement is the
+ * contract (tests/temporal_restate.py restates it in numpy).
+ *
+ * The motion record of one pixel: where the surface point its centre ray hits
+ * was one frame ago.  A refit keeps triangle i in slot i (tmpt_scene_update), so
+ * the hit's triangle id and barycentrics name the same material point in the
+ * previous pose. */
+typedef struct {          /* 32 B, two 16-byte stores */
+    float    px, py;      /* where this pixel's surface point was in the previous frame, in continuous
+                             pixel coordinates of the whole frame (pixel (x, y)'s centre is (x+0.5, y+0.5)) */
+    float    depth;       /* t of this frame's centre ray */
+    float    depth_prev;  /* distance of the previous point from the previous camera's origin */
+    float    u, v;        /* barycentrics of the hit, the bits the triangle test returns */
+    int32_t  tri_id;      /* closest triangle, or -1 */
+    uint32_t flags;       /* 1 = hit, 2 = px, py, depth_prev are valid */
+} tmpt_motion_pixel;
+/* The motion pass of desc's shard (tmpt_tile_rows(desc) * width records, the
+ * compact tile layout of tmpt_render; y below is the global row).  desc is read as
+ * tmpt_render_aov reads it -- width, height, band_rows, shard, num_shards, flags
+ * (TMPT_FLAG_OUT_DEVICE: out, and prev_tris if given, are device pointers, out
+ * 16-byte aligned; TMPT_FLAG_WAIT_STREAM), wait_stream; spp, seed_mode and engine
+ * are not read.
+ *
+ * Centre ray: one ray per pixel (x, y), no random draw, from the lens centre:
+ *   s = ((float)x + 0.5f) * invW,  t = ((float)y + 0.5f) * invH
+ *       (invW = 1.0f / (float)width, invH = 1.0f / (float)height)
+ *   o = cam.origin
+ *   d = normalize(((lower_left + s*horizontal) + t*vertical) - origin)
+ * This is the camera's ray expression with the lens offset left out altogether
+ * (not added as zero: o is origin itself and d has one subtraction).
+ * The hit: the closest hit over [0.001, 1e7] as tmpt_scene_hit answers it, with
+ * the scene's tie rule and, where the octree is built, its root test.  A miss
+ * writes tri_id = -1, flags = 0 and zeros elsewhere; a hit writes depth = t, u,
+ * v, tri_id and flags |= 1.
+ * Previous position: (v0', v1', v2') = triangle tri_id of prev_tris (prev_n x 9
+ * floats; prev_n must be the scene's n); prev_tris NULL = the geometry did not
+ * move: prev_n is ignored and the scene's own vertices are used.
+ *   P' = (((1.0f - u) - v) * v0' + u * v1') + v * v2'       (componentwise)
+ * A host prev_tris is uploaded into a buffer the scene keeps (grown, never shrunk).
+ * Projection through prev_cam (fields o, ll, hz, vt, w), a pinhole: the lens is
+ * ignored, so a defocused camera reprojects its plane of focus exactly and
+ * everything else to the centre of its blur:
+ *   dd  = P' - o            q = ll - o            (componentwise)
+ *   den = dot(dd, w)        num = dot(q, w)
+ *   valid iff den < 0.0f    (in front of the camera; a NaN is not valid)
+ *   k   = num / den         r = k*dd - q          (r.c = k*dd.c - q.c)
+ *   px  = (dot(r, hz) / dot(hz, hz)) * (float)width
+ *   py  = (dot(r, vt) / dot(vt, vt)) * (float)height
+ *   depth_prev = sqrtf(dot(dd, dd))
+ * Valid: flags |= 2.  Not valid: px = py = depth_prev = 0.
+ *
+ * -22 with a message, before any device call and in this order: a null cam,
+ * prev_cam, desc or out; a size outside tmpt_render's limits; an invalid shard;
+ * TMPT_FLAG_COUNT_VISITS; a misaligned device out; a null scene; prev_n != n where
+ * prev_tris is given (the scene is looked at last, so the checks before it need no
+ * device).  *ray_count (may be NULL) = the pixels of the tile.  tmpt_get_stats
+ * afterwards as after the AOV pass: render_ms, extend_ms, extend_rays,
+ * extend_launches = 1, tie_queries, root_misses, crack_queries.  The progressive
+ * state is left alone, and option sample_base is not read. */
+int tmpt_render_motion(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_camera* prev_cam,
+                       const float* prev_tris, int32_t prev_n, const tmpt_render_desc* desc,
+                       tmpt_motion_pixel* out, uint64_t* ray_count);
+
+typedef struct {
+    int32_t width, height;
+    int32_t flags;          /* TMPT_FLAG_OUT_DEVICE (every pointer a device pointer), TMPT_FLAG_WAIT_STREAM */
+    float   n_max;          /* cap on the history length, >= 1; 0 = default (3) */
+    float   sigma_depth;    /* relative depth tolerance, > 0; 0 = default (0.05) */
+    int32_t reserved0;
+    uint64_t wait_stream;
+    int32_t reserved[4];
+} tmpt_temporal_desc;
+/* One step of temporal accumulation over whole frames (width x height, contiguous
+ * rows, row 0 at the bottom, as tmpt_denoise): the current radiance frame blended
+ * with the previous accumulation, fetched where motion says each pixel's surface
+ * was and accepted where prev_motion (the previous frame's motion records) shows
+ * the same depth there.  A frame's .w is its history length: tmpt_render_radiance
+ * writes 1.0f, so a plain radiance frame is a history of length one, and
+ * tmpt_denoise passes .w through.  rgba32f_out (may be NULL) may be rgba32f_cur;
+ * it must not overlap rgba32f_history, whose neighbours are read.  rgba8_out (may
+ * be NULL) takes the packed pixels; at least one output is given.
+ *
+ * Per pixel p = (x, y), with m = motion[p]:
+ *   reset:  out_p = {cur_p.r, cur_p.g, cur_p.b, 1.0f}
+ *   if !(m.flags & 2), or m.px / m.py is not finite or lies outside
+ *      [-1, width+1) / [-1, height+1): reset
+ *   fx = m.px - 0.5f   fy = m.py - 0.5f   x0 = floorf(fx)   y0 = floorf(fy)
+ *   ax = fx - x0       ay = fy - y0
+ *   csum = {0,0,0}  nsum = 0  wsum = 0
+ *   for j = 0, 1 (outer), i = 0, 1 (inner): q = ((int)x0 + i, (int)y0 + j)
+ *       wgt = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay)
+ *       skipped: q outside the frame;  !(prev_motion[q].flags & 1);
+ *                fabsf(prev_motion[q].depth - m.depth_prev) > sigma_depth * m.depth_prev
+ *                (a NaN compares false: not skipped)
+ *       csum.k = csum.k + hist_q.k * wgt  (k = r, g, b)
+ *       nsum = nsum + hist_q.w * wgt      wsum = wsum + wgt
+ *   if !(wsum > 0.0f): reset
+ *   h.k = csum.k / wsum    n = fminf(nsum / wsum + 1.0f, n_max)    a = 1.0f / n
+ *   out_p.k = h.k + (cur_p.k - h.k) * a      out_p.w = n
+ * rgba8_out packs out as every render packs its pixels (sqrt, saturate, * 255).
+ * Nothing is screened (a NaN in an input spreads to the pixels that read it), as in
+ * tmpt_denoise.  Sky pixels (misses) restart every frame.
+ * Defaults n_max = 3, sigma_depth = 0.05 (tools/temporal_sweep.py,
+ * profiles/temporal_sweep.log, DESIGN.md "Temporal accumulation": over twisting
+ * and static sequences at 4 spp a frame, 3 is the cap whose worst sequence is best
+ * -- the shading of a moving surface changes under the fixed light, and a longer
+ * mean lags behind it; a static view gains up to n_max = 16 and beyond, so raise it
+ * where little moves.  sigma_depth 0.02 .. 0.2 measured within 0.3 % of one another).
+ * The scene lends its device, stream and error channel; no geometry is read and
+ * the progressive state is left alone.  -22, in this order, for: a null desc; a
+ * size outside tmpt_render's limits; a missing pointer (cur, motion, prev_motion,
+ * history, or both outputs); n_max < 1 (after the default) or not finite; a
+ * negative or non-finite sigma_depth; other flags; a misaligned device pointer (16
+ * bytes; rgba8_out: 4); rgba32f_out overlapping rgba32f_history; a null scene.  tmpt_get_stats
+ * afterwards: render_ms is the blend's time on the device; the other fields keep
+ * the last render's. */
+int tmpt_temporal(tmpt_scene* scene, const tmpt_temporal_desc* desc, const float* rgba32f_cur,
+                  const tmpt_motion_pixel* motion, const tmpt_motion_pixel* prev_motion,
+                  const float* rgba32f_history, float* rgba32f_out, uint8_t* rgba8_out);
+
 /* main.cpp:312-331 over several devices in ONE process (SURVEY.md §8e's
  * single-process form): a scene per entry of devices[] (created here, freed on
  * return), the frame's rows dealt round-robin to them (1-row bands), one host

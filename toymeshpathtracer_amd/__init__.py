@@ -18,6 +18,9 @@ reference                   here
 (none: denoiser)            :meth:`Scene.denoise` (edge-avoiding a-trous filter guided by the AOV records)
 (none: adaptive sampling)   :meth:`Scene.trace_adaptive` (per-pixel sample counts by a variance test)
 (none: scene update)        :meth:`Scene.update` (new triangles in place: a device BVH refit, or a rebuild)
+(none: temporal)            :meth:`Scene.trace_motion` (:data:`MOTION_DTYPE` records: where each pixel's surface
+                            was one frame ago) and :meth:`Scene.temporal` (the reprojected, accumulated history);
+                            render option ``sample_base`` gives every frame its own samples
 ``stbi_write_png`` :342     :func:`write_png`
 ==========================  ==============================================
 
@@ -37,7 +40,7 @@ __all__ = [
     "Camera", "Scene", "Hit", "RenderStats", "load_scene", "write_png", "device_count",
     "SEED_ROW", "SEED_PIXEL", "SEED_SAMPLE", "ENGINE_WAVEFRONT", "ENGINE_MEGAKERNEL", "ENGINE_PERSISTENT", "lib_path", "TmptError",
     "tile_rows", "tile_row_to_y", "render_multi", "octree_bounds", "octree_digest", "octree_flags",
-    "AOV_DTYPE",
+    "AOV_DTYPE", "MOTION_DTYPE",
 ]
 
 SEED_ROW, SEED_PIXEL, SEED_SAMPLE = 0, 1, 2
@@ -48,6 +51,9 @@ FLAG_OUT_DEVICE, FLAG_COUNT_VISITS, FLAG_WAIT_STREAM, FLAG_REQUIRE_RCCL = 1, 2, 
 #: tmpt_aov_pixel (include/tmpt.h), one record of :meth:`Scene.trace_aov`, 32 bytes
 AOV_DTYPE = np.dtype([("normal", np.float32, (3,)), ("depth", np.float32), ("direct", np.float32),
                       ("tri_id", np.int32), ("hits", np.uint32), ("lit", np.uint32)])
+#: tmpt_motion_pixel (include/tmpt.h), one record of :meth:`Scene.trace_motion`, 32 bytes
+MOTION_DTYPE = np.dtype([("px", np.float32), ("py", np.float32), ("depth", np.float32), ("depth_prev", np.float32),
+                         ("u", np.float32), ("v", np.float32), ("tri_id", np.int32), ("flags", np.uint32)])
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # TMPT_LIB_PATH: another in-tree build of the library (compiler-flag A/B in tools/)
@@ -105,6 +111,12 @@ class _DenoiseDesc(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("spp", ctypes.c_int32),
                 ("levels", ctypes.c_int32), ("normal_exp", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("sigma_depth", ctypes.c_float), ("sigma_direct", ctypes.c_float),
+                ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
+
+
+class _TemporalDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("n_max", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("reserved0", ctypes.c_int32),
                 ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
@@ -212,7 +224,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
-           "tmpt_scene_update")
+           "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal")
 
 
 def _check(rc: int, what: str) -> None:
@@ -789,6 +801,107 @@ class Scene:
         _check(_denoise(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
                         aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
                         img.ctypes.data_as(ctypes.c_void_p)), "denoise")
+        return res, img
+
+    def trace_motion(self, camera: Camera, prev_camera: Camera, width: int, height: int, prev_triangles=None,
+                     band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None, wait_stream="current"):
+        """The motion pass of one shard (tmpt_render_motion; include/tmpt.h states
+        its arithmetic): returns (records[tile_rows, width] of :data:`MOTION_DTYPE`,
+        rays) -- per pixel the closest hit of its centre ray (depth, barycentrics,
+        triangle id) and where that surface point lay in the previous frame:
+        ``prev_triangles`` [n, 3, 3] is the previous pose (``None``: the geometry
+        did not move), ``prev_camera`` the previous camera; ``px``, ``py`` are
+        continuous pixel coordinates of the whole frame.  rays = the tile's
+        pixels.  Device form: ``out`` a device pointer with tile_rows*width*32
+        bytes (16-byte aligned; then records is None), ``prev_triangles`` a
+        device pointer to the scene's n x 9 floats or None, ``wait_stream`` as in
+        :meth:`trace_image`."""
+        # bound on first use, as tmpt_fastdiv is
+        fn = _sig("tmpt_render_motion", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
+                                                       ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int32,
+                                                       ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, 1, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        rows = int(_tile_rows(ctypes.byref(d)))
+        rays = ctypes.c_uint64()
+        cam, pcam = camera._to_c(), prev_camera._to_c()
+        if out is not None:
+            prev = None if prev_triangles is None else ctypes.c_void_p(int(prev_triangles))
+            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), prev, self.n, ctypes.byref(d),
+                      ctypes.c_void_p(int(out)), ctypes.byref(rays)), "trace_motion")
+            return None, int(rays.value)
+        prev, pn = None, 0
+        if prev_triangles is not None:
+            pt = np.ascontiguousarray(np.asarray(prev_triangles, np.float32).reshape(-1, 9))
+            prev, pn = pt.ctypes.data_as(ctypes.c_void_p), pt.shape[0]
+        rec = np.zeros((rows, width), MOTION_DTYPE)
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), prev, pn, ctypes.byref(d),
+                  rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)), "trace_motion")
+        return rec, int(rays.value)
+
+    def temporal(self, radiance, motion, prev_motion, history, n_max: float = 0.0, sigma_depth: float = 0.0,
+                 out=None, width: Optional[int] = None, height: Optional[int] = None, wait_stream="current"):
+        """One step of temporal accumulation (tmpt_temporal; include/tmpt.h states
+        its arithmetic) over a whole frame: ``radiance`` float32[h, w, 4] (this
+        frame, :meth:`trace_radiance`), ``motion`` and ``prev_motion`` the
+        :data:`MOTION_DTYPE` records [h, w] of this frame and the previous one
+        (:meth:`trace_motion`), ``history`` float32[h, w, 4] the previous
+        accumulation, whose alpha is its history length (a plain radiance frame
+        is a history of length one).  Returns (float32[h, w, 4], rgba8[h, w, 4]):
+        keep the float frame as the next history.  0.0 selects the defaults
+        (n_max 3, sigma_depth 0.05; raise n_max where little moves).  ``out``: a float32 array [h, w, 4] that
+        takes the frame (it may be ``radiance`` itself, never ``history``).
+        Device form, as :meth:`denoise`: the four inputs are device pointers
+        (ints, 16-byte aligned), ``width`` and ``height`` give the size and
+        ``out`` = (float frame pointer or None, rgba8 pointer or None); returns
+        (None, None)."""
+        fn = _sig("tmpt_temporal", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_TemporalDesc), ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p])
+        dev = isinstance(radiance, int)
+        d = _TemporalDesc()
+        if dev:
+            if width is None or height is None or out is None:
+                raise ValueError("temporal: device pointers need width, height and out")
+            h, w = int(height), int(width)
+        else:
+            radiance = np.ascontiguousarray(radiance, np.float32)
+            history = np.ascontiguousarray(history, np.float32)
+            motion = np.ascontiguousarray(motion, MOTION_DTYPE)
+            prev_motion = np.ascontiguousarray(prev_motion, MOTION_DTYPE)
+            h, w = radiance.shape[:2]
+            if (radiance.shape != (h, w, 4) or history.shape != (h, w, 4) or motion.shape != (h, w)
+                    or prev_motion.shape != (h, w)):
+                raise ValueError("temporal: radiance and history [h, w, 4], motion and prev_motion [h, w] of one "
+                                 "whole frame")
+        d.width, d.height, d.n_max, d.sigma_depth = w, h, n_max, sigma_depth
+        if dev:
+            d.flags = FLAG_OUT_DEVICE
+            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+            if ws is not None:
+                d.flags |= FLAG_WAIT_STREAM
+                d.wait_stream = int(ws)
+            f32, u8 = out
+            _check(fn(self._h, ctypes.byref(d), ctypes.c_void_p(radiance), ctypes.c_void_p(int(motion)),
+                      ctypes.c_void_p(int(prev_motion)), ctypes.c_void_p(int(history)),
+                      None if f32 is None else ctypes.c_void_p(int(f32)),
+                      None if u8 is None else ctypes.c_void_p(int(u8))), "temporal")
+            return None, None
+        res = np.zeros((h, w, 4), np.float32) if out is None else out
+        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+                and res.flags.c_contiguous):
+            raise ValueError("temporal: out must be a contiguous float32 array [h, w, 4] (it may be radiance itself)")
+        img = np.zeros((h, w, 4), np.uint8)
+        _check(fn(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
+                  motion.ctypes.data_as(ctypes.c_void_p), prev_motion.ctypes.data_as(ctypes.c_void_p),
+                  history.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
+                  img.ctypes.data_as(ctypes.c_void_p)), "temporal")
         return res, img
 
     def camera_rays(self, camera: Camera, width: int, height: int, spp: int, spp_begin: int = 0,

@@ -114,6 +114,7 @@ const OptionDef kOptions[] = {
     {"ploc_radius", true, 1, 256, &Options::ploc_radius, nullptr, nullptr},
     {"sah_c_leaf", true, 0, 1e6, nullptr, &Options::sah_c_leaf, nullptr},
     {"sah_c_tri", true, 0, 1e6, nullptr, &Options::sah_c_tri, nullptr},
+    {"sample_base", false, 0, 64512, &Options::sample_base, nullptr, nullptr},
     {"sample_block", false, 0, 1024, &Options::sample_block, nullptr, nullptr},
     {"sample_tail", false, -1, 64, &Options::sample_tail, nullptr, nullptr},
     {"sbuf_max", false, 0, 1e18, nullptr, nullptr, &Options::sbuf_max},
@@ -155,6 +156,7 @@ const OptionDef kOptions[] = {
     {"tie_rule", false, 0, 1, &Options::tie_rule, nullptr, nullptr},
     {"aov_group", false, 0, 16, &Options::aov_group, nullptr, nullptr},
     {"denoise_lds", false, -1, 1, &Options::denoise_lds, nullptr, nullptr},
+    {"motion_tile", false, -1, 1, &Options::motion_tile, nullptr, nullptr},
 };
 
 const OptionDef* find_option(const char* key)
@@ -613,7 +615,17 @@ int tmpt_scene_set_option(tmpt_scene* h, const char* key, double value)
 {
     TMPT_GUARD_BEGIN
     if (!h) return bad("tmpt_scene_set_option: null scene");
-    return options_set(h->s.opt, key, value, false);
+    Scene& s = h->s;
+    const int base = s.opt.sample_base;
+    const int rc = options_set(s.opt, key, value, false);
+    if (s.opt.sample_base != base) {
+        // another window of every pixel's stream: the jump tables are rebuilt by the
+        // next sample-seeded call, and carried sums belong to the old window, as
+        // they would to another camera (spp_begin > 0 fails next)
+        s.jt_spp = 0;
+        s.prog_key[6] = -1;
+    }
+    return rc;
     TMPT_GUARD_END
 }
 
@@ -1001,6 +1013,120 @@ int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f
         if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
             (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_denoise: readback failed"), -1);
+    }
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_render_motion(tmpt_scene* h, const tmpt_camera* cam, const tmpt_camera* prev_cam, const float* prev_tris,
+                       int32_t prev_n, const tmpt_render_desc* d, tmpt_motion_pixel* out, uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    // everything that needs no scene first, so that it is refused without a device
+    if (!cam || !prev_cam || !d || !out) return bad("tmpt_render_motion: null argument");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_motion: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_motion: invalid height");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
+        return bad("tmpt_render_motion: invalid shard");
+    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_motion: TMPT_FLAG_COUNT_VISITS is not supported");
+    const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev_out && (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
+        return bad("tmpt_render_motion: a device output must be 16-byte aligned");
+    if (!h) return bad("tmpt_render_motion: null scene");
+    Scene& s = h->s;
+    if (prev_tris && prev_n != s.bvh.n)
+        return bad("tmpt_render_motion: prev_n differs from the scene's triangle count (the previous pose has the "
+                   "scene's triangles, slot for slot)");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    TMPT_HIP(hipSetDevice(s.device));
+    const float* d_prev = prev_tris;
+    if (prev_tris && !dev_out) {  // a host pose: into the scene's kept buffer
+        const size_t pb = sizeof(float) * 9 * (size_t)prev_n;
+        TMPT_HIP(hipStreamSynchronize(s.stream));
+        if (pb && !s.motion_prev.reserve(pb)) return bad("tmpt_render_motion: out of device memory");
+        if (pb && hipMemcpy(s.motion_prev, prev_tris, pb, hipMemcpyHostToDevice) != hipSuccess)
+            return (set_error("tmpt_render_motion: upload failed"), -1);
+        d_prev = s.motion_prev;
+    }
+    const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * sizeof(tmpt_motion_pixel);
+    DeviceBuffer<tmpt_motion_pixel> own;
+    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render_motion: out of device memory");
+    tmpt_motion_pixel* d_out = dev_out ? out : own.get();
+    int rc = render_motion(s, cam, prev_cam, d_prev, d, d_out, ray_count);
+    if (!rc) rc = check_report(s, "tmpt_render_motion");
+    if (!rc && !dev_out && bytes) {
+        if (hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = (set_error("tmpt_render_motion: readback failed"), -1);
+    }
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_temporal(tmpt_scene* h, const tmpt_temporal_desc* d, const float* rgba32f_cur, const tmpt_motion_pixel* motion,
+                  const tmpt_motion_pixel* prev_motion, const float* rgba32f_history, float* rgba32f_out,
+                  uint8_t* rgba8_out)
+{
+    TMPT_GUARD_BEGIN
+    // the descriptor first, before anything that needs a scene or a device
+    if (!d) return bad("tmpt_temporal: null descriptor");
+    if (d->width < 1 || d->width > 10000) return bad("tmpt_temporal: invalid width");
+    if (d->height < 1 || d->height > 10000) return bad("tmpt_temporal: invalid height");
+    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return bad("tmpt_temporal: null argument");
+    if (!rgba32f_out && !rgba8_out) return bad("tmpt_temporal: no output (rgba32f_out and rgba8_out are both null)");
+    tmpt_temporal_desc r = *d;  // the defaults, in one place ("Temporal accumulation")
+    if (r.n_max == 0.0f) r.n_max = 3.0f;
+    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
+    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f))
+        return bad("tmpt_temporal: n_max must be finite and at least 1 (0 = default)");
+    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
+        return bad("tmpt_temporal: sigma_depth must be finite and not negative (0 = default)");
+    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return bad("tmpt_temporal: unknown flag");
+    const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    if (dev && (((reinterpret_cast<uintptr_t>(rgba32f_cur) | reinterpret_cast<uintptr_t>(motion) |
+                  reinterpret_cast<uintptr_t>(prev_motion) | reinterpret_cast<uintptr_t>(rgba32f_history) |
+                  reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
+                (reinterpret_cast<uintptr_t>(rgba8_out) & 3u) != 0))
+        return bad("tmpt_temporal: device pointers must be 16-byte aligned (rgba8_out: 4)");
+    const size_t n = (size_t)r.width * (size_t)r.height;
+    if (rgba32f_out) {
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(rgba32f_out), h0 = reinterpret_cast<uintptr_t>(rgba32f_history);
+        if (o0 < h0 + n * sizeof(float4) && h0 < o0 + n * sizeof(float4))
+            return bad("tmpt_temporal: rgba32f_out overlaps rgba32f_history (its neighbours are read)");
+    }
+    if (!h) return bad("tmpt_temporal: null scene");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const float4* d_cur = reinterpret_cast<const float4*>(rgba32f_cur);
+    const float4* d_hist = reinterpret_cast<const float4*>(rgba32f_history);
+    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
+    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
+    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
+    DeviceBuffer<float4> own_cur, own_hist;
+    DeviceBuffer<tmpt_motion_pixel> own_m, own_pm;
+    DeviceBuffer<uint32_t> own_8;
+    if (!dev) {  // host pointers: staged on the device; the float result is blended in place there
+        if (!own_cur.alloc(n * sizeof(float4)) || !own_hist.alloc(n * sizeof(float4)) ||
+            !own_m.alloc(n * sizeof(tmpt_motion_pixel)) || !own_pm.alloc(n * sizeof(tmpt_motion_pixel)) ||
+            (rgba8_out && !own_8.alloc(n * 4)))
+            return bad("tmpt_temporal: out of device memory");
+        if (hipMemcpy(own_cur, rgba32f_cur, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(own_hist, rgba32f_history, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(own_m, motion, n * sizeof(tmpt_motion_pixel), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(own_pm, prev_motion, n * sizeof(tmpt_motion_pixel), hipMemcpyHostToDevice) != hipSuccess)
+            return (set_error("tmpt_temporal: upload failed"), -1);
+        d_cur = own_cur;
+        d_hist = own_hist;
+        d_m = own_m;
+        d_pm = own_pm;
+        d_o32 = rgba32f_out ? own_cur.get() : nullptr;
+        d_o8 = own_8;
+    }
+    int rc = temporal(s, &r, d_cur, d_m, d_pm, d_hist, d_o32, d_o8);
+    if (!rc && !dev) {
+        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
+            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = (set_error("tmpt_temporal: readback failed"), -1);
     }
     return rc;
     TMPT_GUARD_END

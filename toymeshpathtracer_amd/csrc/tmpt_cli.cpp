@@ -1,7 +1,8 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
-//        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png] [--twist DEG,FRAMES [--rebuild]]
+//        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
+//        [--twist DEG,FRAMES [--rebuild] [--temporal]]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -25,6 +26,12 @@
 // (a refit; --rebuild: the full build) and the octree built again over the twisted mesh's bounds, the
 // camera staying frame 0's.  The frames go to OUT_000.png, OUT_001.png, ... (OUT: --out less its
 // .png); per frame the update's device time and the tree's bvh_cost are printed.
+// --temporal (with --twist, --seed sample, the persistent engine, a refit): temporal accumulation over the
+// sequence.  Frame f sets the option sample_base to f * spp, so no frame repeats another's random
+// numbers, renders its radiance (tmpt_render_radiance; its packed pixels are the plain frame), runs
+// the motion pass (tmpt_render_motion) against frame f-1's triangles and the same camera, and blends
+// (tmpt_temporal, its defaults) with the accumulation kept from frame f-1; frame 0's accumulation is
+// frame 0 itself.  The accumulated frames go to OUT_temporal_000.png, ... beside the plain ones.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -190,13 +197,22 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
 
 // --twist: see the head of this file.  tris: the n triangles of tmpt_load_obj (the last two are the floor).
 static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, const tmpt_render_desc* desc, int device,
-                        double degrees, int frames, bool rebuild, const char* out)
+                        double degrees, int frames, bool rebuild, bool temporal, const char* out)
 {
     tmpt_scene* scene = nullptr;
     if (tmpt_scene_create(tris, n, device, &scene)) return 1;
     const int w = desc->width, h = desc->height;
     std::vector<uint8_t> image((size_t)w * h * 4, 0);
     std::vector<float> cur((size_t)n * 9);
+    // --temporal: the previous pose, this frame's radiance, the accumulation, both frames' motion records
+    std::vector<float> prev, rad, acc;
+    std::vector<tmpt_motion_pixel> mot, pmot;
+    std::vector<uint8_t> timage;
+    if (temporal) {
+        rad.resize((size_t)w * h * 4);
+        mot.resize((size_t)w * h);
+        timage.resize((size_t)w * h * 4);
+    }
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t i = 0; i < (size_t)n * 3; ++i)
         for (int c = 0; c < 3; ++c) {
@@ -226,14 +242,38 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
         double ms = 0.0, cost = 0.0;
         uint64_t rays = 0;
         tmpt_stats st;
-        rc = tmpt_scene_update(scene, cur.data(), n, rebuild ? TMPT_UPDATE_REBUILD : TMPT_UPDATE_REFIT);
+        if (temporal) rc = tmpt_scene_set_option(scene, "sample_base", (double)f * desc->spp);
+        if (!rc) rc = tmpt_scene_update(scene, cur.data(), n, rebuild ? TMPT_UPDATE_REBUILD : TMPT_UPDATE_REFIT);
         if (!rc) rc = tmpt_octree_bounds(bmin, bmax, box);
         if (!rc) rc = tmpt_scene_build_octree(scene, box, box + 3);
         if (!rc) rc = tmpt_scene_get_option(scene, "update_ms", &ms);
         if (!rc) rc = tmpt_scene_get_option(scene, "bvh_cost", &cost);
-        if (!rc) rc = tmpt_render(scene, cam, desc, image.data(), &rays);
+        if (!rc && !temporal) rc = tmpt_render(scene, cam, desc, image.data(), &rays);
+        if (!rc && temporal) rc = tmpt_render_radiance(scene, cam, desc, rad.data(), image.data(), &rays);
         if (!rc) rc = tmpt_get_stats(scene, &st);
+        if (!rc && temporal) {
+            rc = tmpt_render_motion(scene, cam, cam, f ? prev.data() : nullptr, n, desc, mot.data(), nullptr);
+            if (!rc && f == 0) {  // a history of length one
+                acc = rad;
+                timage = image;
+            } else if (!rc) {
+                tmpt_temporal_desc td;
+                memset(&td, 0, sizeof(td));
+                td.width = w;
+                td.height = h;
+                rc = tmpt_temporal(scene, &td, rad.data(), mot.data(), pmot.data(), acc.data(), rad.data(), timage.data());
+                if (!rc) acc.swap(rad);
+            }
+            pmot = mot;
+            prev = cur;
+        }
         if (rc) break;
+        if (temporal) {
+            char tname[32];
+            snprintf(tname, sizeof(tname), "_temporal_%03d.png", f);
+            rc = tmpt_write_png((stem + tname).c_str(), timage.data(), w, h);
+            if (rc) break;
+        }
         char name[32];
         snprintf(name, sizeof(name), "_%03d.png", f);
         printf("frame %d: twist %.2f deg, %s %.3f ms, bvh_cost %.3f, %.1f K Rays in %.3f ms\n", f,
@@ -250,11 +290,13 @@ int main(int argc, const char** argv)
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
                "[--denoise file.png] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
-               "[--twist deg,frames [--rebuild]]\n"
+               "[--twist deg,frames [--rebuild] [--temporal]]\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
                "any pixel within radius columns and rows of it\n"
                "  --twist: frames of the mesh twisted about y by up to deg on one scene, each a tmpt_scene_update "
-               "(a refit; --rebuild: a full build), to <out>_000.png ...\n");
+               "(a refit; --rebuild: a full build), to <out>_000.png ...\n"
+               "  --temporal (with --twist, --seed sample): each frame draws its own samples (sample_base) and is "
+               "blended with the reprojected accumulation of the frames before it, to <out>_temporal_000.png ...\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -269,7 +311,7 @@ int main(int argc, const char** argv)
     const char* aov = nullptr;
     const char* denoised = nullptr;
     const char* spp_map = nullptr;
-    bool adaptive = false, twist = false, rebuild = false;
+    bool adaptive = false, twist = false, rebuild = false, temporal = false;
     double twist_deg = 0.0;
     int twist_frames = 0;
     tmpt_adaptive_desc ad;
@@ -312,6 +354,7 @@ int main(int argc, const char** argv)
             twist = true;
         }
         else if (!strcmp(argv[i], "--rebuild")) rebuild = true;
+        else if (!strcmp(argv[i], "--temporal")) temporal = true;
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -334,6 +377,14 @@ int main(int argc, const char** argv)
     }
     if (spp_map && !adaptive) { printf("ERROR: --spp-map needs --adaptive\n"); return 1; }
     if (rebuild && !twist) { printf("ERROR: --rebuild needs --twist\n"); return 1; }
+    if (temporal && (!twist || rebuild || seed != TMPT_SEED_SAMPLE || engine != TMPT_ENGINE_PERSISTENT)) {
+        printf("ERROR: --temporal needs --twist without --rebuild, --seed sample and the persistent engine\n");
+        return 1;
+    }
+    if (temporal && (long long)(twist_frames - 1) * spp > 64512) {
+        printf("ERROR: --temporal: (FRAMES - 1) * spp must not exceed 64512 (option sample_base)\n");
+        return 1;
+    }
     if (twist && (gpus > 1 || adaptive || aov || denoised)) {
         printf("ERROR: --twist runs on one device (--gpus 1), without --adaptive, --aov and --denoise\n");
         return 1;
@@ -360,7 +411,7 @@ int main(int argc, const char** argv)
     float box[6];
     tmpt_octree_bounds(bmin, bmax, box);
     if (twist) {  // the frames of one scene handle, each written by render_twist
-        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, out)) {
+        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, temporal, out)) {
             printf("ERROR: %s\n", tmpt_last_error());
             return 1;
         }

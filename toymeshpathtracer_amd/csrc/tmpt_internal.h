@@ -329,7 +329,9 @@ struct Options {
     int ploc_radius = 32; // PLOC nearest-neighbour search radius
     float sah_c_leaf = 0.7f, sah_c_tri = 0.5f;  // SAH collapse costs (inner node = 1)
     // render (tmpt_scene_set_option)
-    int sample_block = 0;     // sample seeding: samples per work unit, a power of two (0 = auto)
+    int sample_base = 0;      // sample seeding: sample s starts 2^16 (s + sample_base) steps into the pixel's stream
+                              // (host only: ensure_sample_tables builds J_(s + B); 0 .. 64512)
+    int sample_block = 0;    // sample seeding: samples per work unit, a power of two (0 = auto)
     int rowstream_dynamic = 1;  // row seeding, streaming: windows and spread follow the live rows
     int row_flag_leaves = 1;    // row seeding, streaming, octree answering: flag-only leaves (TIES 2)
     int row_occ = 0;            // row seeding, streaming: worker waves per SIMD (0 = by load, 4, 5)
@@ -382,6 +384,8 @@ struct Options {
     int pop_key_cap = -1;     // test hook: at most this many key bits in a stack entry (-1 = no cap; below
                               // kPopKeyMin there is no key and nothing is culled)
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
+    int motion_tile = -1;     // tmpt_render_motion: a wave takes an 8 x 8 block of pixels (1), 64 pixels of a row
+                              // (0), or the measured choice (-1)
     int denoise_lds = -1;     // tmpt_denoise: levels of stride 1 and 2 read an LDS tile + halo (1), every level
                               // reads global memory directly (0), or the measured choice per stride (-1)
 };
@@ -460,6 +464,7 @@ struct Scene {
     DeviceBuffer<uint32_t> chk;  // the checked build's device word triple (kChk* codes), else unused
     Event render_ev[2];          // first / last kernel of a render
     DeviceBuffer<> ws;           // render workspace, kept and grown on demand
+    DeviceBuffer<float> motion_prev;  // tmpt_render_motion: a host prev_tris uploaded (kept, grown, never shrunk)
     // progressive spp: per-pixel {colour sum xyz, rng} of the last pass (kept,
     // grown), and the shard it belongs to (width, height, spp, band_rows,
     // shard, num_shards, next sample)

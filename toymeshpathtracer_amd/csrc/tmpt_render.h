@@ -2,7 +2,8 @@
 // the persistent path engine and the host side of a render call;
 // tmpt_rows.hip: the row engines; tmpt_mega.hip: the megakernel;
 // tmpt_wavefront.hip: the wavefront engine; tmpt_hitscene.hip: the batched
-// queries; tmpt_aov.hip: the AOV pass;
+// queries; tmpt_aov.hip: the AOV pass; tmpt_motion.hip: the motion pass and
+// the reprojected history;
 // tmpt_denoise.hip: the filter over a finished frame): the kernel argument
 // block of one render call, the wave helpers, the host helpers of a render
 // call (defined in tmpt_render.hip) and the entry points of the engines that
@@ -131,7 +132,8 @@ int occupancy_grid(const void* fn, int block, size_t dyn_lds, int device);
 int ensure_ws(Scene& s, size_t bytes);
 SceneView view(const Scene& s);
 RenderArgs make_args(const tmpt_camera* c, const tmpt_render_desc* d);
-// sample_seed's jump tables on the device for samples [0, spp) (Scene::jt, grown, never shrunk)
+// sample_seed's jump tables on the device for samples [0, spp) of the window that
+// option sample_base opens (Scene::jt, grown, never shrunk)
 int ensure_sample_tables(Scene& s, int32_t spp, const char* what);
 // a jump table uploaded into a new buffer that replaces dst's on success
 int upload_tables(DeviceBuffer<uint32_t>& dst, const std::vector<uint32_t>& tab, const char* what);
@@ -142,8 +144,8 @@ int wait_caller_stream(Scene& s, const tmpt_render_desc* d, const char* what);
 int32_t camera_root_check(const Scene& s, const Camera& cam);
 // the statistics of the last render, zeroed before a new one
 void reset_render_stats(Scene& s);
-// sample_seed's byte tables for jumps J_i = M^(i * stride), i in [0, count)
-void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& tab);
+// sample_seed's byte tables for jumps J_i = M^((first + i) * stride), i in [0, count)
+void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& tab, uint32_t first = 0);
 
 // ---- the engines outside tmpt_render.hip (its render() picks one)
 // tmpt_mega.hip
@@ -176,5 +178,16 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
 // normal_exp and sigmas.  d_out32 or d_out8 may be null; d_out32 may be d_in.
 int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt_aov_pixel* d_aov, float4* d_out32,
             uint32_t* d_out8);
+
+// tmpt_motion.hip: the motion pass of one shard (tmpt_render_motion), d_out on
+// the device; d_prev the previous pose on the device (9 floats per triangle) or
+// null (the scene's own vertices)
+int render_motion(Scene& s, const tmpt_camera* cam, const tmpt_camera* prev_cam, const float* d_prev,
+                  const tmpt_render_desc* d, tmpt_motion_pixel* d_out, uint64_t* ray_count);
+// tmpt_motion.hip: the reprojected history (tmpt_temporal) over a whole frame,
+// every pointer on the device; d (checked by the caller) holds the resolved
+// n_max and sigma_depth.  d_out32 or d_out8 may be null; d_out32 may be d_cur.
+int temporal(Scene& s, const tmpt_temporal_desc* d, const float4* d_cur, const tmpt_motion_pixel* d_motion,
+             const tmpt_motion_pixel* d_pmotion, const float4* d_hist, float4* d_out32, uint32_t* d_out8);
 
 }  // namespace tmpt

@@ -1935,12 +1935,12 @@ void xorshift_power(uint64_t n, uint32_t* acc)
 
 }  // namespace
 
-// sample_seed's byte tables for jumps J_i = M^(i * stride), i in [0, count)
-void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& tab)
+// sample_seed's byte tables for jumps J_i = M^((first + i) * stride), i in [0, count)
+void jump_tables(uint64_t stride_steps, int32_t count, std::vector<uint32_t>& tab, uint32_t first)
 {
     uint32_t stride[32], J[32];
     xorshift_power(stride_steps, stride);
-    for (int j = 0; j < 32; ++j) J[j] = 1u << j;
+    xorshift_power(stride_steps * first, J);  // the identity for first = 0
     tab.assign((size_t)count * 1024u, 0u);
     for (int32_t i = 0; i < count; ++i) {
         uint32_t* t = tab.data() + (size_t)i * 1024u;
@@ -2720,11 +2720,14 @@ int upload_tables(DeviceBuffer<uint32_t>& dst, const std::vector<uint32_t>& tab,
     return 0;
 }
 
+// Option sample_base = B: table s holds J_(s + B), so every kernel's
+// sample_seed(jt, s, ...) starts 2^16 (s + B) steps into the pixel's stream
+// (setting the option drops the tables: jt_spp = 0)
 int ensure_sample_tables(Scene& s, int32_t spp, const char* what)
 {
     if (s.jt_spp >= spp) return 0;
     std::vector<uint32_t> tab;
-    sample_jump_tables(spp, tab);
+    jump_tables(kSampleStride, spp, tab, (uint32_t)s.opt.sample_base);
     if (int rc = upload_tables(s.jt, tab, what)) return rc;
     s.jt_spp = spp;
     return 0;
