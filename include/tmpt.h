@@ -672,6 +672,86 @@ int tmpt_render_adaptive(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_r
 int tmpt_denoise(tmpt_scene* scene, const tmpt_denoise_desc* desc, const float* rgba32f_in,
                  const tmpt_aov_pixel* aov, float* rgba32f_out, uint8_t* rgba8_out);
 
+/* ---- The noise-aware filter: luminance moments and wavelet shrinkage.
+ *
+ * tmpt_render_moments is tmpt_render_adaptive with the same arguments, plus each
+ * pixel's luminance moments.  Every output but moments_out, the ray count, info,
+ * the statistics, the restrictions (sample seeding, the persistent engine,
+ * spp_min >= 2, the per-sample colour buffer and its -12) and every rule of
+ * tmpt_render_adaptive hold bit for bit: the radius rule, shards and bands, the
+ * option sample_base, TMPT_FLAG_OUT_DEVICE, TMPT_FLAG_WAIT_STREAM.
+ *   ad NULL  means the UNIFORM schedule spp_min = desc->spp: one pass, every pixel
+ *            at n_p = desc->spp (so desc->spp >= 2).  It does NOT mean the
+ *            adaptive defaults, as it does in tmpt_render_adaptive; pass a zeroed
+ *            tmpt_adaptive_desc with threshold = -1 for those.
+ *   moments_out  is required (-22 without it; the other three outputs may then
+ *            all be NULL): 4 floats per pixel in the compact tile layout, 16-byte
+ *            aligned where it is a device pointer.  With m1, m2 the sums stated
+ *            above (carried in sample order over the pixel's n_p samples) and
+ *            fn = (float)n_p:
+ *              mom = { m1 / fn,  m2 / fn,  1.0f / fn,  1.0f }
+ * A moments tile is a frame in the sense tmpt_temporal uses: its .w is a history
+ * of length one.  Temporal use needs no call of its own: pass the moments frame
+ * through tmpt_temporal exactly as the colour frame goes (as rgba32f_cur, the
+ * previous accumulated moments as rgba32f_history), with the same motion records,
+ * n_max and sigma_depth; the result is {mean mu1, mean mu2, mean 1/n, history
+ * length} over the same taps.  rgba8_out of that call is meaningless and may be NULL.
+ * Additive, the ABI version stays. */
+int tmpt_render_moments(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
+                        const tmpt_adaptive_desc* ad, float* rgba32f_out, float* moments_out,
+                        uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count);
+
+/* tmpt_denoise_moments: tmpt_denoise steered by a moments frame.  desc is read
+ * exactly as tmpt_denoise reads it; moments holds width * height float4 (a whole
+ * frame, like the other inputs: tmpt_render_moments' tiles assembled, or that
+ * frame accumulated by tmpt_temporal).  shrink > 0; 0 selects the default, 2.0f;
+ * negative, NaN or infinite is -22.  The validation order (shrink after the
+ * sigmas, moments with the other pointers), the aliasing rule (rgba32f_out may be
+ * rgba32f_in), the alignment of device pointers and the statistics are
+ * tmpt_denoise's.
+ *
+ * The arithmetic IS the contract: float32, one rounding per operation, no
+ * contraction, `/` correctly rounded, in the order written.  The guides, the 25
+ * taps, their skip rules, their weights w (the centre's h[2]*h[2] included), csum
+ * and wsum are tmpt_denoise's own (tmpt_denoise_desc above).  c_0 = rgba32f_in,
+ * and c_(L+1) is that filter's level L over c_L: the bits tmpt_denoise produces.
+ * Once per call, per pixel (mom = the pixel's moments):
+ *   ne   = mom.w / mom.z                                  effective sample count
+ *   v_0  = fmaxf(0.0f, mom.y - mom.x * mom.x) / fmaxf(ne - 1.0f, 1.0f)
+ *                                                         variance of the pixel's mean luminance
+ *   keep = {0, 0, 0}
+ * Level L = 0 .. levels-1, stride s = 1 << L, pixel p:
+ *   vsum = 0;  for every tap q that counts, in the taps' order:  vsum = vsum + v_L(q) * (w * w)
+ *   v_(L+1)(p) = vsum / (wsum * wsum)
+ *   gsum = 0, ksum = 0                                    a 3x3 Gaussian of v_L, distance 1 at every level
+ *   for j = -1 .. 1 (outer), i = -1 .. 1 (inner): q = p + (i, j)
+ *       skipped: q outside the frame;  cov_q != cov_p
+ *       k = k3[i+1] * k3[j+1], k3 = {0.25f, 0.5f, 0.25f}
+ *       gsum = gsum + v_L(q) * k;   ksum = ksum + k
+ *   g    = gsum / ksum                                    ksum >= 0.25: the centre counts
+ *   d.k  = c_L(p).k - c_(L+1)(p).k           k = r, g, b  the detail this level removed
+ *   dY   = (0.2126f * d.r + 0.7152f * d.g) + 0.0722f * d.b
+ *   e = dY * dY;   n = shrink * g
+ *   gain = e > n ? (e - n) / e : 0.0f                     a NaN compares false
+ *   keep.k = keep.k + d.k * gain
+ * After the last level N = levels:
+ *   out.k = c_N(p).k + keep.k;   out.w = in.w
+ *   rgba8_out packs out as every render packs its pixels
+ * In words: the filter runs as before, and at every level each pixel takes back
+ * the part of its removed detail that the noise estimate cannot explain.  Nothing
+ * is screened, as in tmpt_denoise; fmaxf returns the other operand for a NaN; sky
+ * pixels follow the same statements with their plain weights.  What follows:
+ *   - on a frame of positive finite values with v_0 > 0 everywhere and
+ *     shrink = 3e38f every gain is 0: the output is tmpt_denoise's, bit for bit;
+ *   - a pixel whose taps are all skipped but the centre has c_(L+1) = c_L, d = 0,
+ *     and passes through.
+ * The render option denoise_lds selects the staged or the direct kernels as for
+ * tmpt_denoise; the output is the same for every value.  Additive, the ABI
+ * version stays. */
+int tmpt_denoise_moments(tmpt_scene* scene, const tmpt_denoise_desc* desc, float shrink,
+                         const float* rgba32f_in, const tmpt_aov_pixel* aov, const float* moments,
+                         float* rgba32f_out, uint8_t* rgba8_out);
+
 /* ---- Temporal accumulation: the motion pass and the reprojected history.
  * Everything below is float32 arithmetic that rounds once per operation and is
  * not contracted; '/' and sqrtf are correctly rounded; operations happen in the

@@ -17,6 +17,8 @@ reference                   here
 (none: float frame)         :meth:`Scene.trace_radiance` (the render's linear radiance beside its bytes)
 (none: denoiser)            :meth:`Scene.denoise` (edge-avoiding a-trous filter guided by the AOV records)
 (none: adaptive sampling)   :meth:`Scene.trace_adaptive` (per-pixel sample counts by a variance test)
+(none: noise-aware filter)  :meth:`Scene.trace_moments` (the frame with each pixel's luminance moments) and
+                            :meth:`Scene.denoise_moments` (the filter steered by them: wavelet shrinkage)
 (none: scene update)        :meth:`Scene.update` (new triangles in place: a device BVH refit, or a rebuild)
 (none: temporal)            :meth:`Scene.trace_motion` (:data:`MOTION_DTYPE` records: where each pixel's surface
                             was one frame ago) and :meth:`Scene.temporal` (the reprojected, accumulated history);
@@ -224,7 +226,8 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_scene_build_octree", "tmpt_octree_bounds", "tmpt_octree_digest",
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
-           "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal")
+           "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal", "tmpt_render_moments",
+           "tmpt_denoise_moments")
 
 
 def _check(rc: int, what: str) -> None:
@@ -801,6 +804,114 @@ class Scene:
         _check(_denoise(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
                         aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
                         img.ctypes.data_as(ctypes.c_void_p)), "denoise")
+        return res, img
+
+    def trace_moments(self, camera: Camera, width: int, height: int, spp: int, spp_min: Optional[int] = None,
+                      spp_step: int = 0, threshold: float = -1.0, radius: int = 0, band_rows: int = 0, shard: int = 0,
+                      num_shards: int = 1, out=None, wait_stream="current"):
+        """:meth:`trace_adaptive` that also hands out each pixel's luminance
+        moments (tmpt_render_moments; include/tmpt.h states them): returns
+        (radiance, moments float32[tile_rows, width, 4], rgba8, spp_map, rays,
+        info) -- moments = {m1 / n, m2 / n, 1 / n, 1.0} over the pixel's n
+        samples, everything else bit for bit what :meth:`trace_adaptive` returns.
+        ``spp_min=None`` means uniform: one pass, every pixel at ``spp`` (>= 2);
+        ``spp_min=0`` the adaptive default.  A moments tile is a frame as
+        :meth:`temporal` reads one (alpha = a history of length one): accumulate
+        it exactly as the colour frame, then hand both to
+        :meth:`denoise_moments`.  ``out``: a 4-tuple of device pointers (float
+        tile or None, moments tile, rgba8 tile or None, int32 map or None); the
+        arrays returned are then None.  ``wait_stream`` as in :meth:`trace_image`."""
+        # bound on first use, as tmpt_render_adaptive is
+        fn = _sig("tmpt_render_moments", ctypes.c_int,
+                  [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_AdaptiveInfo),
+                   _u64p])
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        ad = None
+        if spp_min is not None:
+            ad = _AdaptiveDesc()
+            ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
+            ad = ctypes.byref(ad)
+        rows = int(_tile_rows(ctypes.byref(d)))
+        rays = ctypes.c_uint64()
+        inf = _AdaptiveInfo()
+        cam = camera._to_c()
+
+        def info():
+            return {"passes": int(inf.passes), "samples": int(inf.samples),
+                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
+
+        if out is not None:
+            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
+            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, ptr[0], ptr[1], ptr[2], ptr[3],
+                      ctypes.byref(inf), ctypes.byref(rays)), "trace_moments")
+            return None, None, None, None, int(rays.value), info()
+        rad = np.zeros((rows, width, 4), np.float32)
+        mom = np.zeros((rows, width, 4), np.float32)
+        img = np.zeros((rows, width, 4), np.uint8)
+        cnt = np.zeros((rows, width), np.int32)
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, rad.ctypes.data_as(ctypes.c_void_p),
+                  mom.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p),
+                  cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf), ctypes.byref(rays)), "trace_moments")
+        return rad, mom, img, cnt, int(rays.value), info()
+
+    def denoise_moments(self, radiance, aov, moments, spp: int, shrink: float = 0.0, levels: int = 0,
+                        normal_exp: int = -1, sigma_depth: float = 0.0, sigma_direct: float = 0.0, out=None,
+                        width: Optional[int] = None, height: Optional[int] = None, wait_stream="current"):
+        """The noise-aware filter (tmpt_denoise_moments; include/tmpt.h states its
+        arithmetic): :meth:`denoise` with the frame's ``moments`` float32[h, w, 4]
+        (:meth:`trace_moments`, or that frame accumulated by :meth:`temporal`) --
+        at every level each pixel takes back the part of its removed detail that
+        the noise estimate cannot explain.  ``shrink`` > 0 scales the estimate
+        (0.0: the default, 2.0; larger filters more, 3e38 is :meth:`denoise`).
+        Everything else, the host and the device form (``moments`` then a device
+        pointer too) as :meth:`denoise`."""
+        # bound on first use, as tmpt_render_adaptive is
+        fn = _sig("tmpt_denoise_moments", ctypes.c_int,
+                  [ctypes.c_void_p, ctypes.POINTER(_DenoiseDesc), ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+        dev = isinstance(radiance, int)
+        d = _DenoiseDesc()
+        if dev:
+            if width is None or height is None or out is None:
+                raise ValueError("denoise_moments: device pointers need width, height and out")
+            h, w = int(height), int(width)
+        else:
+            radiance = np.ascontiguousarray(radiance, np.float32)
+            aov = np.ascontiguousarray(aov, AOV_DTYPE)
+            moments = np.ascontiguousarray(moments, np.float32)
+            h, w = radiance.shape[:2]
+            if radiance.shape != (h, w, 4) or aov.shape != (h, w) or moments.shape != (h, w, 4):
+                raise ValueError("denoise_moments: radiance and moments [h, w, 4] and aov [h, w] of one whole frame")
+        d.width, d.height, d.spp, d.levels, d.normal_exp = w, h, spp, levels, normal_exp
+        d.sigma_depth, d.sigma_direct = sigma_depth, sigma_direct
+        if dev:
+            d.flags = FLAG_OUT_DEVICE
+            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+            if ws is not None:
+                d.flags |= FLAG_WAIT_STREAM
+                d.wait_stream = int(ws)
+            f32, u8 = out
+            _check(fn(self._h, ctypes.byref(d), shrink, ctypes.c_void_p(radiance), ctypes.c_void_p(int(aov)),
+                      ctypes.c_void_p(int(moments)), None if f32 is None else ctypes.c_void_p(int(f32)),
+                      None if u8 is None else ctypes.c_void_p(int(u8))), "denoise_moments")
+            return None, None
+        res = np.zeros((h, w, 4), np.float32) if out is None else out
+        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+                and res.flags.c_contiguous):
+            raise ValueError("denoise_moments: out must be a contiguous float32 array [h, w, 4] (it may be radiance "
+                             "itself)")
+        img = np.zeros((h, w, 4), np.uint8)
+        _check(fn(self._h, ctypes.byref(d), shrink, radiance.ctypes.data_as(ctypes.c_void_p),
+                  aov.ctypes.data_as(ctypes.c_void_p), moments.ctypes.data_as(ctypes.c_void_p),
+                  res.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p)), "denoise_moments")
         return res, img
 
     def trace_motion(self, camera: Camera, prev_camera: Camera, width: int, height: int, prev_triangles=None,

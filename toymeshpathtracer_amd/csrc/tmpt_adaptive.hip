@@ -13,7 +13,8 @@
 // come from the own tests dilated over the tile instead: k_adapt_update_own,
 // k_adapt_pack, k_adapt_dilate and k_adapt_gather below; radius 0 launches none
 // of them.  k_adapt_final scales, packs and writes the three
-// outputs.  The host reads the next list's length (one word, with the pass's
+// outputs; tmpt_render_moments is the same call with k_adapt_final_mom in its
+// place, which also writes each pixel's luminance moments.  The host reads the next list's length (one word, with the pass's
 // counters) after every pass but the last: that length sizes the next launch.
 #include <hip/hip_runtime.h>
 
@@ -288,19 +289,44 @@ __global__ void __launch_bounds__(256) k_adapt_final(const AdaptState* __restric
     if (ospp) ospp[i] = st.n;
 }
 
+// k_adapt_final with the pixel's luminance moments beside the three outputs
+// (tmpt_render_moments; include/tmpt.h): {m1 / fn, m2 / fn, 1.0f / fn, 1.0f},
+// fn = (float)n -- a kernel of its own, so that tmpt_render_adaptive keeps
+// k_adapt_final's code as it is.  mom is never null.
+__global__ void __launch_bounds__(256) k_adapt_final_mom(const AdaptState* __restrict__ state, int64_t n,
+                                                         float4* __restrict__ o32, uint32_t* __restrict__ o8,
+                                                         int32_t* __restrict__ ospp, float4* __restrict__ mom)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const AdaptState st = state[i];
+    const float fn = (float)st.n;
+    const float recip = 1.0f / fn;
+    const f3 sum = mk(st.r, st.g, st.b);
+    if (o32) {
+        const f3 col = sum * recip;
+        o32[i] = make_float4(col.x, col.y, col.z, 1.0f);
+    }
+    if (o8) o8[i] = pack_pixel(sum, recip);
+    if (ospp) ospp[i] = st.n;
+    mom[i] = make_float4(st.m1 / fn, st.m2 / fn, recip, 1.0f);
+}
+
 static size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 // ad: the resolved descriptor (defaults applied, ranges checked by the
-// caller); d_f32 / d_u8 / d_spp: device tiles or null.
+// caller); d_f32 / d_u8 / d_spp: device tiles or null.  d_mom (tmpt_render_moments,
+// `what` its name): the moments tile, or null.
 int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
-                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count)
+                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count,
+                    float4* d_mom, const char* what)
 {
     RenderArgs a = make_args(cam, d);
     s.row_render = false;
     s.pixel_render = false;
-    if (int rc = ensure_sample_tables(s, a.spp, "tmpt_render_adaptive")) return rc;
+    if (int rc = ensure_sample_tables(s, a.spp, what)) return rc;
     a.jt = s.jt;
-    if (int rc = wait_caller_stream(s, d, "tmpt_render_adaptive")) return rc;
+    if (int rc = wait_caller_stream(s, d, what)) return rc;
     if (ensure_counters(s)) return -1;
     a.root_check = camera_root_check(s, a.cam);
     tmpt_adaptive_info inf;
@@ -323,7 +349,7 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
         const size_t o_own = o_total + 256, o_bits = o_own + align256(slots), o_dil = o_bits + align256(8 * (size_t)nwords);
         const size_t need = radius > 0 ? o_dil + align256(8 * (size_t)nwords) : o_total + 256;
         if (!s.adapt_buf.reserve(need)) {
-            set_error("tmpt_render_adaptive: out of device memory (the per-pixel state and lists)");
+            set_error(std::string(what) + ": out of device memory (the per-pixel state and lists)");
             return -12;
         }
         TMPT_HIP(s.adapt_host.ensure(64));
@@ -410,7 +436,11 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
             n1 = std::min(n1 + ad->spp_step, a.spp);
         }
         if (rc) return rc;
-        k_adapt_final<<<(unsigned)((a.slots + 255) / 256), 256, 0, s.stream>>>(state, a.slots, d_f32, d_u8, d_spp);
+        const unsigned fb = (unsigned)((a.slots + 255) / 256);
+        if (d_mom)
+            k_adapt_final_mom<<<fb, 256, 0, s.stream>>>(state, a.slots, d_f32, d_u8, d_spp, d_mom);
+        else
+            k_adapt_final<<<fb, 256, 0, s.stream>>>(state, a.slots, d_f32, d_u8, d_spp);
         TMPT_HIP(hipGetLastError());
     }
     TMPT_HIP(hipEventRecord(e1, s.stream));

@@ -887,99 +887,138 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
     TMPT_GUARD_END
 }
 
-int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d,
-                         const tmpt_adaptive_desc* ad, float* rgba32f_out, uint8_t* rgba8_out, int32_t* spp_out,
-                         tmpt_adaptive_info* info, uint64_t* ray_count)
+// tmpt_render_adaptive and tmpt_render_moments: one body.  `name` is the call's
+// name in errors; with_mom: moments_out is required, and ad NULL means the
+// uniform schedule spp_min = desc->spp, not the adaptive defaults.
+static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const tmpt_camera* cam,
+                         const tmpt_render_desc* d, const tmpt_adaptive_desc* ad, float* rgba32f_out, float* moments_out,
+                         uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count)
 {
-    TMPT_GUARD_BEGIN
-    if (!h || !cam || !d) return bad("tmpt_render_adaptive: null argument");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_adaptive: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_adaptive: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_adaptive: invalid samplesPerPixel");
+    const auto no = [name](const char* msg) { return bad((std::string(name) + ": " + msg).c_str()); };
+    if (!h || !cam || !d) return no("null argument");
+    if (d->width < 1 || d->width > 10000) return no("invalid width");
+    if (d->height < 1 || d->height > 10000) return no("invalid height");
+    if (d->spp < 1 || d->spp > 1024) return no("invalid samplesPerPixel");
     if (d->seed_mode != TMPT_SEED_SAMPLE)
-        return bad("tmpt_render_adaptive: seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a sample is a "
-                   "function of pixel and sample)");
-    if (d->engine != TMPT_ENGINE_PERSISTENT) return bad("tmpt_render_adaptive: engine must be TMPT_ENGINE_PERSISTENT");
+        return no("seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a sample is a "
+                  "function of pixel and sample)");
+    if (d->engine != TMPT_ENGINE_PERSISTENT) return no("engine must be TMPT_ENGINE_PERSISTENT");
     if (d->spp_begin != 0 || d->spp_count != 0)
-        return bad("tmpt_render_adaptive: spp_begin / spp_count must be 0 (the call makes its own passes)");
-    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_adaptive: TMPT_FLAG_COUNT_VISITS is not supported");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_render_adaptive: invalid shard");
+        return no("spp_begin / spp_count must be 0 (the call makes its own passes)");
+    if (d->flags & TMPT_FLAG_COUNT_VISITS) return no("TMPT_FLAG_COUNT_VISITS is not supported");
+    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards)) return no("invalid shard");
     tmpt_adaptive_desc r;  // the defaults, in one place ("Adaptive sampling")
     memset(&r, 0, sizeof(r));
     if (ad) r = *ad;
     else r.threshold = -1.0f;
+    if (!ad && with_mom) r.spp_min = d->spp;  // uniform: one pass, every pixel at desc->spp
     if (r.spp_min == 0) r.spp_min = std::min(24, d->spp);
     if (r.spp_step == 0) r.spp_step = 8;
     if (!(r.threshold >= -3.0e38f) || !(r.threshold <= 3.0e38f))
-        return bad("tmpt_render_adaptive: threshold must be finite (negative = default)");
+        return no("threshold must be finite (negative = default)");
     if (r.threshold < 0.0f) r.threshold = 0.015f;
-    if (r.spp_min < 2 || r.spp_min > d->spp)
-        return bad("tmpt_render_adaptive: spp_min outside 2 .. spp (0 = default)");
-    if (r.spp_step < 1) return bad("tmpt_render_adaptive: spp_step must not be negative (0 = default)");
-    if (r.radius < 0 || r.radius > 8) return bad("tmpt_render_adaptive: radius outside 0 .. 8 (0 = no neighbourhood rule)");
+    if (r.spp_min < 2 || r.spp_min > d->spp) return no("spp_min outside 2 .. spp (0 = default)");
+    if (r.spp_step < 1) return no("spp_step must not be negative (0 = default)");
+    if (r.radius < 0 || r.radius > 8) return no("radius outside 0 .. 8 (0 = no neighbourhood rule)");
     if (1 + (d->spp - r.spp_min + r.spp_step - 1) / r.spp_step > 64)
-        return bad("tmpt_render_adaptive: spp_min / spp_step give a schedule of more than 64 passes");
-    if (!rgba32f_out && !rgba8_out && !spp_out)
-        return bad("tmpt_render_adaptive: no output (rgba32f_out, rgba8_out and spp_out are all null)");
+        return no("spp_min / spp_step give a schedule of more than 64 passes");
+    if (with_mom) {
+        if (!moments_out) return no("moments_out is required");
+    } else if (!rgba32f_out && !rgba8_out && !spp_out) {
+        return no("no output (rgba32f_out, rgba8_out and spp_out are all null)");
+    }
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev_out && ((reinterpret_cast<uintptr_t>(rgba32f_out) & 15u) != 0 ||
+    if (dev_out && (((reinterpret_cast<uintptr_t>(rgba32f_out) | reinterpret_cast<uintptr_t>(moments_out)) & 15u) != 0 ||
                     ((reinterpret_cast<uintptr_t>(rgba8_out) | reinterpret_cast<uintptr_t>(spp_out)) & 3u) != 0))
-        return bad("tmpt_render_adaptive: device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
-                   "spp_out 4)");
+        return no(with_mom ? "device outputs must be aligned (rgba32f_out and moments_out 16 bytes, rgba8_out and "
+                             "spp_out 4)"
+                           : "device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
+                             "spp_out 4)");
     (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
     Scene& s = h->s;
     TMPT_HIP(hipSetDevice(s.device));
     const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width;
     // host outputs are staged in device tiles of the library's own
     float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
+    float4* d_m = dev_out ? reinterpret_cast<float4*>(moments_out) : nullptr;
     uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
     int32_t* d_n = dev_out ? spp_out : nullptr;
-    DeviceBuffer<float4> own_f;
+    DeviceBuffer<float4> own_f, own_m;
     DeviceBuffer<uint32_t> own_8;
     DeviceBuffer<int32_t> own_n;
     if (!dev_out && px &&
-        ((rgba32f_out && !own_f.alloc(px * sizeof(float4))) || (rgba8_out && !own_8.alloc(px * 4)) ||
-         (spp_out && !own_n.alloc(px * 4))))
-        return bad("tmpt_render_adaptive: out of device memory");
+        ((rgba32f_out && !own_f.alloc(px * sizeof(float4))) || (moments_out && !own_m.alloc(px * sizeof(float4))) ||
+         (rgba8_out && !own_8.alloc(px * 4)) || (spp_out && !own_n.alloc(px * 4))))
+        return no("out of device memory");
     if (own_f) d_f = own_f;
+    if (own_m) d_m = own_m;
     if (own_8) d_8 = own_8;
     if (own_n) d_n = own_n;
-    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count);
-    if (!rc) rc = check_report(s, "tmpt_render_adaptive");
+    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count, d_m, name);
+    if (!rc) rc = check_report(s, name);
     if (!rc && !dev_out && px) {
         if ((rgba32f_out && hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
+            (moments_out && hipMemcpy(moments_out, d_m, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
             (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
             (spp_out && hipMemcpy(spp_out, d_n, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error("tmpt_render_adaptive: readback failed"), -1);
+            rc = (set_error(std::string(name) + ": readback failed"), -1);
     }
     return rc;
+}
+
+int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d,
+                         const tmpt_adaptive_desc* ad, float* rgba32f_out, uint8_t* rgba8_out, int32_t* spp_out,
+                         tmpt_adaptive_info* info, uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    return adaptive_call("tmpt_render_adaptive", false, h, cam, d, ad, rgba32f_out, nullptr, rgba8_out, spp_out, info,
+                         ray_count);
     TMPT_GUARD_END
 }
 
-int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f_in, const tmpt_aov_pixel* aov,
-                 float* rgba32f_out, uint8_t* rgba8_out)
+int tmpt_render_moments(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d,
+                        const tmpt_adaptive_desc* ad, float* rgba32f_out, float* moments_out, uint8_t* rgba8_out,
+                        int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count)
 {
     TMPT_GUARD_BEGIN
+    return adaptive_call("tmpt_render_moments", true, h, cam, d, ad, rgba32f_out, moments_out, rgba8_out, spp_out, info,
+                         ray_count);
+    TMPT_GUARD_END
+}
+
+// tmpt_denoise_moments' default shrink: the grid point tools/noise_aware_sweep.py's rule
+// picks ("Noise-aware filter")
+constexpr float kShrinkDefault = 2.0f;
+
+// tmpt_denoise and tmpt_denoise_moments: one body.  `name` is the call's name in
+// errors; with_mom: the moments frame is required and shrink is read.
+static int denoise_call(const char* name, bool with_mom, tmpt_scene* h, const tmpt_denoise_desc* d, float shrink,
+                        const float* rgba32f_in, const tmpt_aov_pixel* aov, const float* moments, float* rgba32f_out,
+                        uint8_t* rgba8_out)
+{
+    const auto no = [name](const char* msg) { return bad((std::string(name) + ": " + msg).c_str()); };
     // the descriptor first, before anything that needs a scene or a device
-    if (!d) return bad("tmpt_denoise: null descriptor");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_denoise: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_denoise: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_denoise: invalid samplesPerPixel");
-    if (d->levels < 0 || d->levels > 6) return bad("tmpt_denoise: levels out of range (1..6, 0 = 5)");
-    if (d->normal_exp < -1 || d->normal_exp > 8) return bad("tmpt_denoise: normal_exp out of range (0..8, -1 = 5)");
+    if (!d) return no("null descriptor");
+    if (d->width < 1 || d->width > 10000) return no("invalid width");
+    if (d->height < 1 || d->height > 10000) return no("invalid height");
+    if (d->spp < 1 || d->spp > 1024) return no("invalid samplesPerPixel");
+    if (d->levels < 0 || d->levels > 6) return no("levels out of range (1..6, 0 = 5)");
+    if (d->normal_exp < -1 || d->normal_exp > 8) return no("normal_exp out of range (0..8, -1 = 5)");
     if (!(d->sigma_depth >= 0.0f) || !(d->sigma_depth <= 3.0e38f))
-        return bad("tmpt_denoise: sigma_depth must be finite and not negative (0 = auto)");
+        return no("sigma_depth must be finite and not negative (0 = auto)");
     if (!(d->sigma_direct >= 0.0f) || !(d->sigma_direct <= 3.0e38f))
-        return bad("tmpt_denoise: sigma_direct must be finite and not negative (0 = default)");
-    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return bad("tmpt_denoise: unknown flag");
-    if (!rgba32f_out && !rgba8_out) return bad("tmpt_denoise: no output (rgba32f_out and rgba8_out are both null)");
-    if (!h || !rgba32f_in || !aov) return bad("tmpt_denoise: null argument");
+        return no("sigma_direct must be finite and not negative (0 = default)");
+    if (with_mom && (!(shrink >= 0.0f) || !(shrink <= 3.4028235e38f)))
+        return no("shrink must be finite and not negative (0 = default)");
+    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
+    if (!rgba32f_out && !rgba8_out) return no("no output (rgba32f_out and rgba8_out are both null)");
+    if (!h || !rgba32f_in || !aov || (with_mom && !moments)) return no("null argument");
     const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
     if (dev && (((reinterpret_cast<uintptr_t>(rgba32f_in) | reinterpret_cast<uintptr_t>(aov) |
-                  reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
+                  reinterpret_cast<uintptr_t>(moments) | reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
                 (reinterpret_cast<uintptr_t>(rgba8_out) & 3u) != 0))
-        return bad("tmpt_denoise: device pointers must be 16-byte aligned (rgba8_out: 4)");
+        return no("device pointers must be 16-byte aligned (rgba8_out: 4)");
+    if (shrink == 0.0f) shrink = kShrinkDefault;
     tmpt_denoise_desc r = *d;  // the defaults, in one place
     if (r.levels == 0) r.levels = 5;
     if (r.normal_exp < 0) r.normal_exp = 5;
@@ -996,25 +1035,45 @@ int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f
     DeviceBuffer<float4> own_in;
     DeviceBuffer<tmpt_aov_pixel> own_aov;
     DeviceBuffer<uint32_t> own_8;
+    const float4* d_mom = reinterpret_cast<const float4*>(moments);
+    DeviceBuffer<float4> own_mom;
     if (!dev) {  // host pointers: staged on the device; the float result is filtered in place there
         if (!own_in.alloc(n * sizeof(float4)) || !own_aov.alloc(n * sizeof(tmpt_aov_pixel)) ||
-            (rgba8_out && !own_8.alloc(n * 4)))
-            return bad("tmpt_denoise: out of device memory");
+            (rgba8_out && !own_8.alloc(n * 4)) || (with_mom && !own_mom.alloc(n * sizeof(float4))))
+            return no("out of device memory");
         if (hipMemcpy(own_in, rgba32f_in, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess)
-            return (set_error("tmpt_denoise: upload failed"), -1);
+            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess ||
+            (with_mom && hipMemcpy(own_mom, moments, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess))
+            return (set_error(std::string(name) + ": upload failed"), -1);
         d_in = own_in;
         d_aov = own_aov;
+        d_mom = own_mom;
         d_o32 = rgba32f_out ? own_in.get() : nullptr;
         d_o8 = own_8;
     }
-    int rc = denoise(s, &r, d_in, d_aov, d_o32, d_o8);
+    int rc = with_mom ? denoise_moments(s, &r, shrink, d_in, d_aov, d_mom, d_o32, d_o8)
+                      : denoise(s, &r, d_in, d_aov, d_o32, d_o8);
     if (!rc && !dev) {
         if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
             (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error("tmpt_denoise: readback failed"), -1);
+            rc = (set_error(std::string(name) + ": readback failed"), -1);
     }
     return rc;
+}
+
+int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f_in, const tmpt_aov_pixel* aov,
+                 float* rgba32f_out, uint8_t* rgba8_out)
+{
+    TMPT_GUARD_BEGIN
+    return denoise_call("tmpt_denoise", false, h, d, 0.0f, rgba32f_in, aov, nullptr, rgba32f_out, rgba8_out);
+    TMPT_GUARD_END
+}
+
+int tmpt_denoise_moments(tmpt_scene* h, const tmpt_denoise_desc* d, float shrink, const float* rgba32f_in,
+                         const tmpt_aov_pixel* aov, const float* moments, float* rgba32f_out, uint8_t* rgba8_out)
+{
+    TMPT_GUARD_BEGIN
+    return denoise_call("tmpt_denoise_moments", true, h, d, shrink, rgba32f_in, aov, moments, rgba32f_out, rgba8_out);
     TMPT_GUARD_END
 }
 

@@ -1,6 +1,6 @@
 // tmpt_cli.cpp -- the reference's command line (main.cpp:248-345) over the C ABI:
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
-//        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png]
+//        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png [--shrink K]]
 //        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
 //        [--twist DEG,FRAMES [--rebuild] [--temporal]]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
@@ -15,6 +15,10 @@
 // PREFIX_depth.png.
 // --denoise OUT.png (one device, --seed sample): beside the usual output, the frame's float
 // radiance (tmpt_render_radiance) filtered by tmpt_denoise with the AOV records as guides.
+// --shrink K (with --denoise): the noise-aware filter instead -- the radiance comes with its luminance
+// moments (tmpt_render_moments: uniform at spp, which must then be at least 2, or the --adaptive
+// schedule) and tmpt_denoise_moments filters it with shrink K (0 = the default).  Without --shrink
+// nothing changes.
 // --adaptive TAU[,MIN[,STEP[,RADIUS]]] (one device, --seed sample): the frame comes from tmpt_render_adaptive
 // with spp as the cap (MIN, STEP: spp_min, spp_step; left out or 0 = the defaults, a negative TAU
 // too; RADIUS 0..8, left out = 0: the neighbourhood rule -- a pixel goes on while the test holds for
@@ -110,14 +114,15 @@ static int write_aovs(const char* prefix, const float* tris, int32_t n, const fl
 // --denoise OUT.png on `device` (its own scene, the octree built as for the frame): the
 // sample-seeded radiance render (tmpt_render_radiance), the AOV pass at the same size and spp
 // (tmpt_render_aov) and the filter with its defaults (tmpt_denoise); the filtered frame's
-// packed pixels are written to `path`.
+// packed pixels are written to `path`.  shrink (--shrink; null without): the radiance comes from
+// tmpt_render_moments instead, uniform at spp, and tmpt_denoise_moments filters it.
 static int write_denoised(const char* path, const float* tris, int32_t n, const float box[6], const tmpt_camera* cam,
-                          int w, int h, int spp, int device)
+                          int w, int h, int spp, int device, const float* shrink)
 {
     tmpt_scene* scene = nullptr;
     if (tmpt_scene_create(tris, n, device, &scene)) return 1;
     const size_t P = (size_t)w * h;
-    std::vector<float> rad(P * 4);
+    std::vector<float> rad(P * 4), mom(shrink ? P * 4 : 0);
     std::vector<tmpt_aov_pixel> rec(P);
     std::vector<uint8_t> img(P * 4);
     tmpt_render_desc desc;
@@ -130,28 +135,35 @@ static int write_denoised(const char* path, const float* tris, int32_t n, const 
     uint64_t rays = 0, aov_rays = 0;
     tmpt_stats st;
     int rc = tmpt_scene_build_octree(scene, box, box + 3);
-    if (!rc) rc = tmpt_render_radiance(scene, cam, &desc, rad.data(), nullptr, &rays);
+    if (!rc && shrink)
+        rc = tmpt_render_moments(scene, cam, &desc, nullptr, rad.data(), mom.data(), nullptr, nullptr, nullptr, &rays);
+    else if (!rc)
+        rc = tmpt_render_radiance(scene, cam, &desc, rad.data(), nullptr, &rays);
     if (!rc) rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &aov_rays);
-    if (!rc) rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
+    if (!rc && shrink)
+        rc = tmpt_denoise_moments(scene, &dn, *shrink, rad.data(), rec.data(), mom.data(), nullptr, img.data());
+    else if (!rc)
+        rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
     if (!rc) rc = tmpt_get_stats(scene, &st);
     if (tmpt_scene_destroy(scene) && !rc) rc = 1;
     if (rc) return rc;
-    printf("Denoised frame: %.1f K Rays + %.1f K AOV Rays, filter %.3f ms\n", rays / 1000.0, aov_rays / 1000.0,
-           st.render_ms);
+    printf("Denoised frame%s: %.1f K Rays + %.1f K AOV Rays, filter %.3f ms\n", shrink ? " (noise-aware)" : "",
+           rays / 1000.0, aov_rays / 1000.0, st.render_ms);
     return tmpt_write_png(path, img.data(), w, h);
 }
 
 // --adaptive on `device` (its own scene, the octree built as for a frame): the adaptive render
 // into `image` (what --out writes), the spp map as grey uint8(n_p / spp * 255) and, with
-// `denoised`, the filter over the adaptive radiance guided by the AOV pass at spp.
+// `denoised`, the filter over the adaptive radiance guided by the AOV pass at spp.  shrink (--shrink
+// with --denoise; null without): the call is tmpt_render_moments and the filter tmpt_denoise_moments.
 static int render_adaptive_frame(const float* tris, int32_t n, const float box[6], const tmpt_camera* cam, int w, int h,
                                  int spp, int device, const tmpt_adaptive_desc* ad, std::vector<uint8_t>& image,
-                                 const char* spp_map, const char* denoised)
+                                 const char* spp_map, const char* denoised, const float* shrink)
 {
     tmpt_scene* scene = nullptr;
     if (tmpt_scene_create(tris, n, device, &scene)) return 1;
     const size_t P = (size_t)w * h;
-    std::vector<float> rad(P * 4);
+    std::vector<float> rad(P * 4), mom(shrink ? P * 4 : 0);
     std::vector<int32_t> cnt(P);
     tmpt_render_desc desc;
     memset(&desc, 0, sizeof(desc));
@@ -161,7 +173,10 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
     tmpt_stats st;
     uint64_t rays = 0;
     int rc = tmpt_scene_build_octree(scene, box, box + 3);
-    if (!rc) rc = tmpt_render_adaptive(scene, cam, &desc, ad, rad.data(), image.data(), cnt.data(), &info, &rays);
+    if (!rc && shrink)
+        rc = tmpt_render_moments(scene, cam, &desc, ad, rad.data(), mom.data(), image.data(), cnt.data(), &info, &rays);
+    else if (!rc)
+        rc = tmpt_render_adaptive(scene, cam, &desc, ad, rad.data(), image.data(), cnt.data(), &info, &rays);
     if (!rc) rc = tmpt_get_stats(scene, &st);
     if (!rc) {
         printf("Rendered scene at %ix%i, up to %ispp, adaptively in %.3f s (%d passes)\n", w, h, spp,
@@ -184,10 +199,14 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
         dn.width = w; dn.height = h; dn.spp = spp; dn.normal_exp = -1;
         uint64_t aov_rays = 0;
         rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &aov_rays);
-        if (!rc) rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
+        if (!rc && shrink)
+            rc = tmpt_denoise_moments(scene, &dn, *shrink, rad.data(), rec.data(), mom.data(), nullptr, img.data());
+        else if (!rc)
+            rc = tmpt_denoise(scene, &dn, rad.data(), rec.data(), nullptr, img.data());
         if (!rc) rc = tmpt_get_stats(scene, &st);
         if (!rc) {
-            printf("Denoised adaptive frame: %.1f K AOV Rays, filter %.3f ms\n", aov_rays / 1000.0, st.render_ms);
+            printf("Denoised adaptive frame%s: %.1f K AOV Rays, filter %.3f ms\n", shrink ? " (noise-aware)" : "",
+                   aov_rays / 1000.0, st.render_ms);
             rc = tmpt_write_png(denoised, img.data(), w, h);
         }
     }
@@ -289,10 +308,12 @@ int main(int argc, const char** argv)
     if (argc < 5) {
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
-               "[--denoise file.png] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
+               "[--denoise file.png [--shrink k]] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
                "[--twist deg,frames [--rebuild] [--temporal]]\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
                "any pixel within radius columns and rows of it\n"
+               "  --shrink (with --denoise): the noise-aware filter (tmpt_denoise_moments) over the frame and its "
+               "luminance moments, k > 0 scaling the noise estimate (0 = the default); spp >= 2\n"
                "  --twist: frames of the mesh twisted about y by up to deg on one scene, each a tmpt_scene_update "
                "(a refit; --rebuild: a full build), to <out>_000.png ...\n"
                "  --temporal (with --twist, --seed sample): each frame draws its own samples (sample_base) and is "
@@ -311,7 +332,8 @@ int main(int argc, const char** argv)
     const char* aov = nullptr;
     const char* denoised = nullptr;
     const char* spp_map = nullptr;
-    bool adaptive = false, twist = false, rebuild = false, temporal = false;
+    bool adaptive = false, twist = false, rebuild = false, temporal = false, have_shrink = false;
+    float shrink = 0.0f;
     double twist_deg = 0.0;
     int twist_frames = 0;
     tmpt_adaptive_desc ad;
@@ -333,6 +355,13 @@ int main(int argc, const char** argv)
         else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
         else if (!strcmp(argv[i], "--denoise") && i + 1 < argc) denoised = argv[++i];
         else if (!strcmp(argv[i], "--spp-map") && i + 1 < argc) spp_map = argv[++i];
+        else if (!strcmp(argv[i], "--shrink") && i + 1 < argc) {
+            if (sscanf(argv[++i], "%f", &shrink) != 1 || !(shrink >= 0.0f) || !(shrink <= 3.4028235e38f)) {
+                printf("ERROR: invalid --shrink argument '%s' (finite, not negative; 0 = the default)\n", argv[i]);
+                return 1;
+            }
+            have_shrink = true;
+        }
         else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) {
             int mn = 0, stp = 0, rad = 0;
             float tau = -1.0f;
@@ -367,6 +396,10 @@ int main(int argc, const char** argv)
     if (gpus < 1) gpus = 1;
     if (aov && gpus > 1) { printf("ERROR: --aov runs on one device (--gpus 1)\n"); return 1; }
     if (denoised && gpus > 1) { printf("ERROR: --denoise runs on one device (--gpus 1)\n"); return 1; }
+    if (have_shrink && (!denoised || seed != TMPT_SEED_SAMPLE)) {
+        printf("ERROR: --shrink needs --denoise and --seed sample\n");
+        return 1;
+    }
     if (denoised && seed != TMPT_SEED_SAMPLE) {
         printf("ERROR: --denoise needs --seed sample (the AOV records are a sample-seeded frame's)\n");
         return 1;
@@ -419,7 +452,8 @@ int main(int argc, const char** argv)
         return 0;
     }
     if (adaptive) {  // the frame, the spp map and the denoised frame from one adaptive call
-        if (render_adaptive_frame(tris, n, box, &cam, w, h, spp, device, &ad, image, spp_map, denoised)) {
+        if (render_adaptive_frame(tris, n, box, &cam, w, h, spp, device, &ad, image, spp_map, denoised,
+                                  have_shrink ? &shrink : nullptr)) {
             printf("ERROR: %s\n", tmpt_last_error());
             return 1;
         }
@@ -438,7 +472,7 @@ int main(int argc, const char** argv)
         printf("ERROR: %s\n", tmpt_last_error());
         return 1;
     }
-    if (denoised && write_denoised(denoised, tris, n, box, &cam, w, h, spp, device)) {
+    if (denoised && write_denoised(denoised, tris, n, box, &cam, w, h, spp, device, have_shrink ? &shrink : nullptr)) {
         printf("ERROR: %s\n", tmpt_last_error());
         return 1;
     }

@@ -20,10 +20,20 @@
 // staged form: dn_staged() below.  The levels ping-pong two float4 planes of
 // the scene's workspace; the last one writes the caller's buffer and packs the
 // 8-bit pixels in the same pass.
+//
+// The noise-aware form (tmpt_denoise_moments; the header states it too) is the
+// same level kernel with the template flag VAR: beside c_L it carries v_L, the
+// variance of the pixel's mean luminance (k_dn_v0 forms v_0 from the moments),
+// and a keep plane, the detail each level removed that the noise estimate does
+// not explain.  STAGE 1 / 2 stage v_L with the tile (40 B per staged pixel,
+// 17.3 / 25.6 KB); the 3 x 3 prefilter of v_L reads the staged tile (halo >= 2)
+// or, STAGE 0, global memory.  The last level adds keep and packs.  The three
+// VAR = false instantiations are the code they were without the flag.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "tmpt_render.h"
 
@@ -38,6 +48,17 @@ struct DnArgs {
     int32_t W, H, stride, normal_exp;
     float sigma_depth, sigma_direct;
 };
+// the arguments of a VAR level: v_L, v_(L+1), the keep plane (not read at the
+// first level, not written at the last), shrink
+struct DnVarArgs : DnArgs {
+    const float* vin;
+    float* vout;
+    float4* keep;
+    float shrink;
+    int32_t first, last;
+};
+template <bool VAR>
+using DnArgsT = std::conditional_t<VAR, DnVarArgs, DnArgs>;
 
 __global__ void __launch_bounds__(256) k_dn_guides(const float4* __restrict__ aov, int64_t n, float spp,
                                                    float4* __restrict__ g0, float* __restrict__ g1)
@@ -58,6 +79,27 @@ __global__ void __launch_bounds__(256) k_dn_guides(const float4* __restrict__ ao
     g1[p] = b.x;
 }
 
+// v_0 of the noise-aware filter, per pixel, from the frame's moments
+// {mu1, mu2, mean 1/n, history length}: in the header's order.
+__global__ void __launch_bounds__(256) k_dn_v0(const float4* __restrict__ mom, int64_t n, float* __restrict__ v0)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const float4 m = mom[p];
+    const float ne = m.w / m.z;
+    const float sq = m.x * m.x;
+    v0[p] = fmaxf(0.0f, m.y - sq) / fmaxf(ne - 1.0f, 1.0f);
+}
+
+// the staged v_L of a VAR level (a function's own LDS array: the VAR = false
+// instantiations never name it)
+template <int N>
+__device__ __forceinline__ float* dn_lds_v()
+{
+    __shared__ float s_v[N];
+    return s_v;
+}
+
 // the pixel a lane filters
 struct DnCentre {
     f3 nh;
@@ -66,9 +108,10 @@ struct DnCentre {
 };
 
 // One tap other than the centre, already known to lie in the frame with
-// cov_q == cov_p: its weight, in the header's order, and the two sums.
-__device__ __forceinline__ void dn_tap(const DnArgs& a, const DnCentre& p, float hw, float dist, float4 cq, float4 gq,
-                                       float dlq, f3& csum, float& wsum)
+// cov_q == cov_p: its weight, in the header's order, and the two sums.  Returns
+// the weight.
+__device__ __forceinline__ float dn_tap(const DnArgs& a, const DnCentre& p, float hw, float dist, float4 cq, float4 gq,
+                                        float dlq, f3& csum, float& wsum)
 {
     float w = hw;
     if (p.cov) {
@@ -83,21 +126,24 @@ __device__ __forceinline__ void dn_tap(const DnArgs& a, const DnCentre& p, float
     }
     csum = csum + mk(cq.x * w, cq.y * w, cq.z * w);
     wsum = wsum + w;
+    return w;
 }
 
 // STAGE: 0 = global loads at the run-time stride a.stride; 1, 2 = that stride,
 // the block's tile + halo staged in LDS.  out8 (last level only, may be null):
-// the packed pixels.
-template <int STAGE>
+// the packed pixels.  VAR: the noise-aware form (a: DnVarArgs).
+template <int STAGE, bool VAR = false>
 __global__ void __launch_bounds__(256) k_dn_level(const float4* __restrict__ in, const float4* __restrict__ g0,
                                                   const float* __restrict__ g1, float4* __restrict__ out,
-                                                  uint32_t* __restrict__ out8, DnArgs a)
+                                                  uint32_t* __restrict__ out8, DnArgsT<VAR> a)
 {
     constexpr int HALO = 2 * STAGE;
     constexpr int TW = kDnTX + 2 * HALO, TH = kDnTY + 2 * HALO;
     __shared__ float4 s_col[STAGE ? TW * TH : 1];
     __shared__ float4 s_g0[STAGE ? TW * TH : 1];
     __shared__ float s_g1[STAGE ? TW * TH : 1];
+    float* s_v = nullptr;
+    if constexpr (VAR && STAGE != 0) s_v = dn_lds_v<TW * TH>();
     const int tx = (int)threadIdx.x % kDnTX, ty = (int)threadIdx.x / kDnTX;
     const int x0 = (int)blockIdx.x * kDnTX, y0 = (int)blockIdx.y * kDnTY;
     const int x = x0 + tx, y = y0 + ty;
@@ -111,6 +157,7 @@ __global__ void __launch_bounds__(256) k_dn_level(const float4* __restrict__ in,
                 s_col[e] = in[q];
                 s_g0[e] = g0[q];
                 s_g1[e] = g1[q];
+                if constexpr (VAR) s_v[e] = a.vin[q];
             } else {
                 s_g0[e] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kNoPixel));
             }
@@ -130,6 +177,7 @@ __global__ void __launch_bounds__(256) k_dn_level(const float4* __restrict__ in,
     const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     f3 csum = mk(0.0f, 0.0f, 0.0f);
     float wsum = 0.0f;
+    float vsum = 0.0f;  // VAR only
 #pragma unroll
     for (int j = -2; j <= 2; ++j) {
 #pragma unroll
@@ -138,6 +186,7 @@ __global__ void __launch_bounds__(256) k_dn_level(const float4* __restrict__ in,
                 const float w = h[2] * h[2];
                 csum = csum + mk(cp.x * w, cp.y * w, cp.z * w);
                 wsum = wsum + w;
+                if constexpr (VAR) vsum = vsum + (STAGE ? s_v[lc] : a.vin[pi]) * (w * w);
                 continue;
             }
             const float hw = h[i + 2] * h[j + 2];
@@ -147,20 +196,69 @@ __global__ void __launch_bounds__(256) k_dn_level(const float4* __restrict__ in,
                 const float4 gq = s_g0[e];
                 const uint32_t zw = __float_as_uint(gq.w);
                 if (zw == kNoPixel || (zw != kNoCov) != p.cov) continue;
-                dn_tap(a, p, hw, dist, s_col[e], gq, s_g1[e], csum, wsum);
+                const float w = dn_tap(a, p, hw, dist, s_col[e], gq, s_g1[e], csum, wsum);
+                if constexpr (VAR) vsum = vsum + s_v[e] * (w * w);
             } else {
                 const int qx = x + s * i, qy = y + s * j;
                 if (qx < 0 || qx >= a.W || qy < 0 || qy >= a.H) continue;
                 const int64_t q = (int64_t)qy * a.W + qx;
                 const float4 gq = g0[q];
                 if ((__float_as_uint(gq.w) != kNoCov) != p.cov) continue;
-                dn_tap(a, p, hw, dist, in[q], gq, g1[q], csum, wsum);
+                const float w = dn_tap(a, p, hw, dist, in[q], gq, g1[q], csum, wsum);
+                if constexpr (VAR) vsum = vsum + a.vin[q] * (w * w);
             }
         }
     }
     const f3 o = mk(csum.x / wsum, csum.y / wsum, csum.z / wsum);
-    out[pi] = make_float4(o.x, o.y, o.z, cp.w);
-    if (out8) out8[pi] = pack_pixel(o, 1.0f);
+    if constexpr (VAR) {
+        a.vout[pi] = vsum / (wsum * wsum);
+        // the 3 x 3 Gaussian of v_L, distance 1 at every level; the centre always counts
+        const float k3[3] = {0.25f, 0.5f, 0.25f};
+        float gsum = 0.0f, ksum = 0.0f;
+#pragma unroll
+        for (int j = -1; j <= 1; ++j) {
+#pragma unroll
+            for (int i = -1; i <= 1; ++i) {
+                float vq;
+                if (STAGE) {
+                    const int e = lc + j * TW + i;
+                    const uint32_t zw = __float_as_uint(s_g0[e].w);
+                    if (zw == kNoPixel || (zw != kNoCov) != p.cov) continue;
+                    vq = s_v[e];
+                } else {
+                    const int qx = x + i, qy = y + j;
+                    if (qx < 0 || qx >= a.W || qy < 0 || qy >= a.H) continue;
+                    const int64_t q = (int64_t)qy * a.W + qx;
+                    if ((__float_as_uint(g0[q].w) != kNoCov) != p.cov) continue;
+                    vq = a.vin[q];
+                }
+                const float k = k3[i + 1] * k3[j + 1];
+                gsum = gsum + vq * k;
+                ksum = ksum + k;
+            }
+        }
+        const float g = gsum / ksum;
+        const f3 d = mk(cp.x - o.x, cp.y - o.y, cp.z - o.z);  // the detail this level removed
+        const float dy = (0.2126f * d.x + 0.7152f * d.y) + 0.0722f * d.z;
+        const float en = dy * dy, nn = a.shrink * g;
+        const float gain = en > nn ? (en - nn) / en : 0.0f;  // a NaN compares false
+        float4 kp = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!a.first) kp = a.keep[pi];
+        kp.x = kp.x + d.x * gain;
+        kp.y = kp.y + d.y * gain;
+        kp.z = kp.z + d.z * gain;
+        if (a.last) {
+            const f3 r = mk(o.x + kp.x, o.y + kp.y, o.z + kp.z);
+            out[pi] = make_float4(r.x, r.y, r.z, cp.w);
+            if (out8) out8[pi] = pack_pixel(r, 1.0f);
+        } else {
+            a.keep[pi] = kp;
+            out[pi] = make_float4(o.x, o.y, o.z, cp.w);
+        }
+    } else {
+        out[pi] = make_float4(o.x, o.y, o.z, cp.w);
+        if (out8) out8[pi] = pack_pixel(o, 1.0f);
+    }
 }
 
 // Which strides read the staged LDS tile (option denoise_lds = -1): 1 and 2.
@@ -178,27 +276,38 @@ static bool dn_staged(const Options& o, int stride)
     return true;
 }
 
-int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt_aov_pixel* d_aov, float4* d_out32,
-            uint32_t* d_out8)
+// Both filters' host side.  VAR: tmpt_denoise_moments (d_mom, shrink); the
+// workspace then holds two float planes (v_L, ping-pong) and the keep plane too.
+template <bool VAR>
+static int dn_run(Scene& s, const char* what, const tmpt_denoise_desc* d, float shrink, const float4* d_in,
+                  const tmpt_aov_pixel* d_aov, const float4* d_mom, float4* d_out32, uint32_t* d_out8)
 {
     const int64_t n = (int64_t)d->width * d->height;
-    // workspace: two colour planes, then the guide planes
-    const size_t plane = sizeof(float4) * (size_t)n;
-    if (ensure_ws(s, 3 * plane + sizeof(float) * (size_t)n)) return -1;
+    // workspace: two colour planes, then the guide planes (VAR: keep, then two variance planes)
+    const size_t plane = sizeof(float4) * (size_t)n, fplane = sizeof(float) * (size_t)n;
+    if (ensure_ws(s, VAR ? 4 * plane + 3 * fplane : 3 * plane + fplane)) return -1;
     float4* pl[2] = {s.ws.as<float4>(), reinterpret_cast<float4*>(s.ws.as<char>() + plane)};
     float4* g0 = reinterpret_cast<float4*>(s.ws.as<char>() + 2 * plane);
     float* g1 = reinterpret_cast<float*>(s.ws.as<char>() + 3 * plane);
+    float4* keep = reinterpret_cast<float4*>(s.ws.as<char>() + 3 * plane + fplane);  // VAR only, as vp
+    float* vp[2] = {reinterpret_cast<float*>(s.ws.as<char>() + 4 * plane + fplane),
+                    reinterpret_cast<float*>(s.ws.as<char>() + 4 * plane + 2 * fplane)};
     tmpt_render_desc wd{};
     wd.flags = d->flags;
     wd.wait_stream = d->wait_stream;
-    if (int rc = wait_caller_stream(s, &wd, "tmpt_denoise")) return rc;
+    if (int rc = wait_caller_stream(s, &wd, what)) return rc;
     if (ensure_counters(s)) return -1;  // the scene's timing events
     hipEvent_t e0 = s.render_ev[0], e1 = s.render_ev[1];
     TMPT_HIP(hipEventRecord(e0, s.stream));
     k_dn_guides<<<(unsigned)((n + 255) / 256), 256, 0, s.stream>>>(reinterpret_cast<const float4*>(d_aov), n,
                                                                    (float)d->spp, g0, g1);
     TMPT_HIP(hipGetLastError());
-    DnArgs a{d->width, d->height, 1, d->normal_exp, d->sigma_depth, d->sigma_direct};
+    if (VAR) {
+        k_dn_v0<<<(unsigned)((n + 255) / 256), 256, 0, s.stream>>>(d_mom, n, vp[1]);
+        TMPT_HIP(hipGetLastError());
+    }
+    DnArgsT<VAR> a{};
+    static_cast<DnArgs&>(a) = DnArgs{d->width, d->height, 1, d->normal_exp, d->sigma_depth, d->sigma_direct};
     const dim3 grid((unsigned)((d->width + kDnTX - 1) / kDnTX), (unsigned)((d->height + kDnTY - 1) / kDnTY));
     const float4* src = d_in;
     for (int L = 0; L < d->levels; ++L) {
@@ -209,12 +318,20 @@ int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt
         if (last && d_out32 && (const float4*)d_out32 != src) dst = d_out32;
         uint32_t* o8 = last ? d_out8 : nullptr;
         a.stride = 1 << L;
+        if constexpr (VAR) {
+            a.vin = vp[(L + 1) & 1];
+            a.vout = vp[L & 1];
+            a.keep = keep;
+            a.shrink = shrink;
+            a.first = L == 0;
+            a.last = last;
+        }
         if (a.stride == 1 && dn_staged(s.opt, 1))
-            k_dn_level<1><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
+            k_dn_level<1, VAR><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
         else if (a.stride == 2 && dn_staged(s.opt, 2))
-            k_dn_level<2><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
+            k_dn_level<2, VAR><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
         else
-            k_dn_level<0><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
+            k_dn_level<0, VAR><<<grid, 256, 0, s.stream>>>(src, g0, g1, dst, o8, a);
         TMPT_HIP(hipGetLastError());
         if (last && d_out32 && dst != d_out32)
             TMPT_HIP(hipMemcpyAsync(d_out32, dst, plane, hipMemcpyDeviceToDevice, s.stream));
@@ -223,13 +340,25 @@ int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt
     (void)hipEventRecord(e1, s.stream);
     const hipError_t se = hipStreamSynchronize(s.stream);
     if (se != hipSuccess) {
-        set_error(std::string("tmpt_denoise: ") + hipGetErrorString(se));
+        set_error(std::string(what) + ": " + hipGetErrorString(se));
         return -1;
     }
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     s.render_ms = ms;
     return 0;
+}
+
+int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt_aov_pixel* d_aov, float4* d_out32,
+            uint32_t* d_out8)
+{
+    return dn_run<false>(s, "tmpt_denoise", d, 0.0f, d_in, d_aov, nullptr, d_out32, d_out8);
+}
+
+int denoise_moments(Scene& s, const tmpt_denoise_desc* d, float shrink, const float4* d_in, const tmpt_aov_pixel* d_aov,
+                    const float4* d_mom, float4* d_out32, uint32_t* d_out8)
+{
+    return dn_run<true>(s, "tmpt_denoise_moments", d, shrink, d_in, d_aov, d_mom, d_out32, d_out8);
 }
 
 }  // namespace tmpt

@@ -169,15 +169,20 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
 
 // tmpt_adaptive.hip: adaptive sampling (tmpt_render_adaptive) of one shard; ad
 // holds the resolved spp_min, spp_step, threshold and radius (checked by the caller),
-// the three tiles are device pointers or null
+// the three tiles are device pointers or null; d_mom: the moments tile of
+// tmpt_render_moments (`what` then names that call in errors), or null
 int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
-                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count);
+                    float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count,
+                    float4* d_mom = nullptr, const char* what = "tmpt_render_adaptive");
 
 // tmpt_denoise.hip: the a-trous filter (tmpt_denoise) over a whole frame, every
 // pointer on the device; d (checked by the caller) holds the resolved levels,
 // normal_exp and sigmas.  d_out32 or d_out8 may be null; d_out32 may be d_in.
 int denoise(Scene& s, const tmpt_denoise_desc* d, const float4* d_in, const tmpt_aov_pixel* d_aov, float4* d_out32,
             uint32_t* d_out8);
+// the noise-aware form (tmpt_denoise_moments): d_mom the frame's moments, shrink resolved and > 0
+int denoise_moments(Scene& s, const tmpt_denoise_desc* d, float shrink, const float4* d_in, const tmpt_aov_pixel* d_aov,
+                    const float4* d_mom, float4* d_out32, uint32_t* d_out8);
 
 // tmpt_motion.hip: the motion pass of one shard (tmpt_render_motion), d_out on
 // the device; d_prev the previous pose on the device (9 floats per triangle) or
