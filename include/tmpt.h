@@ -60,7 +60,9 @@ extern "C" {
                               still 9, additive: temporal accumulation -- the render option sample_base,
                               tmpt_render_motion with tmpt_motion_pixel (the motion pass) and
                               tmpt_temporal with tmpt_temporal_desc (the reprojected history) -- no
-                              struct above changed */
+                              struct above changed;
+                              still 9, additive: tmpt_temporal_clip with tmpt_temporal_clip_desc (the
+                              reprojected history clipped to the current frame's local statistics) */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -874,6 +876,90 @@ typedef struct {
 int tmpt_temporal(tmpt_scene* scene, const tmpt_temporal_desc* desc, const float* rgba32f_cur,
                   const tmpt_motion_pixel* motion, const tmpt_motion_pixel* prev_motion,
                   const float* rgba32f_history, float* rgba32f_out, uint8_t* rgba8_out);
+
+typedef struct {
+    int32_t width, height;
+    int32_t flags;          /* TMPT_FLAG_OUT_DEVICE (every pointer a device pointer), TMPT_FLAG_WAIT_STREAM */
+    float   n_max;          /* cap on the history length, >= 1; 0 = default (3) */
+    float   sigma_depth;    /* relative depth tolerance, > 0; 0 = default (0.05, tmpt_temporal's) */
+    float   gamma;          /* box half-width in window standard deviations, > 0; 0 = default (0.5) */
+    int32_t radius;         /* window radius 1..3; 0 = default (1) */
+    int32_t reserved0;
+    uint64_t wait_stream;
+    int32_t reserved[4];
+} tmpt_temporal_clip_desc;
+/* tmpt_temporal with history clipping (variance clipping): the reprojected
+ * history value is pulled into the box mean +- gamma * sigma of the current
+ * frame's neighbourhood before it is blended, and a history that had to be pulled
+ * far loses its length.  The window's sigma contains the frame's noise, so the box
+ * is wide where the frame is noisy and tight where it is not.  Frames, rows, the
+ * motion records and a frame's .w are tmpt_temporal's.
+ *   rgba32f_stat  the frame the window statistics are taken from (for instance
+ *                 rgba32f_cur through tmpt_denoise); NULL = rgba32f_cur
+ *   aux_cur, aux_history, aux_out  all three or none: a second frame (for instance
+ *                 the moments frame of tmpt_render_moments) accumulated over the
+ *                 same taps with the same blend factor, and not clipped, so that
+ *                 it stays consistent with the clipped colour frame and
+ *                 tmpt_denoise_moments can follow
+ * rgba32f_out (may be NULL) and rgba8_out (may be NULL; at least one of the two is
+ * given) as in tmpt_temporal, with one difference: rgba32f_out and aux_out must
+ * overlap none of rgba32f_history, aux_history, rgba32f_cur and rgba32f_stat --
+ * here the current frame's neighbours are read too, across blocks, so out may NOT
+ * be cur.  (aux_out may be aux_cur: that frame is read at the pixel itself only.)
+ *
+ * The arithmetic is the contract, under the rules stated above tmpt_motion_pixel
+ * (tests/temporal_clip_restate.py restates it in numpy).  fmaxf / fminf return the
+ * other operand for a NaN; nothing is screened.  Per pixel p = (x, y), with
+ * m = motion[p], S = rgba32f_stat or, when NULL, rgba32f_cur, r = radius:
+ *   fetch:  the reset rule, the validity of m.px / m.py, fx .. ay, the four taps,
+ *           their skip rules, wgt, csum, nsum and wsum are tmpt_temporal's
+ *           statements above, word for word; with aux, on the taps that count,
+ *           asum.k = asum.k + aux_history_q.k * wgt  (k = x, y, z; asum = {0,0,0})
+ *   reset:  out_p = {cur_p.r, cur_p.g, cur_p.b, 1.0f}
+ *           aux_out_p = {aux_cur_p.x, aux_cur_p.y, aux_cur_p.z, 1.0f}
+ *   h.k = csum.k / wsum     nh = nsum / wsum     ha.k = asum.k / wsum
+ *   window: s1 = s2 = {0,0,0}  cnt = 0
+ *     for j = -r .. r (outer), i = -r .. r (inner): q = p + (i, j)
+ *         skipped: q outside the frame;
+ *                  (motion[q].flags & 1) != (m.flags & 1)   (coverage, as tmpt_denoise's cov_q != cov_p)
+ *         s1.k = s1.k + S_q.k     s2.k = s2.k + S_q.k * S_q.k     cnt = cnt + 1.0f
+ *     (the centre always counts; the sums run over the window in exactly this
+ *     order, rows outer, not separably)
+ *   box:    mu.k = s1.k / cnt
+ *           var.k = fmaxf(0.0f, s2.k / cnt - mu.k * mu.k)     sd.k = sqrtf(var.k)
+ *           g.k = gamma * sd.k     lo.k = mu.k - g.k     hi.k = mu.k + g.k
+ *   clip:   hc.k = fminf(fmaxf(h.k, lo.k), hi.k)
+ *           e    = fmaxf(fmaxf(fabsf(h.r - hc.r), fabsf(h.g - hc.g)), fabsf(h.b - hc.b))
+ *           span = fmaxf(fmaxf(g.r, g.g), g.b)
+ *   length: nh' = e > 0.0f ? nh * (span / (span + e)) : nh      (a NaN compares false)
+ *   blend:  n = fminf(nh' + 1.0f, n_max)     a = 1.0f / n
+ *           out_p.k = hc.k + (cur_p.k - hc.k) * a          out_p.w = n
+ *           aux_out_p.k = ha.k + (aux_cur_p.k - ha.k) * a   aux_out_p.w = n
+ * rgba8_out packs out as every render packs its pixels.  What follows:
+ *   - where no history value leaves its box -- with gamma = 3e38f that is every
+ *     pixel whose window has sd.k > 0 for all k (3e38f * sd.k is then far beyond
+ *     any radiance, or +inf) -- hc = h, e = 0, and out is tmpt_temporal's output
+ *     bit for bit at the same n_max and sigma_depth;
+ *   - a window that is the centre alone (a 1 x 1 frame, an isolated covered pixel)
+ *     has mu = S_p and sd = 0, so hc = S_p whatever gamma is (S_p not a NaN), and
+ *     a history that differed from S_p restarts: span = 0, nh' = 0, n = 1.
+ * Defaults n_max = 3, gamma = 0.5, radius = 1: the grid point of
+ * tools/temporal_clip_sweep.py (profiles/temporal_clip_sweep.log, DESIGN.md
+ * "History clipping") whose worst sequence is best; sigma_depth as tmpt_temporal.
+ * The scene lends its device, stream and error channel; the progressive state is
+ * left alone.  Host pointers are staged through one buffer the scene keeps (grown,
+ * never shrunk).  -22, in tmpt_temporal's order, for: a null desc; a size outside
+ * tmpt_render's limits; a missing pointer (cur, motion, prev_motion, history, an
+ * aux triple given in part, or both outputs); n_max < 1 (after the default) or not
+ * finite; a negative or non-finite sigma_depth; a negative or non-finite gamma; a
+ * radius outside 0..3; other flags; a misaligned device pointer (16 bytes;
+ * rgba8_out: 4); an output overlapping a frame named above; a null scene.
+ * tmpt_get_stats afterwards: render_ms is the kernel's time on the device; the
+ * other fields keep the last render's.  Additive, the ABI version stays. */
+int tmpt_temporal_clip(tmpt_scene* scene, const tmpt_temporal_clip_desc* desc, const float* rgba32f_cur,
+                       const float* rgba32f_stat, const tmpt_motion_pixel* motion,
+                       const tmpt_motion_pixel* prev_motion, const float* rgba32f_history, const float* aux_cur,
+                       const float* aux_history, float* aux_out, float* rgba32f_out, uint8_t* rgba8_out);
 
 /* main.cpp:312-331 over several devices in ONE process (SURVEY.md §8e's
  * single-process form): a scene per entry of devices[] (created here, freed on

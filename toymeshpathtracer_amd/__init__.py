@@ -122,6 +122,13 @@ class _TemporalDesc(ctypes.Structure):
                 ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
+class _TemporalClipDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("n_max", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("gamma", ctypes.c_float),
+                ("radius", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("wait_stream", ctypes.c_uint64),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
 class _AdaptiveDesc(ctypes.Structure):
     _fields_ = [("spp_min", ctypes.c_int32), ("spp_step", ctypes.c_int32), ("threshold", ctypes.c_float),
                 ("radius", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
@@ -227,7 +234,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
            "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal", "tmpt_render_moments",
-           "tmpt_denoise_moments")
+           "tmpt_denoise_moments", "tmpt_temporal_clip")
 
 
 def _check(rc: int, what: str) -> None:
@@ -1014,6 +1021,76 @@ class Scene:
                   history.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
                   img.ctypes.data_as(ctypes.c_void_p)), "temporal")
         return res, img
+
+    def temporal_clip(self, radiance, motion, prev_motion, history, gamma: float = 0.0, radius: int = 0,
+                      n_max: float = 0.0, sigma_depth: float = 0.0, stat=None, aux=None, aux_history=None, out=None,
+                      width: Optional[int] = None, height: Optional[int] = None, wait_stream="current"):
+        """:meth:`temporal` with history clipping (tmpt_temporal_clip; include/tmpt.h
+        states its arithmetic): the reprojected history is pulled into the box
+        mean +- ``gamma`` standard deviations of the (2 ``radius`` + 1)^2 window of
+        ``stat`` (float32[h, w, 4]; ``None``: ``radiance`` itself) around the
+        pixel, and loses length by how far it was pulled.  ``aux`` and
+        ``aux_history`` (both or neither, float32[h, w, 4]: a moments frame of
+        :meth:`trace_moments` and its accumulation) ride through the same taps and
+        blend factor, unclipped.  Returns (float32[h, w, 4], rgba8[h, w, 4], aux
+        frame or None).  0 selects the defaults.  ``out``: a float32 array
+        [h, w, 4] that takes the frame; unlike :meth:`temporal` it may be neither
+        ``radiance`` nor ``stat`` nor a history.
+        Device form, as :meth:`temporal`: every frame a device pointer (int,
+        16-byte aligned; ``stat`` may stay ``None``), ``width`` and ``height`` give
+        the size and ``out`` = (float frame pointer or None, rgba8 pointer or
+        None, aux frame pointer or None: given exactly when ``aux`` is); returns
+        (None, None, None)."""
+        # bound on first use, as tmpt_render_adaptive is
+        fn = _sig("tmpt_temporal_clip", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_TemporalClipDesc)]
+                  + [ctypes.c_void_p] * 10)
+        if (aux is None) != (aux_history is None):
+            raise ValueError("temporal_clip: aux and aux_history go together")
+        dev = isinstance(radiance, int)
+        d = _TemporalClipDesc()
+        if dev:
+            if width is None or height is None or out is None:
+                raise ValueError("temporal_clip: device pointers need width, height and out")
+            h, w = int(height), int(width)
+        else:
+            radiance = np.ascontiguousarray(radiance, np.float32)
+            history = np.ascontiguousarray(history, np.float32)
+            motion = np.ascontiguousarray(motion, MOTION_DTYPE)
+            prev_motion = np.ascontiguousarray(prev_motion, MOTION_DTYPE)
+            h, w = radiance.shape[:2]
+            frames = [radiance, history]
+            if stat is not None:
+                stat = np.ascontiguousarray(stat, np.float32)
+                frames.append(stat)
+            if aux is not None:
+                aux = np.ascontiguousarray(aux, np.float32)
+                aux_history = np.ascontiguousarray(aux_history, np.float32)
+                frames += [aux, aux_history]
+            if (any(f.shape != (h, w, 4) for f in frames) or motion.shape != (h, w) or prev_motion.shape != (h, w)):
+                raise ValueError("temporal_clip: radiance, history, stat, aux and aux_history [h, w, 4], motion and "
+                                 "prev_motion [h, w] of one whole frame")
+        d.width, d.height, d.n_max, d.sigma_depth, d.gamma, d.radius = w, h, n_max, sigma_depth, gamma, radius
+        ptr = lambda p: None if p is None else ctypes.c_void_p(int(p))
+        if dev:
+            d.flags = FLAG_OUT_DEVICE
+            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+            if ws is not None:
+                d.flags |= FLAG_WAIT_STREAM
+                d.wait_stream = int(ws)
+            f32, u8, ao = out
+            _check(fn(self._h, ctypes.byref(d), ptr(radiance), ptr(stat), ptr(motion), ptr(prev_motion), ptr(history),
+                      ptr(aux), ptr(aux_history), ptr(ao), ptr(f32), ptr(u8)), "temporal_clip")
+            return None, None, None
+        res = np.zeros((h, w, 4), np.float32) if out is None else out
+        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+                and res.flags.c_contiguous):
+            raise ValueError("temporal_clip: out must be a contiguous float32 array [h, w, 4]")
+        img = np.zeros((h, w, 4), np.uint8)
+        aux_res = None if aux is None else np.zeros((h, w, 4), np.float32)
+        host = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+        _check(fn(self._h, ctypes.byref(d), host(radiance), host(stat), host(motion), host(prev_motion), host(history),
+                  host(aux), host(aux_history), host(aux_res), host(res), host(img)), "temporal_clip")
+        return res, img, aux_res
 
     def camera_rays(self, camera: Camera, width: int, height: int, spp: int, spp_begin: int = 0,
                     spp_count: int = 0, band_rows: int = 0, shard: int = 0, num_shards: int = 1) -> np.ndarray:

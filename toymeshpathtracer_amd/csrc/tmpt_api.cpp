@@ -1191,6 +1191,105 @@ int tmpt_temporal(tmpt_scene* h, const tmpt_temporal_desc* d, const float* rgba3
     TMPT_GUARD_END
 }
 
+// tmpt_temporal_clip's defaults: the grid point tools/temporal_clip_sweep.py's rule
+// chose (profiles/temporal_clip_sweep.log, DESIGN.md section 4, "History clipping")
+constexpr float kClipNMax = 3.0f, kClipGamma = 0.5f;
+constexpr int32_t kClipRadius = 1;
+
+int tmpt_temporal_clip(tmpt_scene* h, const tmpt_temporal_clip_desc* d, const float* rgba32f_cur,
+                       const float* rgba32f_stat, const tmpt_motion_pixel* motion, const tmpt_motion_pixel* prev_motion,
+                       const float* rgba32f_history, const float* aux_cur, const float* aux_history, float* aux_out,
+                       float* rgba32f_out, uint8_t* rgba8_out)
+{
+    TMPT_GUARD_BEGIN
+    const char* const fn = "tmpt_temporal_clip: ";
+    auto no = [&](const char* what) { return bad((std::string(fn) + what).c_str()); };
+    // tmpt_temporal's checks in its order, the new ones where the header puts them
+    if (!d) return no("null descriptor");
+    if (d->width < 1 || d->width > 10000) return no("invalid width");
+    if (d->height < 1 || d->height > 10000) return no("invalid height");
+    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return no("null argument");
+    const bool aux = aux_cur || aux_history || aux_out;
+    if (aux && (!aux_cur || !aux_history || !aux_out))
+        return no("null argument (aux_cur, aux_history and aux_out: all three or none)");
+    if (!rgba32f_out && !rgba8_out) return no("no output (rgba32f_out and rgba8_out are both null)");
+    tmpt_temporal_clip_desc r = *d;  // the defaults, in one place
+    if (r.n_max == 0.0f) r.n_max = kClipNMax;
+    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
+    if (r.gamma == 0.0f) r.gamma = kClipGamma;
+    if (r.radius == 0) r.radius = kClipRadius;
+    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f)) return no("n_max must be finite and at least 1 (0 = default)");
+    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
+        return no("sigma_depth must be finite and not negative (0 = default)");
+    if (!(r.gamma >= 0.0f) || !(r.gamma <= 3.0e38f)) return no("gamma must be finite and not negative (0 = default)");
+    if (r.radius < 1 || r.radius > 3) return no("radius must be 1, 2 or 3 (0 = default)");
+    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
+    const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (dev && (((at(rgba32f_cur) | at(rgba32f_stat) | at(motion) | at(prev_motion) | at(rgba32f_history) | at(aux_cur) |
+                  at(aux_history) | at(aux_out) | at(rgba32f_out)) & 15u) != 0 || (at(rgba8_out) & 3u) != 0))
+        return no("device pointers must be 16-byte aligned (rgba8_out: 4)");
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4);
+    {
+        const struct { const void* p; const char* name; } outs[] = {{rgba32f_out, "rgba32f_out"}, {aux_out, "aux_out"}},
+            ins[] = {{rgba32f_history, "rgba32f_history"}, {aux_history, "aux_history"}, {rgba32f_cur, "rgba32f_cur"},
+                     {rgba32f_stat, "rgba32f_stat"}};
+        for (const auto& o : outs)
+            for (const auto& i : ins)
+                if (o.p && i.p && at(o.p) < at(i.p) + fb && at(i.p) < at(o.p) + fb)
+                    return no((std::string(o.name) + " overlaps " + i.name + " (its neighbours are read)").c_str());
+    }
+    if (!h) return no("null scene");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const float4* d_cur = reinterpret_cast<const float4*>(rgba32f_cur);
+    const float4* d_stat = reinterpret_cast<const float4*>(rgba32f_stat);
+    const float4* d_hist = reinterpret_cast<const float4*>(rgba32f_history);
+    const float4* d_ac = reinterpret_cast<const float4*>(aux_cur);
+    const float4* d_ah = reinterpret_cast<const float4*>(aux_history);
+    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
+    float4* d_ao = reinterpret_cast<float4*>(aux_out);
+    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
+    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
+    if (!dev) {  // host pointers: staged in the scene's kept buffer, frame after frame
+        const size_t mb = n * sizeof(tmpt_motion_pixel);
+        const size_t total = fb * (3 + (rgba32f_stat ? 1 : 0) + (aux ? 3 : 0)) + 2 * mb + n * 4;
+        TMPT_HIP(hipStreamSynchronize(s.stream));
+        if (!s.clip_stage.reserve(total)) return no("out of device memory");
+        char* at_dev = s.clip_stage.as<char>();
+        auto take = [&](size_t bytes) { char* p = at_dev; at_dev += bytes; return p; };
+        auto up = [&](const void* src, size_t bytes) -> char* {
+            char* p = take(bytes);
+            return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? p : nullptr;
+        };
+        d_cur = reinterpret_cast<const float4*>(up(rgba32f_cur, fb));
+        d_hist = reinterpret_cast<const float4*>(up(rgba32f_history, fb));
+        d_m = reinterpret_cast<const tmpt_motion_pixel*>(up(motion, mb));
+        d_pm = reinterpret_cast<const tmpt_motion_pixel*>(up(prev_motion, mb));
+        bool ok = d_cur && d_hist && d_m && d_pm;
+        if (rgba32f_stat) ok = (d_stat = reinterpret_cast<const float4*>(up(rgba32f_stat, fb))) && ok;
+        if (aux) {
+            ok = (d_ac = reinterpret_cast<const float4*>(up(aux_cur, fb))) && ok;
+            ok = (d_ah = reinterpret_cast<const float4*>(up(aux_history, fb))) && ok;
+            d_ao = reinterpret_cast<float4*>(take(fb));
+        }
+        if (!ok) return (set_error(std::string(fn) + "upload failed"), -1);
+        d_o32 = rgba32f_out ? reinterpret_cast<float4*>(take(fb)) : nullptr;
+        d_o8 = rgba8_out ? reinterpret_cast<uint32_t*>(take(n * 4)) : nullptr;
+    }
+    if (!d_stat) d_stat = d_cur;
+    int rc = temporal_clip(s, &r, d_cur, d_stat, d_m, d_pm, d_hist, d_ac, d_ah, d_ao, d_o32, d_o8);
+    if (!rc && !dev) {
+        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (aux && hipMemcpy(aux_out, d_ao, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = (set_error(std::string(fn) + "readback failed"), -1);
+    }
+    return rc;
+    TMPT_GUARD_END
+}
+
 int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, const tmpt_camera* cam,
                       const tmpt_render_desc* desc, const int32_t* devices, int32_t ndevices, uint8_t* rgba_full,
                       uint64_t* ray_count, double* seconds)

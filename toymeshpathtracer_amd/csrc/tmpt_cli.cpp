@@ -2,7 +2,7 @@
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png [--shrink K]]
 //        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
-//        [--twist DEG,FRAMES [--rebuild] [--temporal]]
+//        [--twist DEG,FRAMES [--rebuild] [--temporal [--clip [GAMMA[,RADIUS[,NMAX]]]]]]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -36,6 +36,9 @@
 // the motion pass (tmpt_render_motion) against frame f-1's triangles and the same camera, and blends
 // (tmpt_temporal, its defaults) with the accumulation kept from frame f-1; frame 0's accumulation is
 // frame 0 itself.  The accumulated frames go to OUT_temporal_000.png, ... beside the plain ones.
+// --clip [GAMMA[,RADIUS[,NMAX]]] (with --temporal): the blend is tmpt_temporal_clip instead -- the history
+// clipped to GAMMA standard deviations of the frame's own (2 RADIUS + 1)^2 window, capped at NMAX (left out
+// or 0 = that call's defaults) -- into the same files.  Without --clip nothing changes.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -216,7 +219,8 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
 
 // --twist: see the head of this file.  tris: the n triangles of tmpt_load_obj (the last two are the floor).
 static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, const tmpt_render_desc* desc, int device,
-                        double degrees, int frames, bool rebuild, bool temporal, const char* out)
+                        double degrees, int frames, bool rebuild, bool temporal, const tmpt_temporal_clip_desc* clip,
+                        const char* out)
 {
     tmpt_scene* scene = nullptr;
     if (tmpt_scene_create(tris, n, device, &scene)) return 1;
@@ -224,7 +228,7 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
     std::vector<uint8_t> image((size_t)w * h * 4, 0);
     std::vector<float> cur((size_t)n * 9);
     // --temporal: the previous pose, this frame's radiance, the accumulation, both frames' motion records
-    std::vector<float> prev, rad, acc;
+    std::vector<float> prev, rad, acc, clipped;
     std::vector<tmpt_motion_pixel> mot, pmot;
     std::vector<uint8_t> timage;
     if (temporal) {
@@ -275,6 +279,14 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
             if (!rc && f == 0) {  // a history of length one
                 acc = rad;
                 timage = image;
+            } else if (!rc && clip) {  // (its output may not be the frame itself)
+                tmpt_temporal_clip_desc cd = *clip;
+                cd.width = w;
+                cd.height = h;
+                clipped.resize(rad.size());
+                rc = tmpt_temporal_clip(scene, &cd, rad.data(), nullptr, mot.data(), pmot.data(), acc.data(), nullptr,
+                                        nullptr, nullptr, clipped.data(), timage.data());
+                if (!rc) acc.swap(clipped);
             } else if (!rc) {
                 tmpt_temporal_desc td;
                 memset(&td, 0, sizeof(td));
@@ -309,7 +321,7 @@ int main(int argc, const char** argv)
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
                "[--denoise file.png [--shrink k]] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
-               "[--twist deg,frames [--rebuild] [--temporal]]\n"
+               "[--twist deg,frames [--rebuild] [--temporal [--clip [gamma[,radius[,nmax]]]]]]\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
                "any pixel within radius columns and rows of it\n"
                "  --shrink (with --denoise): the noise-aware filter (tmpt_denoise_moments) over the frame and its "
@@ -317,7 +329,9 @@ int main(int argc, const char** argv)
                "  --twist: frames of the mesh twisted about y by up to deg on one scene, each a tmpt_scene_update "
                "(a refit; --rebuild: a full build), to <out>_000.png ...\n"
                "  --temporal (with --twist, --seed sample): each frame draws its own samples (sample_base) and is "
-               "blended with the reprojected accumulation of the frames before it, to <out>_temporal_000.png ...\n");
+               "blended with the reprojected accumulation of the frames before it, to <out>_temporal_000.png ...\n"
+               "  --clip (with --temporal): the history is clipped to gamma standard deviations of the frame's own "
+               "(2 radius + 1)^2 window first (tmpt_temporal_clip; left out or 0 = its defaults)\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -332,7 +346,9 @@ int main(int argc, const char** argv)
     const char* aov = nullptr;
     const char* denoised = nullptr;
     const char* spp_map = nullptr;
-    bool adaptive = false, twist = false, rebuild = false, temporal = false, have_shrink = false;
+    bool adaptive = false, twist = false, rebuild = false, temporal = false, have_shrink = false, clip = false;
+    tmpt_temporal_clip_desc cd;
+    memset(&cd, 0, sizeof(cd));
     float shrink = 0.0f;
     double twist_deg = 0.0;
     int twist_frames = 0;
@@ -384,6 +400,14 @@ int main(int argc, const char** argv)
         }
         else if (!strcmp(argv[i], "--rebuild")) rebuild = true;
         else if (!strcmp(argv[i], "--temporal")) temporal = true;
+        else if (!strcmp(argv[i], "--clip")) {
+            clip = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0 &&
+                sscanf(argv[++i], "%f,%d,%f", &cd.gamma, &cd.radius, &cd.n_max) < 1) {
+                printf("ERROR: invalid --clip argument '%s' (GAMMA[,RADIUS[,NMAX]])\n", argv[i]);
+                return 1;
+            }
+        }
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -414,6 +438,7 @@ int main(int argc, const char** argv)
         printf("ERROR: --temporal needs --twist without --rebuild, --seed sample and the persistent engine\n");
         return 1;
     }
+    if (clip && !temporal) { printf("ERROR: --clip needs --temporal\n"); return 1; }
     if (temporal && (long long)(twist_frames - 1) * spp > 64512) {
         printf("ERROR: --temporal: (FRAMES - 1) * spp must not exceed 64512 (option sample_base)\n");
         return 1;
@@ -444,7 +469,7 @@ int main(int argc, const char** argv)
     float box[6];
     tmpt_octree_bounds(bmin, bmax, box);
     if (twist) {  // the frames of one scene handle, each written by render_twist
-        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, temporal, out)) {
+        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, temporal, clip ? &cd : nullptr, out)) {
             printf("ERROR: %s\n", tmpt_last_error());
             return 1;
         }

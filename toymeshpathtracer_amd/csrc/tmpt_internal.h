@@ -465,6 +465,7 @@ struct Scene {
     Event render_ev[2];          // first / last kernel of a render
     DeviceBuffer<> ws;           // render workspace, kept and grown on demand
     DeviceBuffer<float> motion_prev;  // tmpt_render_motion: a host prev_tris uploaded (kept, grown, never shrunk)
+    DeviceBuffer<> clip_stage;        // tmpt_temporal_clip: the host form's frames on the device (kept, grown)
     // progressive spp: per-pixel {colour sum xyz, rng} of the last pass (kept,
     // grown), and the shard it belongs to (width, height, spp, band_rows,
     // shard, num_shards, next sample)

@@ -17,6 +17,11 @@
 // k_temporal: one lane per pixel, a 32 x 8 block of pixels per 256-thread
 // block as the denoiser's levels; four history taps and four previous motion
 // records per pixel, global loads.
+//
+// k_temporal_clip<R> (tmpt_temporal_clip): k_temporal's fetch, then the history
+// clipped to the mean +- gamma * sigma of the (2R+1)^2 window of the statistics
+// frame, which the block stages in LDS with its halo; optionally a second (aux)
+// frame through the same taps and blend factor.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +33,7 @@ namespace tmpt {
 
 static_assert(sizeof(tmpt_motion_pixel) == 32, "motion record: two 16-byte stores");
 static_assert(sizeof(tmpt_temporal_desc) == 48, "tmpt_temporal_desc: 48 bytes");
+static_assert(sizeof(tmpt_temporal_clip_desc) == 56, "tmpt_temporal_clip_desc: 56 bytes");
 
 constexpr int kMotionTicket = 8;  // counters[]: the next 64-pixel unit no wave has taken
 
@@ -283,6 +289,158 @@ int temporal(Scene& s, const tmpt_temporal_desc* d, const float4* d_cur, const t
     const hipError_t se = hipStreamSynchronize(s.stream);
     if (se != hipSuccess) {
         set_error(std::string("tmpt_temporal: ") + hipGetErrorString(se));
+        return -1;
+    }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    s.render_ms = ms;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the clipped blend
+struct TemporalClipArgs {
+    int32_t W, H;
+    float n_max, sigma_depth, gamma;
+};
+
+// R: the window's radius.  The block's 32 x 8 pixels of the statistics frame and
+// a halo of R around them are staged in LDS, the coverage of each slot in .w:
+// 1.0f covered, 0.0f not, -1.0f outside the frame (no load is issued there), so
+// that "skipped" is one comparison with the pixel's own coverage.  Every lane of
+// the block stages and takes the barrier, the ones outside the frame too.
+template <int R>
+__global__ void __launch_bounds__(256)
+    k_temporal_clip(const float4* cur, const float4* stat, const float4* __restrict__ motion,
+                    const float4* __restrict__ pmotion, const float4* __restrict__ hist, const float4* aux_cur,
+                    const float4* __restrict__ aux_hist, float4* aux_out, float4* __restrict__ out,
+                    uint32_t* __restrict__ out8, TemporalClipArgs a)
+{
+    constexpr int TW = kTpTX + 2 * R, TH = kTpTY + 2 * R;
+    __shared__ float4 s_tile[TW * TH];
+    const int tx = (int)threadIdx.x % kTpTX, ty = (int)threadIdx.x / kTpTX;
+    const int bx0 = (int)blockIdx.x * kTpTX - R, by0 = (int)blockIdx.y * kTpTY - R;
+    const uint32_t* mwords = reinterpret_cast<const uint32_t*>(motion);
+    for (int s = (int)threadIdx.x; s < TW * TH; s += 256) {
+        const int sy = s / TW, sx = s - sy * TW;
+        const int gx = bx0 + sx, gy = by0 + sy;
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (gx >= 0 && gx < a.W && gy >= 0 && gy < a.H) {
+            const int64_t q = (int64_t)gy * a.W + gx;
+            const float4 sq = stat[q];
+            v = make_float4(sq.x, sq.y, sq.z, (mwords[8 * q + 7] & 1u) ? 1.0f : 0.0f);
+        }
+        s_tile[s] = v;
+    }
+    __syncthreads();
+    const int x = (int)blockIdx.x * kTpTX + tx;
+    const int y = (int)blockIdx.y * kTpTY + ty;
+    if (x >= a.W || y >= a.H) return;
+    const int64_t pi = (int64_t)y * a.W + x;
+    const float4 c = cur[pi];
+    const float4 m0 = motion[2 * pi], m1 = motion[2 * pi + 1];  // {px, py, depth, depth_prev}, {u, v, tri, flags}
+    float4 ac = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (aux_cur) ac = aux_cur[pi];  // (aux_out may be aux_cur: this lane alone reads and writes pixel pi)
+    f3 o = mk(c.x, c.y, c.z), ao = mk(ac.x, ac.y, ac.z);
+    float n = 1.0f;
+    const float mpx = m0.x, mpy = m0.y, dprev = m0.w;
+    const bool valid = (__float_as_uint(m1.w) & 2u) != 0 && mpx >= -1.0f && mpx < (float)a.W + 1.0f && mpy >= -1.0f &&
+                       mpy < (float)a.H + 1.0f;
+    if (valid) {
+        const float fx = mpx - 0.5f, fy = mpy - 0.5f;
+        const float x0 = floorf(fx), y0 = floorf(fy);
+        const float ax = fx - x0, ay = fy - y0;
+        const int ix = (int)x0, iy = (int)y0;
+        f3 csum = mk(0.0f, 0.0f, 0.0f), asum = mk(0.0f, 0.0f, 0.0f);
+        float nsum = 0.0f, wsum = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int qx = ix + i, qy = iy + j;
+                const float wgt = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                if (qx < 0 || qx >= a.W || qy < 0 || qy >= a.H) continue;
+                const int64_t q = (int64_t)qy * a.W + qx;
+                const float4 p0 = pmotion[2 * q], p1 = pmotion[2 * q + 1];
+                if (!(__float_as_uint(p1.w) & 1u)) continue;
+                if (fabsf(p0.z - dprev) > a.sigma_depth * dprev) continue;
+                const float4 hq = hist[q];
+                csum = csum + mk(hq.x * wgt, hq.y * wgt, hq.z * wgt);
+                nsum = nsum + hq.w * wgt;
+                wsum = wsum + wgt;
+                if (aux_hist) {
+                    const float4 aq = aux_hist[q];
+                    asum = asum + mk(aq.x * wgt, aq.y * wgt, aq.z * wgt);
+                }
+            }
+        }
+        if (wsum > 0.0f) {
+            const f3 h = mk(csum.x / wsum, csum.y / wsum, csum.z / wsum);
+            // the window, rows outer: the statement's order
+            const float covp = (__float_as_uint(m1.w) & 1u) ? 1.0f : 0.0f;
+            f3 s1 = mk(0.0f, 0.0f, 0.0f), s2 = mk(0.0f, 0.0f, 0.0f);
+            float cnt = 0.0f;
+#pragma unroll
+            for (int j = 0; j <= 2 * R; ++j) {
+#pragma unroll
+                for (int i = 0; i <= 2 * R; ++i) {
+                    const float4 t = s_tile[(ty + j) * TW + (tx + i)];
+                    if (t.w != covp) continue;
+                    s1 = s1 + mk(t.x, t.y, t.z);
+                    s2 = s2 + mk(t.x * t.x, t.y * t.y, t.z * t.z);
+                    cnt = cnt + 1.0f;
+                }
+            }
+            const f3 mu = mk(s1.x / cnt, s1.y / cnt, s1.z / cnt);
+            const f3 g = mk(a.gamma * sqrtf(fmaxf(0.0f, s2.x / cnt - mu.x * mu.x)),
+                            a.gamma * sqrtf(fmaxf(0.0f, s2.y / cnt - mu.y * mu.y)),
+                            a.gamma * sqrtf(fmaxf(0.0f, s2.z / cnt - mu.z * mu.z)));
+            const f3 hc = mk(fminf(fmaxf(h.x, mu.x - g.x), mu.x + g.x), fminf(fmaxf(h.y, mu.y - g.y), mu.y + g.y),
+                             fminf(fmaxf(h.z, mu.z - g.z), mu.z + g.z));
+            const float e = fmaxf(fmaxf(fabsf(h.x - hc.x), fabsf(h.y - hc.y)), fabsf(h.z - hc.z));
+            const float span = fmaxf(fmaxf(g.x, g.y), g.z);
+            float nh = nsum / wsum;
+            if (e > 0.0f) nh = nh * (span / (span + e));
+            n = fminf(nh + 1.0f, a.n_max);
+            const float al = 1.0f / n;
+            o = mk(hc.x + (c.x - hc.x) * al, hc.y + (c.y - hc.y) * al, hc.z + (c.z - hc.z) * al);
+            if (aux_cur) {
+                const f3 ha = mk(asum.x / wsum, asum.y / wsum, asum.z / wsum);
+                ao = mk(ha.x + (ac.x - ha.x) * al, ha.y + (ac.y - ha.y) * al, ha.z + (ac.z - ha.z) * al);
+            }
+        }
+    }
+    if (out) out[pi] = make_float4(o.x, o.y, o.z, n);
+    if (aux_out) aux_out[pi] = make_float4(ao.x, ao.y, ao.z, n);
+    if (out8) out8[pi] = pack_pixel(o, 1.0f);
+}
+
+// d (checked by the caller) holds the resolved n_max, sigma_depth, gamma and
+// radius (1..3); every pointer on the device; d_stat is a frame (d_cur where the
+// caller gave none); the three aux pointers all or none; d_out32 or d_out8 may be
+// null.  The outputs overlap no frame whose neighbours are read (the caller's check).
+int temporal_clip(Scene& s, const tmpt_temporal_clip_desc* d, const float4* d_cur, const float4* d_stat,
+                  const tmpt_motion_pixel* d_motion, const tmpt_motion_pixel* d_pmotion, const float4* d_hist,
+                  const float4* d_aux_cur, const float4* d_aux_hist, float4* d_aux_out, float4* d_out32,
+                  uint32_t* d_out8)
+{
+    tmpt_render_desc wd{};
+    wd.flags = d->flags;
+    wd.wait_stream = d->wait_stream;
+    if (int rc = wait_caller_stream(s, &wd, "tmpt_temporal_clip")) return rc;
+    if (ensure_counters(s)) return -1;  // the scene's timing events
+    hipEvent_t e0 = s.render_ev[0], e1 = s.render_ev[1];
+    TMPT_HIP(hipEventRecord(e0, s.stream));
+    const TemporalClipArgs a{d->width, d->height, d->n_max, d->sigma_depth, d->gamma};
+    const dim3 grid((unsigned)((d->width + kTpTX - 1) / kTpTX), (unsigned)((d->height + kTpTY - 1) / kTpTY));
+    auto fn = d->radius == 1 ? k_temporal_clip<1> : d->radius == 2 ? k_temporal_clip<2> : k_temporal_clip<3>;
+    fn<<<grid, 256, 0, s.stream>>>(d_cur, d_stat, reinterpret_cast<const float4*>(d_motion),
+                                   reinterpret_cast<const float4*>(d_pmotion), d_hist, d_aux_cur, d_aux_hist, d_aux_out,
+                                   d_out32, d_out8, a);
+    TMPT_HIP(hipGetLastError());
+    (void)hipEventRecord(e1, s.stream);
+    const hipError_t se = hipStreamSynchronize(s.stream);
+    if (se != hipSuccess) {
+        set_error(std::string("tmpt_temporal_clip: ") + hipGetErrorString(se));
         return -1;
     }
     float ms = 0;

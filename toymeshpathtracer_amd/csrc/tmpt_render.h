@@ -194,5 +194,13 @@ int render_motion(Scene& s, const tmpt_camera* cam, const tmpt_camera* prev_cam,
 // n_max and sigma_depth.  d_out32 or d_out8 may be null; d_out32 may be d_cur.
 int temporal(Scene& s, const tmpt_temporal_desc* d, const float4* d_cur, const tmpt_motion_pixel* d_motion,
              const tmpt_motion_pixel* d_pmotion, const float4* d_hist, float4* d_out32, uint32_t* d_out8);
+// tmpt_motion.hip: the clipped form (tmpt_temporal_clip); d holds the resolved
+// n_max, sigma_depth, gamma and radius; d_stat a frame (d_cur where none was
+// given); the aux pointers all three or none.  No output overlaps d_cur, d_stat
+// or a history.
+int temporal_clip(Scene& s, const tmpt_temporal_clip_desc* d, const float4* d_cur, const float4* d_stat,
+                  const tmpt_motion_pixel* d_motion, const tmpt_motion_pixel* d_pmotion, const float4* d_hist,
+                  const float4* d_aux_cur, const float4* d_aux_hist, float4* d_aux_out, float4* d_out32,
+                  uint32_t* d_out8);
 
 }  // namespace tmpt
