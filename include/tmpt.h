@@ -62,7 +62,11 @@ extern "C" {
                               tmpt_temporal with tmpt_temporal_desc (the reprojected history) -- no
                               struct above changed;
                               still 9, additive: tmpt_temporal_clip with tmpt_temporal_clip_desc (the
-                              reprojected history clipped to the current frame's local statistics) */
+                              reprojected history clipped to the current frame's local statistics);
+                              still 9, additive: the render options octree_build and octree_dev_max (the
+                              reference's octree built on the device) and the check hooks
+                              tmpt_scene_dump_octree and tmpt_octree_arrays, TMPT_FLAG_OCTREE_DEVICE for
+                              tmpt_render_multi -- no struct above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -100,7 +104,9 @@ enum {
                                     even with the octree built, so on a scene whose ties decide
                                     pixels the image is the one of tie_rule = index */
     TMPT_FLAG_WAIT_STREAM = 4,   /* the render starts after the work enqueued on desc->wait_stream */
-    TMPT_FLAG_REQUIRE_RCCL = 8   /* tmpt_render_multi: fail unless the gather runs over RCCL */
+    TMPT_FLAG_REQUIRE_RCCL = 8,  /* tmpt_render_multi: fail unless the gather runs over RCCL */
+    TMPT_FLAG_OCTREE_DEVICE = 16 /* tmpt_render_multi: its scenes build their octree on the device (option
+                                    octree_build = device); every other call refuses it as it did */
 };
 
 /* One render call = one shard of one frame (TraceImageBody over its rows,
@@ -153,7 +159,7 @@ typedef struct {
     /* the reference's octree (tmpt_scene_build_octree; 0 when none) */
     int32_t octree_nodes, octree_leaves;
     int64_t octree_refs;             /* triangle references in its leaves */
-    double octree_build_ms;          /* host build */
+    double octree_build_ms;          /* the whole tmpt_scene_build_octree call, host or device build */
     /* the last render or HitScene call: closest-hit queries whose t two or more
      * triangles share, answered again in the octree's visit order; and queries
      * the reference's root box test rejected (answered as misses) */
@@ -441,7 +447,16 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    choice per stride; the output is the same for every value
  *   motion_tile      tmpt_render_motion: the 64 pixels a wave takes at a time -- 1: an 8 x 8 block,
  *                    0: 64 consecutive pixels of a row, -1 (default): the measured choice (the row); the
- *                    records are the same for every value */
+ *                    records are the same for every value
+ *   octree_build     tmpt_scene_build_octree: where the octree is built -- 0 or "host" (default): the
+ *                    recursion on the host, uploaded; 1 or "device": a level-order build on the scene's
+ *                    stream from the triangles the scene keeps on the device, nothing uploaded.  The
+ *                    octree, its grid and the flat marks are the same word for word, and so are images,
+ *                    hits, ray counts and every statistic but octree_build_ms
+ *   octree_dev_max   octree_build=device: cap in bytes on the build's scratch (kept by the scene
+ *                    between builds) plus its result (0 = half of the free device memory).  A build
+ *                    that would pass it, or whose allocation fails, returns -12 with a message and
+ *                    the scene keeps its previous octree, flat marks and statistics exactly */
 int tmpt_scene_create_ex(const float* tris, int32_t n, int32_t device, const char* options, tmpt_scene** out);
 int tmpt_scene_set_option(tmpt_scene* scene, const char* key, double value);
 int tmpt_scene_get_option(const tmpt_scene* scene, const char* key, double* value);
@@ -471,6 +486,34 @@ int tmpt_octree_bounds(const float bmin[3], const float bmax[3], float box[6]);
  * the preorder walk (box bits, leaf lists)}.  Tests compare it with the
  * oracle's octree. */
 int tmpt_octree_digest(const float* tris, int32_t n, const float bmin[3], const float bmax[3], uint64_t out[5]);
+/* Check hook: the octree a scene holds, as its kernels read it, copied to host memory.
+ *   nodes  info[0] records of 8 words (32 B) in depth-first preorder: box min.xyz (f32 bits), [3] the
+ *          skip link (the index of the node after this subtree), box max.xyz, [7] the offset of the
+ *          leaf's list in refs, or -1 for an inner node
+ *   refs   info[2] words: per leaf in preorder its count, then its triangle ids in the scene's order
+ *   info   {nodes, leaves, reference words (counts included), depth, triangles marked flat}; all 0
+ *          on a scene without an octree
+ *   grid   (may be NULL) the 16 floats of the crack grid: reach, drift.xyz, r0.xyz, 1/cell.xyz,
+ *          cell.xyz, band.xyz
+ * nodes = refs = NULL: only info (and grid) are written (the sizes to allocate).  The call
+ * synchronises the scene's stream and launches nothing.  -22 with a message, checked in this order
+ * before any device call: a null scene, a null info, one buffer without the other, node_words below
+ * 8 * nodes, ref_words below the reference words. */
+int tmpt_scene_dump_octree(const tmpt_scene* scene, uint32_t* nodes, uint64_t node_words, uint32_t* refs,
+                           uint64_t ref_words, int64_t info[5], float grid[16]);
+/* Check hook (host only, no device): the same arrays for n triangles and a root box, made by
+ *   method 0  the recursion tmpt_scene_build_octree runs under octree_build=host
+ *   method 1  the passes of the device build (octree_build=device) run as host loops, one loop per
+ *             kernel: level-order lists, counts, prefix sums, bottom-up sizes, top-down preorder
+ *             indices
+ * info[4] and grid come from the arrays by the scene's own rules; the two methods give the same
+ * words.  nodes = refs = NULL: only info (and grid) are written.  -22 with a message, checked in
+ * this order: n < 0, null tris with n > 0, a null bmin or bmax, a method other than 0 / 1, a null
+ * info, one buffer without the other; then, once the sizes are known, node_words below 8 * nodes or
+ * ref_words below the reference words; an octree past INT32_MAX nodes or reference words. */
+int tmpt_octree_arrays(const float* tris, int32_t n, const float bmin[3], const float bmax[3], int32_t method,
+                       uint32_t* nodes, uint64_t node_words, uint32_t* refs, uint64_t ref_words, int64_t info[5],
+                       float grid[16]);
 /* Check hook (host only, no device): which of n_rays answered queries the
  * octree re-answers besides ties -- rays n_rays x {o.xyz, d.xyz}, t and ids the
  * closest (or first) hit of each (ids < 0: a miss, never flagged):
@@ -1110,8 +1153,8 @@ int tmpt_scene_dump_bvh(const tmpt_scene* scene, int32_t layout, uint32_t* nodes
  * Both modes synchronise the scene's stream first, replace the scene's host copy of the
  * triangles, and DROP THE OCTREE exactly as if none had been built: the device octree is freed,
  * tmpt_stats.octree_* read 0, tie_rule in effect is index (1), no record carries the flat mark.
- * Call tmpt_scene_build_octree again with the new bounds (the octree is a host build over bounds
- * only the caller knows).  The progressive state is invalidated: a render with spp_begin > 0
+ * Call tmpt_scene_build_octree again with the new bounds (only the caller knows them; under option
+ * octree_build=device that build runs on the device too).  The progressive state is invalidated: a render with spp_begin > 0
  * straight after fails with -22, as after a camera change.  Like tmpt_scene_build_octree the call
  * must not run while a call on the scene is in flight on another host thread.
  * -22 with a message, checked in this order before any device call: an unknown mode, n < 0, null

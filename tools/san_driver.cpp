@@ -10,6 +10,8 @@
 //   * the reference's octree (tmpt_octree.cpp build_octree): the root's 8
 //     subtrees on 8 threads, spliced -- vs the oracle's octree (digest)
 //   * the crack grid and flat triangles of that octree (host code only)
+//   * the device build's passes as host loops (build_octree_levels,
+//     octree_offsets_levels; tmpt_octree_build.h) -- vs that octree, word for word
 //   * the oracle's pthreads: batched HitScene and the row-parallel render, on
 //     1 and 8 threads -- the same answers and pixels
 // Exit status 0 = every check passed (the sanitizers abort on their own finds).
@@ -101,6 +103,18 @@ int main(int argc, char** argv)
         std::vector<uint8_t> flat;
         const int32_t nflat = tmpt::octree_flat_triangles(t1.data(), n, g, flat);
         CHECK(nflat >= 0 && (int32_t)flat.size() == n, "flat %s", name);
+        // ---- the level-order passes of the device build, on the host
+        tmpt::OctreeHost ol;
+        CHECK(tmpt::build_octree_levels(t1.data(), n, omin, omax, ol) == 0, "level passes %s", name);
+        CHECK(ol.nodes.size() == oh.nodes.size() && ol.refs == oh.refs && ol.leaves == oh.leaves && ol.depth == oh.depth &&
+                  !memcmp(static_cast<const void*>(ol.nodes.data()), static_cast<const void*>(oh.nodes.data()),
+                          oh.nodes.size() * sizeof(tmpt::OctNode)),
+              "level passes vs recursion %s", name);
+        double w[3];
+        tmpt::octree_offsets_levels(ol, omin, omax, w);
+        tmpt::OctGrid gl;
+        tmpt::octree_grid_from_offsets(ol.depth, w, omin, omax, gl);
+        CHECK(!memcmp(&gl, &g, sizeof g), "grid from offsets %s", name);
 
         // ---- the oracle's threads: batched HitScene and a render, 1 vs 8 threads
         const int64_t nr = 20000;

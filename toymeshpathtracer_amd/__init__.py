@@ -41,7 +41,7 @@ import numpy as np
 __all__ = [
     "Camera", "Scene", "Hit", "RenderStats", "load_scene", "write_png", "device_count",
     "SEED_ROW", "SEED_PIXEL", "SEED_SAMPLE", "ENGINE_WAVEFRONT", "ENGINE_MEGAKERNEL", "ENGINE_PERSISTENT", "lib_path", "TmptError",
-    "tile_rows", "tile_row_to_y", "render_multi", "octree_bounds", "octree_digest", "octree_flags",
+    "tile_rows", "tile_row_to_y", "render_multi", "octree_bounds", "octree_digest", "octree_flags", "octree_arrays",
     "AOV_DTYPE", "MOTION_DTYPE",
 ]
 
@@ -234,7 +234,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
            "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal", "tmpt_render_moments",
-           "tmpt_denoise_moments", "tmpt_temporal_clip")
+           "tmpt_denoise_moments", "tmpt_temporal_clip", "tmpt_scene_dump_octree", "tmpt_octree_arrays")
 
 
 def _check(rc: int, what: str) -> None:
@@ -311,6 +311,38 @@ def octree_digest(tris: np.ndarray, box_min, box_max) -> dict:
     out = (ctypes.c_uint64 * 5)()
     _check(_octree_digest(_fp(t), t.shape[0], _fp(lo), _fp(hi), out), "octree_digest")
     return dict(zip(("nodes", "leaves", "refs", "depth", "digest"), (int(v) for v in out)))
+
+
+_OCT_INFO = ("nodes", "leaves", "refs", "depth", "flat")
+
+
+def _octree_result(nodes, refs, info, grid) -> dict:
+    return {"nodes": nodes, "refs": refs, "info": dict(zip(_OCT_INFO, (int(v) for v in info))), "grid": grid}
+
+
+def octree_arrays(tris: np.ndarray, box_min, box_max, method: int = 0) -> dict:
+    """The octree Scene.build_octree(box_min, box_max) builds, as arrays, on the
+    host (tmpt_octree_arrays, no GPU): ``nodes`` uint32[n, 8] in preorder (box
+    min, skip link, box max, leaf-list offset or -1), ``refs`` int32 (per leaf
+    its count, then its triangle ids), ``info`` (nodes, leaves, refs, depth,
+    flat) and ``grid``, the 16 floats of the crack grid.  ``method=0``: the
+    recursion of the host build; ``method=1``: the passes of the device build
+    (option octree_build=device) run as host loops.  Both give the same words."""
+    # bound on first use: an earlier build of the library (TMPT_LIB_PATH, the A/B tools) has no such symbol
+    fn = _sig("tmpt_octree_arrays", ctypes.c_int, [_f32p, ctypes.c_int32, _f32p, _f32p, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p])
+    t = np.ascontiguousarray(np.asarray(tris, np.float32).reshape(-1, 9))
+    lo, hi = np.asarray(box_min, np.float32), np.asarray(box_max, np.float32)
+    info = np.zeros(5, np.int64)
+    grid = np.zeros(16, np.float32)
+    _check(fn(_fp(t), t.shape[0], _fp(lo), _fp(hi), method, None, 0, None, 0, info.ctypes.data, grid.ctypes.data),
+           "octree_arrays")
+    nodes = np.zeros((int(info[0]), 8), np.uint32)
+    refs = np.zeros(int(info[2]), np.int32)
+    _check(fn(_fp(t), t.shape[0], _fp(lo), _fp(hi), method, nodes.ctypes.data, nodes.size, refs.ctypes.data,
+              refs.size, info.ctypes.data, grid.ctypes.data), "octree_arrays")
+    return _octree_result(nodes, refs, info, grid)
 
 
 def octree_flags(tris: np.ndarray, box_min, box_max, rays, t, ids):
@@ -1132,6 +1164,23 @@ class Scene:
                   info.ctypes.data_as(_i32p)), "dump_bvh")
         keys = ("n", "n_nodes4", "depth4", "leaf_max", "count_shift", "link_bits", "builder_iters", "soa")
         return {"nodes": nodes, "tris": tris, "info": dict(zip(keys, (int(v) for v in info)))}
+
+    def dump_octree(self) -> dict:
+        """The octree the scene holds, as its kernels read it (tmpt_scene_dump_octree):
+        the arrays of :func:`octree_arrays`; all empty on a scene without one.
+        Synchronises the scene's stream, launches no kernel."""
+        fn = _sig("tmpt_scene_dump_octree", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                           ctypes.c_void_p])
+        info = np.zeros(5, np.int64)
+        grid = np.zeros(16, np.float32)
+        _check(fn(self._h, None, 0, None, 0, info.ctypes.data, grid.ctypes.data), "dump_octree")
+        nodes = np.zeros((int(info[0]), 8), np.uint32)
+        refs = np.zeros(int(info[2]), np.int32)
+        if nodes.size:
+            _check(fn(self._h, nodes.ctypes.data, nodes.size, refs.ctypes.data, refs.size, info.ctypes.data,
+                      grid.ctypes.data), "dump_octree")
+        return _octree_result(nodes, refs, info, grid)
 
     def radix_sort(self, keys, vals, bits: int = 32):
         """The device radix sort of the build and the pixel supply on caller data

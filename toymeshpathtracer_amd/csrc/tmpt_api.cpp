@@ -155,6 +155,8 @@ const OptionDef kOptions[] = {
     {"rowstream_test_abort", false, 0, 1, &Options::rowstream_test_abort, nullptr, nullptr},
     {"tie_rule", false, 0, 1, &Options::tie_rule, nullptr, nullptr},
     {"aov_group", false, 0, 16, &Options::aov_group, nullptr, nullptr},
+    {"octree_build", false, 0, 1, &Options::octree_build, nullptr, nullptr},
+    {"octree_dev_max", false, 0, 1e18, nullptr, nullptr, &Options::octree_dev_max},
     {"denoise_lds", false, -1, 1, &Options::denoise_lds, nullptr, nullptr},
     {"motion_tile", false, -1, 1, &Options::motion_tile, nullptr, nullptr},
 };
@@ -247,6 +249,7 @@ int options_parse(Options& o, const char* text, bool allow_build)
         if (key == "builder" && (val == "ploc" || val == "lbvh")) val = val == "lbvh" ? "1" : "0";
         if (key == "collapse" && (val == "greedy" || val == "sah")) val = val == "sah" ? "1" : "0";
         if (key == "tie_rule" && (val == "visit" || val == "index")) val = val == "index" ? "1" : "0";
+        if (key == "octree_build" && (val == "host" || val == "device")) val = val == "device" ? "1" : "0";
         if (key == "layout" && (val == "aos" || val == "soa")) val = val == "soa" ? "1" : "0";
         char* endp = nullptr;
         const double v = strtod(val.c_str(), &endp);
@@ -452,26 +455,42 @@ int tmpt_scene_build_octree(tmpt_scene* h, const float bmin[3], const float bmax
     TMPT_HIP(hipSetDevice(s.device));
     const auto t0 = std::chrono::steady_clock::now();
     OctreeHost t;
-    build_octree(s.tris_host.data(), s.bvh.n, bmin, bmax, t);
-    if (t.refs.size() >= (size_t)INT32_MAX || t.nodes.size() >= (size_t)INT32_MAX)
-        return bad("tmpt_scene_build_octree: octree too large");
     Octree o;
-    const size_t nb = t.nodes.size() * sizeof(OctNode), rb = std::max<size_t>(1, t.refs.size()) * sizeof(int32_t);
-    if (!o.oct.alloc(nb) || !o.oct_refs.alloc(rb) || !o.oct_view.alloc(sizeof(OctView)) ||
-        hipMemcpy(o.oct, t.nodes.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-        (t.refs.size() && hipMemcpy(o.oct_refs, t.refs.data(), t.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice) !=
-                              hipSuccess))
-        return (set_error("tmpt_scene_build_octree: out of device memory"), -1);
+    const bool on_device = s.opt.octree_build == 1;
+    double wmax[3] = {0.0, 0.0, 0.0};
+    if (on_device) {
+        // the level-order build on the scene's stream, from the triangles the
+        // scene keeps on the device; a failure leaves the scene as it was
+        (void)hipGetLastError();
+        if (int rc = build_octree_device(s, bmin, bmax, o, wmax)) return rc;
+    } else {
+        build_octree(s.tris_host.data(), s.bvh.n, bmin, bmax, t);
+        if (t.refs.size() >= (size_t)INT32_MAX || t.nodes.size() >= (size_t)INT32_MAX)
+            return bad("tmpt_scene_build_octree: octree too large");
+        const size_t nb = t.nodes.size() * sizeof(OctNode), rb = std::max<size_t>(1, t.refs.size()) * sizeof(int32_t);
+        if (!o.oct.alloc(nb) || !o.oct_refs.alloc(rb) || !o.oct_view.alloc(sizeof(OctView)) ||
+            hipMemcpy(o.oct, t.nodes.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+            (t.refs.size() && hipMemcpy(o.oct_refs, t.refs.data(), t.refs.size() * sizeof(int32_t), hipMemcpyHostToDevice) !=
+                                  hipSuccess))
+            return (set_error("tmpt_scene_build_octree: out of device memory"), -1);
+    }
     if (ensure_counters(s)) return -1;
     if (s.stream) (void)hipStreamSynchronize(s.stream);  // a render in flight may still read the old one
     // the crack grid and the flat triangles (tmpt_internal.h OctGrid), marked
     // in the BVH's triangle records so that a hit on one flags its query
-    octree_grid(t, bmin, bmax, o.oct_grid);
+    if (on_device)
+        octree_grid_from_offsets(o.oct_depth, wmax, bmin, bmax, o.oct_grid);
+    else
+        octree_grid(t, bmin, bmax, o.oct_grid);
     std::vector<uint8_t> flat;
     o.oct_flat = octree_flat_triangles(s.tris_host.data(), s.bvh.n, o.oct_grid, flat);
     if (mark_flat_triangles(s, flat)) return -1;
-    o.n_oct = (int32_t)t.nodes.size();
-    o.n_oct_refs = (int64_t)t.refs.size();
+    if (!on_device) {
+        o.n_oct = (int32_t)t.nodes.size();
+        o.n_oct_refs = (int64_t)t.refs.size();
+        o.oct_leaves = t.leaves;
+        o.oct_depth = t.depth;
+    }
     const OctView ov{o.oct, o.oct_refs, o.n_oct, o.oct_flat, s.ties, o.oct_grid, o.n_oct_refs};
     if (hipMemcpy(o.oct_view, &ov, sizeof(ov), hipMemcpyHostToDevice) != hipSuccess) {
         // the previous octree (if any) stays in use: give the records back its
@@ -481,8 +500,6 @@ int tmpt_scene_build_octree(tmpt_scene* h, const float bmin[3], const float bmax
         (void)mark_flat_triangles(s, old_flat);
         return (set_error("tmpt_scene_build_octree: upload failed"), -1);
     }
-    o.oct_leaves = t.leaves;
-    o.oct_depth = t.depth;
     for (int c = 0; c < 3; ++c) {
         o.oct_lo[c] = bmin[c];
         o.oct_hi[c] = bmax[c];
@@ -574,6 +591,84 @@ int tmpt_octree_digest(const float* tris, int32_t n, const float bmin[3], const 
     out[2] = t.refs.size() - (uint64_t)t.leaves;  // triangle references (the count words excluded)
     out[3] = (uint64_t)t.depth;
     out[4] = octree_digest(t);
+    return 0;
+    TMPT_GUARD_END
+}
+
+namespace {
+void grid_floats(const OctGrid& g, float out[16])
+{
+    static_assert(sizeof(OctGrid) == 16 * sizeof(float), "OctGrid is 16 floats");
+    memcpy(out, &g, sizeof(OctGrid));
+}
+}  // namespace
+
+int tmpt_scene_dump_octree(const tmpt_scene* hc, uint32_t* nodes, uint64_t node_words, uint32_t* refs,
+                           uint64_t ref_words, int64_t info[5], float grid[16])
+{
+    TMPT_GUARD_BEGIN
+    if (!hc) return bad("tmpt_scene_dump_octree: null scene");
+    if (!info) return bad("tmpt_scene_dump_octree: null info");
+    if ((nodes == nullptr) != (refs == nullptr)) return bad("tmpt_scene_dump_octree: nodes and refs go together");
+    Scene& s = const_cast<tmpt_scene*>(hc)->s;
+    const Octree& o = s.octree;
+    const bool have = (bool)o.oct;
+    const uint64_t nw = have ? 8 * (uint64_t)o.n_oct : 0, rw = have ? (uint64_t)o.n_oct_refs : 0;
+    if (nodes && node_words < nw) return bad("tmpt_scene_dump_octree: node buffer too small");
+    if (nodes && ref_words < rw) return bad("tmpt_scene_dump_octree: reference buffer too small");
+    info[0] = have ? o.n_oct : 0;
+    info[1] = have ? o.oct_leaves : 0;
+    info[2] = (int64_t)rw;
+    info[3] = have ? o.oct_depth : 0;
+    info[4] = have ? o.oct_flat : 0;
+    if (grid) grid_floats(have ? o.oct_grid : OctGrid{}, grid);
+    if (!nodes || !have) return 0;
+    TMPT_HIP(hipSetDevice(s.device));
+    TMPT_HIP(hipStreamSynchronize(s.stream));
+    if (nw) TMPT_HIP(hipMemcpy(nodes, o.oct, 4 * nw, hipMemcpyDeviceToHost));
+    if (rw) TMPT_HIP(hipMemcpy(refs, o.oct_refs, 4 * rw, hipMemcpyDeviceToHost));
+    return 0;
+    TMPT_GUARD_END
+}
+
+int tmpt_octree_arrays(const float* tris, int32_t n, const float bmin[3], const float bmax[3], int32_t method,
+                       uint32_t* nodes, uint64_t node_words, uint32_t* refs, uint64_t ref_words, int64_t info[5],
+                       float grid[16])
+{
+    TMPT_GUARD_BEGIN
+    if (n < 0) return bad("tmpt_octree_arrays: n < 0");
+    if (n > 0 && !tris) return bad("tmpt_octree_arrays: null triangles with n > 0");
+    if (!bmin || !bmax) return bad("tmpt_octree_arrays: null bounds");
+    if (method != 0 && method != 1) return bad("tmpt_octree_arrays: method is 0 (recursion) or 1 (level-order passes)");
+    if (!info) return bad("tmpt_octree_arrays: null info");
+    if ((nodes == nullptr) != (refs == nullptr)) return bad("tmpt_octree_arrays: nodes and refs go together");
+    OctreeHost t;
+    OctGrid g;
+    if (method == 0) {
+        build_octree(tris, n, bmin, bmax, t);
+        if (t.refs.size() >= (size_t)INT32_MAX || t.nodes.size() >= (size_t)INT32_MAX)
+            return bad("tmpt_octree_arrays: octree too large");
+        octree_grid(t, bmin, bmax, g);
+    } else {
+        if (build_octree_levels(tris, n, bmin, bmax, t)) return bad("tmpt_octree_arrays: octree too large");
+        double w[3];
+        octree_offsets_levels(t, bmin, bmax, w);
+        octree_grid_from_offsets(t.depth, w, bmin, bmax, g);
+    }
+    const uint64_t nw = 8 * (uint64_t)t.nodes.size(), rw = t.refs.size();
+    if (nodes && node_words < nw) return bad("tmpt_octree_arrays: node buffer too small");
+    if (nodes && ref_words < rw) return bad("tmpt_octree_arrays: reference buffer too small");
+    std::vector<uint8_t> flat;
+    info[0] = (int64_t)t.nodes.size();
+    info[1] = t.leaves;
+    info[2] = (int64_t)rw;
+    info[3] = t.depth;
+    info[4] = octree_flat_triangles(tris, n, g, flat);
+    if (grid) grid_floats(g, grid);
+    if (nodes) {
+        memcpy(nodes, static_cast<const void*>(t.nodes.data()), 4 * nw);
+        if (rw) memcpy(refs, t.refs.data(), 4 * rw);
+    }
     return 0;
     TMPT_GUARD_END
 }
@@ -1359,6 +1454,8 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
         for (int g = 0; g < nd; ++g)
             th.emplace_back([&, g]() {
                 rcs[(size_t)g] = tmpt_scene_create(tris, n, devices[g], &scenes[(size_t)g]);
+                if (!rcs[(size_t)g] && octree_box && (desc->flags & TMPT_FLAG_OCTREE_DEVICE))
+                    rcs[(size_t)g] = tmpt_scene_set_option(scenes[(size_t)g], "octree_build", 1.0);
                 if (!rcs[(size_t)g] && octree_box)  // main.cpp:312
                     rcs[(size_t)g] = tmpt_scene_build_octree(scenes[(size_t)g], octree_box, octree_box + 3);
                 if (rcs[(size_t)g]) errs[(size_t)g] = tmpt_last_error();

@@ -2,7 +2,7 @@
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png [--shrink K]]
 //        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
-//        [--twist DEG,FRAMES [--rebuild] [--temporal [--clip [GAMMA[,RADIUS[,NMAX]]]]]]
+//        [--twist DEG,FRAMES [--rebuild] [--temporal [--clip [GAMMA[,RADIUS[,NMAX]]]]]] [--octree host|device]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -57,6 +57,15 @@ static double now_s()
 
 static float saturate(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 
+// --octree host|device: where every scene of this run builds its octree (option octree_build)
+static int g_octree_device = 0;
+static int build_octree(tmpt_scene* scene, const float box[6])
+{
+    if (g_octree_device)
+        if (int rc = tmpt_scene_set_option(scene, "octree_build", 1.0)) return rc;
+    return tmpt_scene_build_octree(scene, box, box + 3);
+}
+
 // The AOV pass on `device` (its own scene, the octree built as for the frame) and its three
 // images, all float32 maps, alpha 255:
 //   PREFIX_normal.png  uint8(saturate(n * 0.5 + 0.5) * 255) per channel
@@ -74,7 +83,7 @@ static int write_aovs(const char* prefix, const float* tris, int32_t n, const fl
     memset(&desc, 0, sizeof(desc));
     desc.width = w; desc.height = h; desc.spp = spp; desc.seed_mode = TMPT_SEED_SAMPLE;
     uint64_t rays = 0;
-    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    int rc = build_octree(scene, box);
     if (!rc) rc = tmpt_render_aov(scene, cam, &desc, rec.data(), &rays);
     tmpt_stats st;
     if (!rc) rc = tmpt_get_stats(scene, &st);
@@ -137,7 +146,7 @@ static int write_denoised(const char* path, const float* tris, int32_t n, const 
     dn.width = w; dn.height = h; dn.spp = spp; dn.normal_exp = -1;
     uint64_t rays = 0, aov_rays = 0;
     tmpt_stats st;
-    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    int rc = build_octree(scene, box);
     if (!rc && shrink)
         rc = tmpt_render_moments(scene, cam, &desc, nullptr, rad.data(), mom.data(), nullptr, nullptr, nullptr, &rays);
     else if (!rc)
@@ -175,7 +184,7 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
     tmpt_adaptive_info info;
     tmpt_stats st;
     uint64_t rays = 0;
-    int rc = tmpt_scene_build_octree(scene, box, box + 3);
+    int rc = build_octree(scene, box);
     if (!rc && shrink)
         rc = tmpt_render_moments(scene, cam, &desc, ad, rad.data(), mom.data(), image.data(), cnt.data(), &info, &rays);
     else if (!rc)
@@ -268,7 +277,7 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
         if (temporal) rc = tmpt_scene_set_option(scene, "sample_base", (double)f * desc->spp);
         if (!rc) rc = tmpt_scene_update(scene, cur.data(), n, rebuild ? TMPT_UPDATE_REBUILD : TMPT_UPDATE_REFIT);
         if (!rc) rc = tmpt_octree_bounds(bmin, bmax, box);
-        if (!rc) rc = tmpt_scene_build_octree(scene, box, box + 3);
+        if (!rc) rc = build_octree(scene, box);
         if (!rc) rc = tmpt_scene_get_option(scene, "update_ms", &ms);
         if (!rc) rc = tmpt_scene_get_option(scene, "bvh_cost", &cost);
         if (!rc && !temporal) rc = tmpt_render(scene, cam, desc, image.data(), &rays);
@@ -321,7 +330,9 @@ int main(int argc, const char** argv)
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
                "[--denoise file.png [--shrink k]] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
-               "[--twist deg,frames [--rebuild] [--temporal [--clip [gamma[,radius[,nmax]]]]]]\n"
+               "[--twist deg,frames [--rebuild] [--temporal [--clip [gamma[,radius[,nmax]]]]]] [--octree host|device]\n"
+               "  --octree: where the reference's octree is built, every time this run builds one (each frame of "
+               "--twist too): host (default) or device (option octree_build)\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
                "any pixel within radius columns and rows of it\n"
                "  --shrink (with --denoise): the noise-aware filter (tmpt_denoise_moments) over the frame and its "
@@ -398,6 +409,14 @@ int main(int argc, const char** argv)
             }
             twist = true;
         }
+        else if (!strcmp(argv[i], "--octree") && i + 1 < argc) {
+            ++i;
+            if (strcmp(argv[i], "host") != 0 && strcmp(argv[i], "device") != 0) {
+                printf("ERROR: invalid --octree argument '%s' (host or device)\n", argv[i]);
+                return 1;
+            }
+            g_octree_device = !strcmp(argv[i], "device");
+        }
         else if (!strcmp(argv[i], "--rebuild")) rebuild = true;
         else if (!strcmp(argv[i], "--temporal")) temporal = true;
         else if (!strcmp(argv[i], "--clip")) {
@@ -459,6 +478,7 @@ int main(int argc, const char** argv)
     tmpt_render_desc desc;
     memset(&desc, 0, sizeof(desc));
     desc.width = w; desc.height = h; desc.spp = spp; desc.seed_mode = seed; desc.engine = engine;
+    if (g_octree_device) desc.flags |= TMPT_FLAG_OCTREE_DEVICE;  // read by tmpt_render_multi, which builds its own scenes
     std::vector<int32_t> devs(gpus);
     for (int g = 0; g < gpus; ++g) devs[g] = device + g;
     uint64_t total = 0;

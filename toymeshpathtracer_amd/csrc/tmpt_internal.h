@@ -187,7 +187,9 @@ struct alignas(16) TriOrig {
 //   hi = box max.xyz, w = ref  (int bits): -1 for an inner node; a leaf's
 //        triangles are refs[ref + 1 .. ref + refs[ref]] in the reference's order
 // Built on the host (the reference's build is untimed too, main.cpp:312 vs
-// :319) by tmpt_octree.cpp; read by the device only for flagged queries.
+// :319) by tmpt_octree.cpp, or under option octree_build=device by
+// tmpt_octree_dev.hip, word for word the same; read by the device only for
+// flagged queries.
 struct alignas(16) OctNode {
     float4 lo;
     float4 hi;
@@ -261,6 +263,16 @@ uint64_t octree_digest(const OctreeHost& t);
 // flat on one of its planes (flat[i] = 1).
 void octree_grid(const OctreeHost& t, const float bmin[3], const float bmax[3], OctGrid& g);
 int32_t octree_flat_triangles(const float* tris9, int32_t n, const OctGrid& g, std::vector<uint8_t>& flat);
+// octree_grid in its two halves: the cell of axis k at `depth`, and the grid
+// from the largest plane offset per axis (what octree_grid finds over t.nodes;
+// the device build reduces it on the device)
+double octree_cell(int32_t depth, const float bmin[3], const float bmax[3], int k);
+void octree_grid_from_offsets(int32_t depth, const double wmax[3], const float bmin[3], const float bmax[3], OctGrid& g);
+// The device build's passes (tmpt_octree_build.h) as host loops: the same
+// arrays as build_octree (0), or -1 where a level or the result passes
+// INT32_MAX; and its plane-offset reduction.  tmpt_octree_arrays method 1.
+int build_octree_levels(const float* tris9, int32_t n, const float bmin[3], const float bmax[3], OctreeHost& out);
+void octree_offsets_levels(const OctreeHost& t, const float bmin[3], const float bmax[3], double w[3]);
 
 // Build option layout=soa (the north star's "SoA" A/B):
 // the BVH4Q nodes and the leaf-ordered triangle records as planes, each plane
@@ -386,6 +398,9 @@ struct Options {
     int aov_group = 0;        // AOV pass: lanes that share a pixel (0 = auto, else 1, 2, 4, 8 or 16)
     int motion_tile = -1;     // tmpt_render_motion: a wave takes an 8 x 8 block of pixels (1), 64 pixels of a row
                               // (0), or the measured choice (-1)
+    int octree_build = 0;     // tmpt_scene_build_octree: 0 = the host build (tmpt_octree.cpp), 1 = the level-order
+                              // build on the device (tmpt_octree_dev.hip); the same octree word for word
+    double octree_dev_max = 0.0;  // octree_build=device: cap on its scratch and result, bytes (0 = half of the free HBM)
     int denoise_lds = -1;     // tmpt_denoise: levels of stride 1 and 2 read an LDS tile + halo (1), every level
                               // reads global memory directly (0), or the measured choice per stride (-1)
 };
@@ -450,6 +465,10 @@ struct Scene {
     // the reference's octree, and the counter of closest-hit queries answered
     // through it in the current call
     Octree octree;
+    // octree_build=device: the build's scratch, bump-allocated chunks (kept, and
+    // grown by further chunks; counted against octree_dev_max)
+    std::vector<DeviceBuffer<>> oct_scratch;
+    DeviceBuffer<uint32_t> oct_flags;  // and its overlap flags, one level's at a time (kept, grown)
     unsigned long long* ties = nullptr;  // [0] re-answered ties, [1] root-box misses (inside counters)
     uint64_t tie_queries = 0, root_misses = 0, crack_queries = 0;
     // row seeding: the engine of the last render (0 none, 1 one lane per row,
@@ -584,6 +603,12 @@ int bvh_cost(Scene& s, double* out);
 // the octree's flat triangles marked in the leaf-ordered records (bit 0 of the
 // doubled index), the others cleared; flat has s.n entries (empty: clear all)
 int mark_flat_triangles(Scene& s, const std::vector<uint8_t>& flat);
+// tmpt_octree_dev.hip: option octree_build=device.  The reference's octree of
+// the scene's triangles (bvh.tri_orig) built on s.stream into o (oct, oct_refs,
+// the counts, leaves, depth) and the largest plane offset per axis for
+// octree_grid_from_offsets.  0; -12 over octree_dev_max or out of device memory
+// (the scene unchanged); -22 for a tree the host path refuses too; -1 HIP error.
+int build_octree_device(Scene& s, const float bmin[3], const float bmax[3], Octree& o, double wmax[3]);
 // tmpt_render.hip: the scene's counters, pinned copy and render events (once)
 int ensure_counters(Scene& s);
 int check_report(Scene& s, const char* what);

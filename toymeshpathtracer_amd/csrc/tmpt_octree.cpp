@@ -21,6 +21,10 @@
 // The 8 subtrees of the root are built on their own threads and spliced.
 // Like the reference's BuildOctree (main.cpp:312, outside the timed region
 // :319-333), this is scene set-up, not part of a render.
+//
+// The box and overlap rules live in tmpt_octree_build.h, shared with the device
+// build (tmpt_octree_dev.hip, option octree_build=device), whose passes are
+// restated here as host loops too (build_octree_levels).
 #include <string.h>
 
 #include <algorithm>
@@ -29,81 +33,11 @@
 #include <vector>
 
 #include "tmpt_internal.h"
+#include "tmpt_octree_build.h"  // comp, tri_overlaps_box, oct_child_box: shared with the device build
 
 namespace tmpt {
 
 namespace {
-
-inline float comp(f3 v, int q) { return q == 0 ? v.x : (q == 1 ? v.y : v.z); }
-
-// PlaneIntersectAabb (maths.cpp:165-197): does the plane through `vert` with
-// normal `n` meet the box [-half, half]?  The nearest and farthest box corners
-// along n, offset by -vert, tested with glm::dot's (x*x' + y*y') + z*z'.
-bool plane_meets_box(f3 n, f3 vert, f3 half)
-{
-    float near_c[3], far_c[3];
-    for (int q = 0; q < 3; ++q) {
-        const float h = comp(half, q), v = comp(vert, q);
-        const bool pos = comp(n, q) > 0.0f;
-        near_c[q] = pos ? -h - v : h - v;
-        far_c[q] = pos ? h - v : -h - v;
-    }
-    if (dot(n, mk(near_c[0], near_c[1], near_c[2])) > 0.0f) return false;
-    return dot(n, mk(far_c[0], far_c[1], far_c[2])) >= 0.0f;
-}
-
-// One cross-product axis of the separating-axis test (the AXISTEST_* macros,
-// maths.cpp:112-156): the two distinct vertex projections pa, pb (ordered as
-// the macro orders its pair) against the box's projected radius.
-inline bool axis_separates(float pa, float pb, float rad)
-{
-    const float lo = pa < pb ? pa : pb, hi = pa < pb ? pb : pa;
-    return lo > rad || hi < -rad;
-}
-
-// The triangle's extent on one box axis (FINDMINMAX, maths.cpp:158-163) against
-// the half size.
-inline bool extent_separates(float a, float b, float c, float h)
-{
-    float lo = a, hi = a;
-    if (b < lo) lo = b;
-    if (b > hi) hi = b;
-    if (c < lo) lo = c;
-    if (c > hi) hi = c;
-    return lo > h || hi < -h;
-}
-
-// TriangleIntersectAabb (maths.cpp:199-298): Akenine-Moller's triangle / box
-// overlap with the box centred at `c`, half size `h`.  The nine edge axes in
-// the reference's order (its early exits do not change the answer, only the
-// rounding of each projection does, so each one is formed as the macro does:
-// products, then one difference), then the box axes, then the plane.
-bool tri_overlaps_box(f3 c, f3 h, const f3* tri)
-{
-    const f3 v0 = tri[0] - c, v1 = tri[1] - c, v2 = tri[2] - c;
-    const f3 e[3] = {v1 - v0, v2 - v1, v0 - v2};
-    // vertex pairs per edge: x and y axes use (v0, v2) for edges 0 and 1 and
-    // (v0, v1) for edge 2; the z axis (v1, v2), (v0, v1), (v1, v2), each pair
-    // in the order its macro compares them
-    const f3* xy_pair[3][2] = {{&v0, &v2}, {&v0, &v2}, {&v0, &v1}};
-    const f3* z_pair[3][2] = {{&v2, &v1}, {&v0, &v1}, {&v2, &v1}};  // Z12 orders (p2, p1)
-    for (int k = 0; k < 3; ++k) {
-        const f3 E = e[k];
-        const float ax = fabsf(E.x), ay = fabsf(E.y), az = fabsf(E.z);
-        const f3 &p = *xy_pair[k][0], &q = *xy_pair[k][1];
-        // x: a = E.z, b = E.y -> a*v.y - b*v.z, rad = |E.z| h.y + |E.y| h.z
-        if (axis_separates(E.z * p.y - E.y * p.z, E.z * q.y - E.y * q.z, az * h.y + ay * h.z)) return false;
-        // y: -a*v.x + b*v.z with a = E.z, b = E.x, rad = |E.z| h.x + |E.x| h.z
-        if (axis_separates(-E.z * p.x + E.x * p.z, -E.z * q.x + E.x * q.z, az * h.x + ax * h.z)) return false;
-        // z: a*v.x - b*v.y with a = E.y, b = E.x, rad = |E.y| h.x + |E.x| h.y
-        const f3 &r = *z_pair[k][0], &s = *z_pair[k][1];
-        if (axis_separates(E.y * r.x - E.x * r.y, E.y * s.x - E.x * s.y, ay * h.x + ax * h.y)) return false;
-    }
-    if (extent_separates(v0.x, v1.x, v2.x, h.x)) return false;
-    if (extent_separates(v0.y, v1.y, v2.y, h.y)) return false;
-    if (extent_separates(v0.z, v1.z, v2.z, h.z)) return false;
-    return plane_meets_box(cross(e[0], e[1]), v0, h);
-}
 
 inline float int_bits(int32_t v)
 {
@@ -122,14 +56,8 @@ struct Builder {
     const f3* tris;  // 3 vertices per triangle
     OctreeHost out;
 
-    // child k of [lo, hi] (scene.cpp:119-141): bit 0 of k offsets x, bit 1 z,
-    // bit 2 y by the parent's half size; child 0 keeps the parent's min
-    // without an addition (a -0 coordinate stays -0)
-    static void child_box(f3 lo, f3 half, int k, f3& clo, f3& chi)
-    {
-        clo = k == 0 ? lo : lo + mk((k & 1) ? half.x : 0.0f, (k & 4) ? half.y : 0.0f, (k & 2) ? half.z : 0.0f);
-        chi = clo + half;
-    }
+    // child k of [lo, hi] (scene.cpp:119-141; tmpt_octree_build.h)
+    static void child_box(f3 lo, f3 half, int k, f3& clo, f3& chi) { oct_child_box(lo, half, k, clo, chi); }
 
     // the triangles of `ids` that overlap child box [clo, chi], in order
     // (scene.cpp:144-154: centre and half size from the child's own box)
@@ -221,22 +149,151 @@ void build_octree(const float* tris9, int32_t n, const float bmin[3], const floa
     }
 }
 
+// The device build's passes (tmpt_octree_build.h) run on the host, one loop
+// per kernel of tmpt_octree_dev.hip and in its order: the check hook
+// tmpt_octree_arrays (method 1) compares its output with build_octree's word
+// for word, so the level-order relayout is proved without a device.
+namespace {
+struct HostLevel {
+    std::vector<float> lo, hi;
+    std::vector<int32_t> start, cnt, subn, idx, ids, owner;
+    std::vector<uint32_t> split, fstart;
+    std::vector<int64_t> subr, roff;
+    OctLevel v{};
+    void nodes(size_t n)
+    {
+        lo.resize(3 * n), hi.resize(3 * n), start.resize(n), cnt.resize(n), subn.resize(n), idx.resize(n);
+        split.resize(n + 1), fstart.resize(n + 1), subr.resize(n), roff.resize(n);
+        v.n = (int32_t)n;
+    }
+    void lists(size_t m)
+    {
+        ids.resize(m), owner.resize(m);
+        v.m = (int32_t)m;
+    }
+    const OctLevel& view()
+    {
+        v.lo = lo.data(), v.hi = hi.data(), v.start = start.data(), v.cnt = cnt.data(), v.split = split.data();
+        v.fstart = fstart.data(), v.subn = subn.data(), v.subr = subr.data(), v.idx = idx.data(), v.roff = roff.data();
+        v.ids = ids.data(), v.owner = owner.data();
+        return v;
+    }
+};
+void scan_exclusive(uint32_t* p, size_t n)
+{
+    uint32_t sum = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t x = p[i];
+        p[i] = sum;
+        sum += x;
+    }
+}
+}  // namespace
+
+int build_octree_levels(const float* tris9, int32_t n, const float bmin[3], const float bmax[3], OctreeHost& out)
+{
+    out = OctreeHost();
+    std::vector<HostLevel> lv(1);
+    lv[0].nodes(1);
+    lv[0].lists((size_t)n);
+    for (int q = 0; q < 3; ++q) lv[0].lo[(size_t)q] = bmin[q], lv[0].hi[(size_t)q] = bmax[q];
+    lv[0].start[0] = 0, lv[0].cnt[0] = n;
+    for (int32_t i = 0; i < n; ++i) lv[0].ids[(size_t)i] = i, lv[0].owner[(size_t)i] = 0;  // k_oct_root
+    std::vector<uint32_t> F;
+    for (int d = 0;; ++d) {
+        const OctLevel P = lv[(size_t)d].view();
+        for (int32_t i = 0; i <= P.n; ++i) oct_classify(P, i, d);
+        scan_exclusive(P.split, (size_t)P.n + 1);
+        scan_exclusive(P.fstart, (size_t)P.n + 1);
+        const uint32_t n_split = P.split[P.n], m_split = P.fstart[P.n];
+        if (!n_split) break;
+        if (8 * (uint64_t)n_split >= (uint64_t)INT32_MAX || 8 * (uint64_t)m_split + 1 >= (uint64_t)INT32_MAX) return -1;
+        lv.emplace_back();
+        lv.back().nodes(8 * (size_t)n_split);
+        const OctLevel P1 = lv[(size_t)d].view();  // (the vector moved)
+        OctLevel C = lv.back().view();
+        for (int32_t i = 0; i < P1.n; ++i) oct_children(P1, C, i);
+        F.assign(8 * (size_t)m_split + 1, 0u);
+        for (int32_t e = 0; e < P1.m; ++e) oct_overlap(P1, C, tris9, 9, F.data(), e);
+        scan_exclusive(F.data(), F.size());
+        for (int32_t i = 0; i < P1.n; ++i) oct_child_lists(P1, C, F.data(), i);
+        lv.back().lists((size_t)F.back());
+        C = lv.back().view();
+        for (int32_t e = 0; e < P1.m; ++e) oct_scatter(P1, C, F.data(), e);
+    }
+    const int depth = (int)lv.size() - 1;
+    for (int d = depth; d >= 0; --d) {
+        const OctLevel P = lv[(size_t)d].view(), C = d < depth ? lv[(size_t)d + 1].view() : OctLevel{};
+        for (int32_t i = 0; i < P.n; ++i) oct_sizes(P, C, i);
+    }
+    const int64_t nn = lv[0].subn[0], nr = lv[0].subr[0];
+    if (nr >= (int64_t)INT32_MAX || nn >= (int64_t)INT32_MAX) return -1;
+    lv[0].idx[0] = 0, lv[0].roff[0] = 0;
+    for (int d = 0; d < depth; ++d) {
+        const OctLevel P = lv[(size_t)d].view(), C = lv[(size_t)d + 1].view();
+        for (int32_t i = 0; i < P.n; ++i) oct_preorder(P, C, i);
+    }
+    std::vector<int32_t> words(8 * (size_t)nn);
+    out.refs.resize((size_t)nr);
+    int32_t* nodes8 = words.data();
+    for (int d = 0; d <= depth; ++d) {
+        const OctLevel L = lv[(size_t)d].view();
+        for (int32_t i = 0; i < L.n; ++i) oct_emit_node(L, nodes8, out.refs.data(), i);
+        for (int32_t e = 0; e < L.m; ++e) oct_emit_entry(L, out.refs.data(), e);
+        out.leaves += L.n - (int32_t)L.split[L.n];
+    }
+    out.depth = depth;
+    static_assert(sizeof(OctNode) == 32, "8 words");
+    out.nodes.resize((size_t)nn);
+    memcpy(static_cast<void*>(out.nodes.data()), words.data(), 32 * (size_t)nn);
+    return 0;
+}
+
+// The device build's plane-offset reduction on the host (k_oct_offsets).
+void octree_offsets_levels(const OctreeHost& t, const float bmin[3], const float bmax[3], double w[3])
+{
+    std::vector<int32_t> words(8 * t.nodes.size());
+    if (!words.empty()) memcpy(words.data(), static_cast<const void*>(t.nodes.data()), 4 * words.size());
+    const int32_t* nodes8 = words.data();
+    for (int k = 0; k < 3; ++k) {
+        const double r0 = bmin[k], cell = octree_cell(t.depth, bmin, bmax, k);
+        w[k] = 0.0;
+        for (int32_t i = 0; i < (int32_t)t.nodes.size(); ++i) w[k] = oct_node_offset(nodes8, i, k, r0, cell, w[k]);
+    }
+}
+
 // The crack grid (tmpt_internal.h OctGrid): every node box face lies on a plane
 // r0 + j * cell of the finest level to within the largest offset found here
 // (the rounding of min + half + half down the tree); the band adds margin for
 // the device's float evaluation of the plane and of the hit point.
 void octree_grid(const OctreeHost& t, const float bmin[3], const float bmax[3], OctGrid& g)
 {
-    const double scale = std::ldexp(1.0, t.depth);
-    float cmin = INFINITY;
+    double w[3] = {0.0, 0.0, 0.0};
     for (int k = 0; k < 3; ++k) {
-        const double r0 = bmin[k], size = (double)bmax[k] - (double)bmin[k];
-        const double cell = size > 0.0 ? size / scale : 1.0;
-        double w = 0.0;
+        const double r0 = bmin[k], cell = octree_cell(t.depth, bmin, bmax, k);
         for (const OctNode& nd : t.nodes) {
             const double v[2] = {comp(mk(nd.lo.x, nd.lo.y, nd.lo.z), k), comp(mk(nd.hi.x, nd.hi.y, nd.hi.z), k)};
-            for (double x : v) w = std::max(w, std::fabs(x - (r0 + std::nearbyint((x - r0) / cell) * cell)));
+            for (double x : v) w[k] = std::max(w[k], oct_plane_offset(x, r0, cell));
         }
+    }
+    octree_grid_from_offsets(t.depth, w, bmin, bmax, g);
+}
+
+double octree_cell(int32_t depth, const float bmin[3], const float bmax[3], int k)
+{
+    const double scale = std::ldexp(1.0, depth);
+    const double size = (double)bmax[k] - (double)bmin[k];
+    return size > 0.0 ? size / scale : 1.0;
+}
+
+// The grid from the largest plane offset per axis (a max over all node boxes,
+// exact in any order: the device build reduces it, tmpt_octree_dev.hip).
+void octree_grid_from_offsets(int32_t depth, const double wmax[3], const float bmin[3], const float bmax[3], OctGrid& g)
+{
+    float cmin = INFINITY;
+    for (int k = 0; k < 3; ++k) {
+        const double cell = octree_cell(depth, bmin, bmax, k);
+        const double w = wmax[k];
         const float ulp = std::nextafter(std::max(std::fabs(bmin[k]), std::fabs(bmax[k])), INFINITY) -
                           std::max(std::fabs(bmin[k]), std::fabs(bmax[k]));
         g.r0[k] = bmin[k];
