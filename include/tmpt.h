@@ -66,7 +66,10 @@ extern "C" {
                               still 9, additive: the render options octree_build and octree_dev_max (the
                               reference's octree built on the device) and the check hooks
                               tmpt_scene_dump_octree and tmpt_octree_arrays, TMPT_FLAG_OCTREE_DEVICE for
-                              tmpt_render_multi -- no struct above changed */
+                              tmpt_render_multi -- no struct above changed;
+                              still 9, additive: history-guided sampling -- tmpt_sample_plan (the
+                              accumulated moments reprojected into a per-pixel prior) and
+                              tmpt_render_guided (tmpt_render_moments with that prior in its test) */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -1003,6 +1006,82 @@ int tmpt_temporal_clip(tmpt_scene* scene, const tmpt_temporal_clip_desc* desc, c
                        const float* rgba32f_stat, const tmpt_motion_pixel* motion,
                        const tmpt_motion_pixel* prev_motion, const float* rgba32f_history, const float* aux_cur,
                        const float* aux_history, float* aux_out, float* rgba32f_out, uint8_t* rgba8_out);
+
+/* ---- History-guided sampling: a sample plan and a guided adaptive render.
+ *
+ * tmpt_sample_plan reprojects the accumulated moments frame (the aux frame of
+ * tmpt_temporal_clip, or a moments frame through tmpt_temporal: {mean mu1, mean
+ * mu2, mean 1/n, history length}) into a per-pixel prior for this frame;
+ * tmpt_render_guided is tmpt_render_moments whose stopping test judges the
+ * variance of the frame AS IT WILL BE AFTER THE BLEND, not of the raw frame.  A
+ * pixel with a long, quiet history stops at spp_min = 2; a pixel with no history
+ * keeps the plain test and runs to the cap.
+ *
+ * Frames, row order, flags, defaults and the -22 order are tmpt_temporal's, with
+ * its colour frames left out; desc supplies n_max and sigma_depth with the same
+ * defaults.  prior_out is width * height float4, 16-byte aligned where it is a
+ * device pointer; it must not overlap moments_history, whose neighbours are read.
+ *
+ * The arithmetic is the contract, under the rules stated above tmpt_motion_pixel
+ * (tests/guided_restate.py restates it in numpy).  fmaxf / fminf return the other
+ * operand for a NaN.  Per pixel p = (x, y), with m = motion[p]:
+ *   fetch:  the reset rule, the validity of m.px / m.py, fx .. ay, the four taps,
+ *           their skip rules, wgt, nsum and wsum are tmpt_temporal's statements
+ *           above, word for word, with hist = moments_history; on the taps that
+ *           count,  asum.k = asum.k + hist_q.k * wgt  (k = x, y, z; asum = {0,0,0})
+ *   reset:  prior_p = {0.0f, 0.0f, 1.0f, 0.0f}            -- the null prior
+ *   history statistics:
+ *           hY = asum.x / wsum    h2 = asum.y / wsum    hz = asum.z / wsum
+ *           nh = nsum / wsum
+ *           ne = nh / hz                     the effective sample count, as
+ *                                            tmpt_denoise_moments forms mom.w / mom.z
+ *           vh = fmaxf(0.0f, h2 - hY * hY) / fmaxf(ne - 1.0f, 1.0f)
+ *   blend weights:
+ *           n = fminf(nh + 1.0f, n_max)      a = 1.0f / n      b = 1.0f - a
+ *   result: prior_p = {hY, (b * b) * vh, a, nh}
+ * Nothing is screened.  In words, the prior holds the luminance the history will
+ * contribute, the share of the blended pixel's variance that the history brings,
+ * the blend factor tmpt_temporal will use for this frame at the same n_max, and
+ * the history length.  (tmpt_temporal_clip may shorten a history after the plan
+ * was made; the plan does not anticipate that.)
+ * The scene lends its device, stream and error channel; no geometry is read and
+ * the progressive state is left alone.  Host pointers are staged through the
+ * buffer tmpt_temporal_clip keeps.  -22, in this order, for: a null desc; a size
+ * outside tmpt_render's limits; a missing pointer; n_max < 1 (after the default)
+ * or not finite; a negative or non-finite sigma_depth; other flags; a misaligned
+ * device pointer (16 bytes); prior_out overlapping moments_history; a null scene.
+ * tmpt_get_stats afterwards: render_ms is the kernel's time on the device; the
+ * other fields keep the last render's.  Additive, the ABI version stays. */
+int tmpt_sample_plan(tmpt_scene* scene, const tmpt_temporal_desc* desc, const tmpt_motion_pixel* motion,
+                     const tmpt_motion_pixel* prev_motion, const float* moments_history, float* prior_out);
+
+/* tmpt_render_guided is tmpt_render_moments in every rule, with these differences:
+ *   moments_out  may be NULL; at least one of the four outputs must be given
+ *                (-22 otherwise).  ad NULL means the uniform schedule, as in
+ *                tmpt_render_moments.
+ *   prior        tmpt_tile_rows(desc) * width float4 in the COMPACT TILE LAYOUT of
+ *                the shard (tile row t holds the prior of global row
+ *                tmpt_tile_row_to_y(desc, t)).  It follows the outputs' flag: a
+ *                device pointer under TMPT_FLAG_OUT_DEVICE, 16-byte aligned (-22
+ *                otherwise).  NULL means the null prior everywhere.
+ * Only the own test changes.  After a pass ending at n, with mean, se2 and
+ * lim4 = 4.0f * (tau * tau) as tmpt_adaptive_desc states them and pr = prior[p]:
+ *   se2b  = pr.y + (pr.z * pr.z) * se2
+ *   meanb = pr.x + (mean - pr.x) * pr.z
+ *   lim   = lim4 * fmaxf(meanb, 1.0f / 256.0f)
+ *   own_p = n < S and se2b > lim
+ * The schedule, the sums, m1, m2, the radius rule over own, the bands,
+ * sample_base, the outputs, info, the ray count and the statistics are unchanged.
+ * With the null prior {0, 0, 1, 0}, se2b = se2 and meanb = mean exactly for every
+ * finite mean and every non-negative, infinite or NaN se2.  The call is then
+ * tmpt_render_moments bit for bit.
+ * Per-count identity still holds: a pixel that stopped at n is
+ * tmpt_render_radiance's pixel at spp = n.  Shard tiles still assemble, for the
+ * same reason as before: the prior is read at the pixel itself.  Additive, the
+ * ABI version stays. */
+int tmpt_render_guided(tmpt_scene* scene, const tmpt_camera* cam, const tmpt_render_desc* desc,
+                       const tmpt_adaptive_desc* ad, const float* prior, float* rgba32f_out, float* moments_out,
+                       uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count);
 
 /* main.cpp:312-331 over several devices in ONE process (SURVEY.md §8e's
  * single-process form): a scene per entry of devices[] (created here, freed on

@@ -234,7 +234,8 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_octree_flags", "tmpt_render_aov", "tmpt_render_radiance", "tmpt_denoise", "tmpt_fastdiv",
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
            "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal", "tmpt_render_moments",
-           "tmpt_denoise_moments", "tmpt_temporal_clip", "tmpt_scene_dump_octree", "tmpt_octree_arrays")
+           "tmpt_denoise_moments", "tmpt_temporal_clip", "tmpt_scene_dump_octree", "tmpt_octree_arrays",
+           "tmpt_sample_plan", "tmpt_render_guided")
 
 
 def _check(rc: int, what: str) -> None:
@@ -1123,6 +1124,161 @@ class Scene:
         _check(fn(self._h, ctypes.byref(d), host(radiance), host(stat), host(motion), host(prev_motion), host(history),
                   host(aux), host(aux_history), host(aux_res), host(res), host(img)), "temporal_clip")
         return res, img, aux_res
+
+    def sample_plan(self, motion, prev_motion, moments_history, n_max: float = 0.0, sigma_depth: float = 0.0, out=None,
+                    width: Optional[int] = None, height: Optional[int] = None, wait_stream="current"):
+        """The sample plan of history-guided sampling (tmpt_sample_plan;
+        include/tmpt.h states its arithmetic) over a whole frame: the accumulated
+        moments frame ``moments_history`` float32[h, w, 4] (the aux frame
+        :meth:`temporal_clip` returns, or a moments frame through :meth:`temporal`)
+        fetched where ``motion`` says each pixel's surface was and accepted where
+        ``prev_motion`` shows the same depth, as :meth:`temporal` fetches a
+        history, and turned into the per-pixel prior of :meth:`trace_guided`:
+        returns float32[h, w, 4] = {history luminance, the history's share of the
+        blended pixel's variance, the blend factor of this frame, history
+        length}; {0, 0, 1, 0} (the null prior) where the history restarts.  Use
+        the ``n_max`` and ``sigma_depth`` of the blend that will follow (0.0: the
+        defaults of :meth:`temporal`).  ``out``: a float32 array [h, w, 4] that
+        takes the prior (never ``moments_history``).  Torch tensors on the
+        scene's device may be given in place of the three arrays (``motion`` and
+        ``prev_motion`` as uint8 [h, w, 32] or any tensor of h*w*32 bytes): the
+        prior is then a torch tensor too (``out``: a contiguous float32 tensor
+        [h, w, 4], or None).  Device-pointer form, as :meth:`temporal`: three ints
+        (16-byte aligned), ``width``, ``height`` and ``out`` = the prior's
+        pointer; returns None."""
+        # bound on first use, as tmpt_render_adaptive is
+        fn = _sig("tmpt_sample_plan", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_TemporalDesc)]
+                  + [ctypes.c_void_p] * 4)
+        d = _TemporalDesc()
+        tens = hasattr(moments_history, "data_ptr")
+        dev = tens or isinstance(moments_history, int)
+        res = None
+        if tens:
+            if tuple(moments_history.shape[2:]) != (4,) or moments_history.dim() != 3:
+                raise ValueError("sample_plan: moments_history [h, w, 4] of one whole frame")
+            h, w = int(moments_history.shape[0]), int(moments_history.shape[1])
+            for t, size, name in ((moments_history, 16, "moments_history"), (motion, 32, "motion"),
+                                  (prev_motion, 32, "prev_motion")):
+                if (not hasattr(t, "data_ptr") or not t.is_contiguous() or t.numel() * t.element_size() != h * w * size
+                        or t.device != moments_history.device):
+                    raise ValueError(f"sample_plan: {name} must be a contiguous tensor of one whole frame on the "
+                                     "history's device")
+            if moments_history.dtype != torch.float32:
+                raise ValueError("sample_plan: moments_history must be float32")
+            res = torch.empty((h, w, 4), dtype=torch.float32, device=moments_history.device) if out is None else out
+            if not (hasattr(res, "data_ptr") and res.dtype == torch.float32 and tuple(res.shape) == (h, w, 4)
+                    and res.is_contiguous() and res.device == moments_history.device):
+                raise ValueError("sample_plan: out must be a contiguous float32 tensor [h, w, 4] on the history's device")
+            ptrs = [t.data_ptr() for t in (motion, prev_motion, moments_history, res)]
+        elif dev:
+            if width is None or height is None or out is None:
+                raise ValueError("sample_plan: device pointers need width, height and out")
+            h, w = int(height), int(width)
+            ptrs = [int(motion), int(prev_motion), int(moments_history), int(out)]
+        else:
+            moments_history = np.ascontiguousarray(moments_history, np.float32)
+            motion = np.ascontiguousarray(motion, MOTION_DTYPE)
+            prev_motion = np.ascontiguousarray(prev_motion, MOTION_DTYPE)
+            h, w = moments_history.shape[:2]
+            if moments_history.shape != (h, w, 4) or motion.shape != (h, w) or prev_motion.shape != (h, w):
+                raise ValueError("sample_plan: moments_history [h, w, 4], motion and prev_motion [h, w] of one whole "
+                                 "frame")
+            res = np.zeros((h, w, 4), np.float32) if out is None else out
+            if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+                    and res.flags.c_contiguous):
+                raise ValueError("sample_plan: out must be a contiguous float32 array [h, w, 4]")
+            ptrs = [a.ctypes.data for a in (motion, prev_motion, moments_history, res)]
+        d.width, d.height, d.n_max, d.sigma_depth = w, h, n_max, sigma_depth
+        if dev:
+            d.flags = FLAG_OUT_DEVICE
+            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+            if ws is not None:
+                d.flags |= FLAG_WAIT_STREAM
+                d.wait_stream = int(ws)
+        _check(fn(self._h, ctypes.byref(d), *[ctypes.c_void_p(p) for p in ptrs]), "sample_plan")
+        return res
+
+    def trace_guided(self, camera: Camera, width: int, height: int, spp: int, prior=None,
+                     spp_min: Optional[int] = None, spp_step: int = 0, threshold: float = -1.0, radius: int = 0,
+                     band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None, wait_stream="current"):
+        """:meth:`trace_moments` whose stopping test reads a per-pixel ``prior``
+        (tmpt_render_guided; include/tmpt.h states the test): the variance and the
+        mean are judged as the temporal blend will leave them, so a pixel with a
+        long, quiet history stops at ``spp_min`` (2 is the least) and a pixel
+        whose history restarted runs on as in :meth:`trace_moments`.  Returns
+        :meth:`trace_moments`' tuple (radiance, moments, rgba8, spp_map, rays,
+        info).  ``prior`` is always the WHOLE frame float32[height, width, 4] of
+        :meth:`sample_plan`, a numpy array or a torch tensor on the scene's
+        device; the method hands the call the shard's rows
+        (:func:`tile_row_to_y`), gathered on the device for a tensor.  ``None``
+        (or a frame of {0, 0, 1, 0}) is :meth:`trace_moments` bit for bit.
+        ``out``: a 4-tuple of device pointers, any of them None but not all (the
+        moments tile is optional here); the arrays returned are then None.
+        ``wait_stream`` as in :meth:`trace_image`."""
+        # bound on first use, as tmpt_render_adaptive is
+        fn = _sig("tmpt_render_guided", ctypes.c_int,
+                  [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
+                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                   ctypes.POINTER(_AdaptiveInfo), _u64p])
+        if out is None:
+            ws = None
+        elif isinstance(wait_stream, str):
+            ws = _current_stream(self.device)
+        else:
+            ws = wait_stream
+        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
+                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
+        rows = int(_tile_rows(ctypes.byref(d)))
+        tile = None  # the prior's rows of this shard, kept alive over the call
+        if prior is not None:
+            if tuple(prior.shape) != (height, width, 4):
+                raise ValueError("trace_guided: prior is the whole frame [height, width, 4]")
+            ys = tile_row_to_y(width, height, band_rows, shard, num_shards)
+            whole = len(ys) == height and bool((ys == np.arange(height)).all())
+            if hasattr(prior, "data_ptr"):
+                if prior.dtype != torch.float32:
+                    raise ValueError("trace_guided: prior must be float32")
+                tile = prior if whole else prior.index_select(0, torch.as_tensor(ys, device=prior.device))
+                tile = tile.contiguous()
+                if out is None:
+                    tile = tile.cpu().numpy()
+            else:
+                tile = np.ascontiguousarray(np.asarray(prior, np.float32)[ys])
+                if out is not None:
+                    if torch is None:
+                        raise ValueError("trace_guided: device outputs need a torch prior")
+                    tile = torch.from_numpy(tile).to(f"cuda:{self.device}")
+        p_ptr = None
+        if tile is not None:
+            p_ptr = ctypes.c_void_p(tile.data_ptr() if hasattr(tile, "data_ptr") else tile.ctypes.data)
+        ad = None
+        if spp_min is not None:
+            ad = _AdaptiveDesc()
+            ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
+            ad = ctypes.byref(ad)
+        rays = ctypes.c_uint64()
+        inf = _AdaptiveInfo()
+        cam = camera._to_c()
+
+        def info():
+            return {"passes": int(inf.passes), "samples": int(inf.samples),
+                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
+
+        if out is not None:
+            if tile is not None and ws is None:
+                torch.cuda.current_stream(self.device).synchronize()  # the gathered rows are ready
+            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
+            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, p_ptr, ptr[0], ptr[1], ptr[2], ptr[3],
+                      ctypes.byref(inf), ctypes.byref(rays)), "trace_guided")
+            return None, None, None, None, int(rays.value), info()
+        rad = np.zeros((rows, width, 4), np.float32)
+        mom = np.zeros((rows, width, 4), np.float32)
+        img = np.zeros((rows, width, 4), np.uint8)
+        cnt = np.zeros((rows, width), np.int32)
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, p_ptr, rad.ctypes.data_as(ctypes.c_void_p),
+                  mom.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p),
+                  cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf), ctypes.byref(rays)), "trace_guided")
+        return rad, mom, img, cnt, int(rays.value), info()
 
     def camera_rays(self, camera: Camera, width: int, height: int, spp: int, spp_begin: int = 0,
                     spp_count: int = 0, band_rows: int = 0, shard: int = 0, num_shards: int = 1) -> np.ndarray:

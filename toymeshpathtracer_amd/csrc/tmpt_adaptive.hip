@@ -14,7 +14,9 @@
 // k_adapt_pack, k_adapt_dilate and k_adapt_gather below; radius 0 launches none
 // of them.  k_adapt_final scales, packs and writes the three
 // outputs; tmpt_render_moments is the same call with k_adapt_final_mom in its
-// place, which also writes each pixel's luminance moments.  The host reads the next list's length (one word, with the pass's
+// place, which also writes each pixel's luminance moments; tmpt_render_guided
+// is that call with a per-pixel prior in the test (the update kernels' PRIOR
+// form).  The host reads the next list's length (one word, with the pass's
 // counters) after every pass but the last: that length sizes the next launch.
 #include <hip/hip_runtime.h>
 
@@ -49,10 +51,14 @@ constexpr int kScanBlock = 1024;
 // rounding each (the unit is built with contraction off and correctly rounded
 // division).  Bit t of mask[block] and cnt[block] say which of the block's
 // pixels stay active; none does when the pass is the last (s1 == cap).
+// PRIOR (tmpt_render_guided): the test judges the pixel as the temporal blend
+// will leave it -- one more 16-byte load per listed pixel, prior[slot]; nothing
+// else changes, and PRIOR = false reads no prior at all.
+template <bool PRIOR>
 __global__ void __launch_bounds__(64) k_adapt_update(const float4* __restrict__ sbuf, const uint32_t* __restrict__ list,
                                                      uint32_t n, int32_t spp, int32_t s0, int32_t s1, float lim4,
                                                      AdaptState* __restrict__ state, uint64_t* __restrict__ mask,
-                                                     uint32_t* __restrict__ cnt)
+                                                     uint32_t* __restrict__ cnt, const float4* __restrict__ prior)
 {
     constexpr int kC = 16;               // samples per staged chunk
     __shared__ float4 tile[64][kC + 1];  // +1: a lane's row starts on another bank
@@ -89,8 +95,14 @@ __global__ void __launch_bounds__(64) k_adapt_update(const float4* __restrict__ 
         const float fn = (float)s1;
         const float mean = st.m1 / fn;
         const float var = fmaxf(0.0f, st.m2 / fn - mean * mean);
-        const float se2 = var / (fn - 1.0f);
-        const float lim = lim4 * fmaxf(mean, 1.0f / 256.0f);
+        float se2 = var / (fn - 1.0f);
+        float meanb = mean;
+        if (PRIOR) {  // the frame as it will be after the blend (tmpt_render_guided)
+            const float4 pr = prior[pix];
+            se2 = pr.y + (pr.z * pr.z) * se2;
+            meanb = pr.x + (mean - pr.x) * pr.z;
+        }
+        const float lim = lim4 * fmaxf(meanb, 1.0f / 256.0f);
         active = s1 < spp && se2 > lim;  // a NaN compares false: the pixel stops
         st.n = s1;
         state[pix] = st;
@@ -109,10 +121,12 @@ __global__ void __launch_bounds__(64) k_adapt_update(const float4* __restrict__ 
 // pixel leaves the list only at a pass where its own test failed, so the plane
 // holds false for every dropped pixel with no clearing; pass 0 lists every slot
 // and so initialises it.
+template <bool PRIOR>
 __global__ void __launch_bounds__(64) k_adapt_update_own(const float4* __restrict__ sbuf,
                                                          const uint32_t* __restrict__ list, uint32_t n, int32_t spp,
                                                          int32_t s0, int32_t s1, float lim4,
-                                                         AdaptState* __restrict__ state, uint8_t* __restrict__ own)
+                                                         AdaptState* __restrict__ state, uint8_t* __restrict__ own,
+                                                         const float4* __restrict__ prior)
 {
     constexpr int kC = 16;               // samples per staged chunk
     __shared__ float4 tile[64][kC + 1];  // +1: a lane's row starts on another bank
@@ -148,8 +162,14 @@ __global__ void __launch_bounds__(64) k_adapt_update_own(const float4* __restric
         const float fn = (float)s1;
         const float mean = st.m1 / fn;
         const float var = fmaxf(0.0f, st.m2 / fn - mean * mean);
-        const float se2 = var / (fn - 1.0f);
-        const float lim = lim4 * fmaxf(mean, 1.0f / 256.0f);
+        float se2 = var / (fn - 1.0f);
+        float meanb = mean;
+        if (PRIOR) {  // as in k_adapt_update
+            const float4 pr = prior[pix];
+            se2 = pr.y + (pr.z * pr.z) * se2;
+            meanb = pr.x + (mean - pr.x) * pr.z;
+        }
+        const float lim = lim4 * fmaxf(meanb, 1.0f / 256.0f);
         st.n = s1;
         state[pix] = st;
         own[pix] = s1 < spp && se2 > lim ? 1 : 0;  // a NaN compares false
@@ -316,10 +336,12 @@ static size_t align256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 // ad: the resolved descriptor (defaults applied, ranges checked by the
 // caller); d_f32 / d_u8 / d_spp: device tiles or null.  d_mom (tmpt_render_moments,
-// `what` its name): the moments tile, or null.
+// `what` its name): the moments tile, or null.  d_prior (tmpt_render_guided): the
+// prior tile, one float4 per slot, or null -- the update kernels' PRIOR = false
+// instantiations then, which are the kernels as they were.
 int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
                     float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count,
-                    float4* d_mom, const char* what)
+                    float4* d_mom, const char* what, const float4* d_prior)
 {
     RenderArgs a = make_args(cam, d);
     s.row_render = false;
@@ -384,9 +406,11 @@ int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d,
             const uint32_t n = (uint32_t)n_list, nb = (n + 63u) / 64u;
             const bool last = n1 >= a.spp;
             if (radius > 0)
-                k_adapt_update_own<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, own);
+                (d_prior ? k_adapt_update_own<true> : k_adapt_update_own<false>)<<<nb, 64, 0, s.stream>>>(
+                    s.sbuf, list, n, a.spp, n0, n1, lim4, state, own, d_prior);
             else
-                k_adapt_update<<<nb, 64, 0, s.stream>>>(s.sbuf, list, n, a.spp, n0, n1, lim4, state, mask, cnt);
+                (d_prior ? k_adapt_update<true> : k_adapt_update<false>)<<<nb, 64, 0, s.stream>>>(
+                    s.sbuf, list, n, a.spp, n0, n1, lim4, state, mask, cnt, d_prior);
             TMPT_HIP(hipGetLastError());
             uint32_t* next = lists[k & 1];
             if (!last && radius > 0) {  // the neighbourhood rule: mask / cnt from the dilated own plane

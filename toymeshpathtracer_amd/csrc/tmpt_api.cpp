@@ -982,12 +982,16 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
     TMPT_GUARD_END
 }
 
-// tmpt_render_adaptive and tmpt_render_moments: one body.  `name` is the call's
-// name in errors; with_mom: moments_out is required, and ad NULL means the
-// uniform schedule spp_min = desc->spp, not the adaptive defaults.
+// tmpt_render_adaptive, tmpt_render_moments and tmpt_render_guided: one body.
+// `name` is the call's name in errors; with_mom: ad NULL means the uniform
+// schedule spp_min = desc->spp, not the adaptive defaults, and moments_out is
+// required -- unless guided, where any one of the four outputs will do and
+// `prior` (the tile's float4, following the outputs' flag; may be null) enters
+// the test.
 static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const tmpt_camera* cam,
                          const tmpt_render_desc* d, const tmpt_adaptive_desc* ad, float* rgba32f_out, float* moments_out,
-                         uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count)
+                         uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count,
+                         bool guided = false, const float* prior = nullptr)
 {
     const auto no = [name](const char* msg) { return bad((std::string(name) + ": " + msg).c_str()); };
     if (!h || !cam || !d) return no("null argument");
@@ -1017,7 +1021,10 @@ static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const t
     if (r.radius < 0 || r.radius > 8) return no("radius outside 0 .. 8 (0 = no neighbourhood rule)");
     if (1 + (d->spp - r.spp_min + r.spp_step - 1) / r.spp_step > 64)
         return no("spp_min / spp_step give a schedule of more than 64 passes");
-    if (with_mom) {
+    if (guided) {
+        if (!rgba32f_out && !moments_out && !rgba8_out && !spp_out)
+            return no("no output (rgba32f_out, moments_out, rgba8_out and spp_out are all null)");
+    } else if (with_mom) {
         if (!moments_out) return no("moments_out is required");
     } else if (!rgba32f_out && !rgba8_out && !spp_out) {
         return no("no output (rgba32f_out, rgba8_out and spp_out are all null)");
@@ -1029,6 +1036,7 @@ static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const t
                              "spp_out 4)"
                            : "device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
                              "spp_out 4)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(prior) & 15u) != 0) return no("a device prior must be 16-byte aligned");
     (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
     Scene& s = h->s;
     TMPT_HIP(hipSetDevice(s.device));
@@ -1049,7 +1057,15 @@ static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const t
     if (own_m) d_m = own_m;
     if (own_8) d_8 = own_8;
     if (own_n) d_n = own_n;
-    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count, d_m, name);
+    const float4* d_p = reinterpret_cast<const float4*>(prior);
+    DeviceBuffer<float4> own_p;
+    if (prior && !dev_out && px) {  // a host prior: staged beside the outputs' tiles
+        if (!own_p.alloc(px * sizeof(float4))) return no("out of device memory");
+        if (hipMemcpy(own_p, prior, px * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess)
+            return (set_error(std::string(name) + ": upload failed"), -1);
+        d_p = own_p;
+    }
+    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count, d_m, name, d_p);
     if (!rc) rc = check_report(s, name);
     if (!rc && !dev_out && px) {
         if ((rgba32f_out && hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
@@ -1078,6 +1094,16 @@ int tmpt_render_moments(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render
     TMPT_GUARD_BEGIN
     return adaptive_call("tmpt_render_moments", true, h, cam, d, ad, rgba32f_out, moments_out, rgba8_out, spp_out, info,
                          ray_count);
+    TMPT_GUARD_END
+}
+
+int tmpt_render_guided(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
+                       const float* prior, float* rgba32f_out, float* moments_out, uint8_t* rgba8_out,
+                       int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count)
+{
+    TMPT_GUARD_BEGIN
+    return adaptive_call("tmpt_render_guided", true, h, cam, d, ad, rgba32f_out, moments_out, rgba8_out, spp_out, info,
+                         ray_count, true, prior);
     TMPT_GUARD_END
 }
 
@@ -1282,6 +1308,61 @@ int tmpt_temporal(tmpt_scene* h, const tmpt_temporal_desc* d, const float* rgba3
             (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
             rc = (set_error("tmpt_temporal: readback failed"), -1);
     }
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_sample_plan(tmpt_scene* h, const tmpt_temporal_desc* d, const tmpt_motion_pixel* motion,
+                     const tmpt_motion_pixel* prev_motion, const float* moments_history, float* prior_out)
+{
+    TMPT_GUARD_BEGIN
+    const char* const fn = "tmpt_sample_plan: ";
+    auto no = [&](const char* what) { return bad((std::string(fn) + what).c_str()); };
+    // tmpt_temporal's checks in its order, its colour frames left out
+    if (!d) return no("null descriptor");
+    if (d->width < 1 || d->width > 10000) return no("invalid width");
+    if (d->height < 1 || d->height > 10000) return no("invalid height");
+    if (!motion || !prev_motion || !moments_history || !prior_out) return no("null argument");
+    tmpt_temporal_desc r = *d;  // the defaults, in one place: tmpt_temporal's
+    if (r.n_max == 0.0f) r.n_max = 3.0f;
+    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
+    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f)) return no("n_max must be finite and at least 1 (0 = default)");
+    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
+        return no("sigma_depth must be finite and not negative (0 = default)");
+    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
+    const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
+    auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    if (dev && ((at(motion) | at(prev_motion) | at(moments_history) | at(prior_out)) & 15u) != 0)
+        return no("device pointers must be 16-byte aligned");
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4);
+    if (at(prior_out) < at(moments_history) + fb && at(moments_history) < at(prior_out) + fb)
+        return no("prior_out overlaps moments_history (its neighbours are read)");
+    if (!h) return no("null scene");
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const float4* d_hist = reinterpret_cast<const float4*>(moments_history);
+    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
+    float4* d_out = reinterpret_cast<float4*>(prior_out);
+    if (!dev) {  // host pointers: staged in the scene's kept buffer, as tmpt_temporal_clip stages its own
+        const size_t mb = n * sizeof(tmpt_motion_pixel);
+        TMPT_HIP(hipStreamSynchronize(s.stream));
+        if (!s.clip_stage.reserve(2 * fb + 2 * mb)) return no("out of device memory");
+        char* at_dev = s.clip_stage.as<char>();
+        auto take = [&](size_t bytes) { char* p = at_dev; at_dev += bytes; return p; };
+        auto up = [&](const void* src, size_t bytes) -> char* {
+            char* p = take(bytes);
+            return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? p : nullptr;
+        };
+        d_hist = reinterpret_cast<const float4*>(up(moments_history, fb));
+        d_m = reinterpret_cast<const tmpt_motion_pixel*>(up(motion, mb));
+        d_pm = reinterpret_cast<const tmpt_motion_pixel*>(up(prev_motion, mb));
+        if (!d_hist || !d_m || !d_pm) return (set_error(std::string(fn) + "upload failed"), -1);
+        d_out = reinterpret_cast<float4*>(take(fb));
+    }
+    int rc = sample_plan(s, &r, d_m, d_pm, d_hist, d_out);
+    if (!rc && !dev && hipMemcpy(prior_out, d_out, fb, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = (set_error(std::string(fn) + "readback failed"), -1);
     return rc;
     TMPT_GUARD_END
 }

@@ -2,7 +2,8 @@
 //   tmpt <width> <height> <spp> <objFile> [--seed row|pixel|sample] [--engine persistent|wavefront|mega]
 //        [--gpus N] [--device D] [--out output.png] [--aov PREFIX] [--denoise OUT.png [--shrink K]]
 //        [--adaptive TAU[,MIN[,STEP[,RADIUS]]]] [--spp-map OUT.png]
-//        [--twist DEG,FRAMES [--rebuild] [--temporal [--clip [GAMMA[,RADIUS[,NMAX]]]]]] [--octree host|device]
+//        [--twist DEG,FRAMES [--rebuild] [--temporal [--clip [GAMMA[,RADIUS[,NMAX]]]] [--guided [MIN[,STEP[,TAU[,CAP]]]]]]]
+//        [--octree host|device]
 // Defaults reproduce the reference: row seeding (main.cpp:204) and output.png.
 // Row seeding runs the speculative row engine on the persistent engine (every even RNG offset
 // of a window traced, the chain walked through it) and one lane per row with
@@ -39,6 +40,14 @@
 // --clip [GAMMA[,RADIUS[,NMAX]]] (with --temporal): the blend is tmpt_temporal_clip instead -- the history
 // clipped to GAMMA standard deviations of the frame's own (2 RADIUS + 1)^2 window, capped at NMAX (left out
 // or 0 = that call's defaults) -- into the same files.  Without --clip nothing changes.
+// --guided [MIN[,STEP[,TAU[,CAP]]]] (with --temporal): history-guided sampling.  Frame f sets sample_base to
+// f * CAP and runs the motion pass first, then the sample plan (tmpt_sample_plan) over the accumulated moments
+// of frame f-1 with the blend's n_max, then the guided render (tmpt_render_guided: spp_min MIN, left out or 0 = 2;
+// spp_step STEP and threshold TAU, left out or 0 / negative = the adaptive defaults; the cap CAP, left out or
+// 0 = spp) with its moments, then the blend: tmpt_temporal_clip with the moments frame as aux, or without --clip
+// tmpt_temporal twice, once on the colour frame and once on the moments frame.  The accumulated colour and
+// moments are the next frame's history; frame 0 has no prior.  --spp-map OUT.png then writes one map per frame,
+// OUT_000.png, ... (n_p / CAP as grey).  Without --guided nothing changes.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -229,7 +238,8 @@ static int render_adaptive_frame(const float* tris, int32_t n, const float box[6
 // --twist: see the head of this file.  tris: the n triangles of tmpt_load_obj (the last two are the floor).
 static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, const tmpt_render_desc* desc, int device,
                         double degrees, int frames, bool rebuild, bool temporal, const tmpt_temporal_clip_desc* clip,
-                        const char* out)
+                        const char* out, const tmpt_adaptive_desc* guided = nullptr, int cap = 0,
+                        const char* spp_map = nullptr)
 {
     tmpt_scene* scene = nullptr;
     if (tmpt_scene_create(tris, n, device, &scene)) return 1;
@@ -240,6 +250,19 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
     std::vector<float> prev, rad, acc, clipped;
     std::vector<tmpt_motion_pixel> mot, pmot;
     std::vector<uint8_t> timage;
+    // --guided: this frame's moments, their accumulation, the prior, the counts
+    std::vector<float> mom, macc, mout, prior;
+    std::vector<int32_t> cnt;
+    tmpt_render_desc gdesc = *desc;
+    if (guided) {
+        gdesc.spp = cap;
+        mom.resize((size_t)w * h * 4);
+        mout.resize((size_t)w * h * 4);
+        prior.resize((size_t)w * h * 4);
+        cnt.resize((size_t)w * h);
+    }
+    std::string map_stem(spp_map ? spp_map : "");
+    if (map_stem.size() > 4 && map_stem.compare(map_stem.size() - 4, 4, ".png") == 0) map_stem.resize(map_stem.size() - 4);
     if (temporal) {
         rad.resize((size_t)w * h * 4);
         mot.resize((size_t)w * h);
@@ -274,16 +297,68 @@ static int render_twist(const float* tris, int32_t n, const tmpt_camera* cam, co
         double ms = 0.0, cost = 0.0;
         uint64_t rays = 0;
         tmpt_stats st;
-        if (temporal) rc = tmpt_scene_set_option(scene, "sample_base", (double)f * desc->spp);
+        if (temporal) rc = tmpt_scene_set_option(scene, "sample_base", (double)f * (guided ? cap : desc->spp));
         if (!rc) rc = tmpt_scene_update(scene, cur.data(), n, rebuild ? TMPT_UPDATE_REBUILD : TMPT_UPDATE_REFIT);
         if (!rc) rc = tmpt_octree_bounds(bmin, bmax, box);
         if (!rc) rc = build_octree(scene, box);
         if (!rc) rc = tmpt_scene_get_option(scene, "update_ms", &ms);
         if (!rc) rc = tmpt_scene_get_option(scene, "bvh_cost", &cost);
+        tmpt_adaptive_info ginfo;
+        memset(&ginfo, 0, sizeof(ginfo));
+        if (!rc && guided) {  // motion, then the plan, then the guided render with its moments
+            tmpt_temporal_desc pd;
+            memset(&pd, 0, sizeof(pd));
+            pd.width = w;
+            pd.height = h;
+            pd.n_max = clip ? clip->n_max : 0.0f;
+            pd.sigma_depth = clip ? clip->sigma_depth : 0.0f;
+            rc = tmpt_render_motion(scene, cam, cam, f ? prev.data() : nullptr, n, desc, mot.data(), nullptr);
+            if (!rc && f) rc = tmpt_sample_plan(scene, &pd, mot.data(), pmot.data(), macc.data(), prior.data());
+            if (!rc)
+                rc = tmpt_render_guided(scene, cam, &gdesc, guided, f ? prior.data() : nullptr, rad.data(), mom.data(),
+                                        image.data(), cnt.data(), &ginfo, &rays);
+        }
         if (!rc && !temporal) rc = tmpt_render(scene, cam, desc, image.data(), &rays);
-        if (!rc && temporal) rc = tmpt_render_radiance(scene, cam, desc, rad.data(), image.data(), &rays);
+        if (!rc && temporal && !guided) rc = tmpt_render_radiance(scene, cam, desc, rad.data(), image.data(), &rays);
         if (!rc) rc = tmpt_get_stats(scene, &st);
-        if (!rc && temporal) {
+        if (!rc && guided) {  // the blend carries the moments along
+            if (f == 0) {
+                acc = rad;
+                macc = mom;
+                timage = image;
+            } else if (clip) {
+                tmpt_temporal_clip_desc cd = *clip;
+                cd.width = w;
+                cd.height = h;
+                clipped.resize(rad.size());
+                rc = tmpt_temporal_clip(scene, &cd, rad.data(), nullptr, mot.data(), pmot.data(), acc.data(), mom.data(),
+                                        macc.data(), mout.data(), clipped.data(), timage.data());
+                if (!rc) acc.swap(clipped), macc.swap(mout);
+            } else {
+                tmpt_temporal_desc td;
+                memset(&td, 0, sizeof(td));
+                td.width = w;
+                td.height = h;
+                rc = tmpt_temporal(scene, &td, rad.data(), mot.data(), pmot.data(), acc.data(), rad.data(), timage.data());
+                if (!rc) rc = tmpt_temporal(scene, &td, mom.data(), mot.data(), pmot.data(), macc.data(), mom.data(), nullptr);
+                if (!rc) acc.swap(rad), macc.swap(mom);
+            }
+            pmot = mot;
+            prev = cur;
+            if (!rc) {
+                printf("frame %d: guided, %d passes, %llu of %llu samples traced (%.1f%%)\n", f, ginfo.passes,
+                       (unsigned long long)ginfo.samples, (unsigned long long)w * h * cap,
+                       100.0 * ginfo.samples / ((double)w * h * cap));
+                if (spp_map) {
+                    std::vector<uint8_t> grey((size_t)w * h * 4, 255);
+                    for (size_t i = 0; i < (size_t)w * h; ++i)
+                        for (int c = 0; c < 3; ++c) grey[4 * i + c] = (uint8_t)((float)cnt[i] / (float)cap * 255.0f);
+                    char mname[32];
+                    snprintf(mname, sizeof(mname), "_%03d.png", f);
+                    rc = tmpt_write_png((map_stem + mname).c_str(), grey.data(), w, h);
+                }
+            }
+        } else if (!rc && temporal) {
             rc = tmpt_render_motion(scene, cam, cam, f ? prev.data() : nullptr, n, desc, mot.data(), nullptr);
             if (!rc && f == 0) {  // a history of length one
                 acc = rad;
@@ -330,7 +405,8 @@ int main(int argc, const char** argv)
         printf("Usage: tmpt [width] [height] [samplesPerPixel] [objFile] [--seed row|pixel|sample] "
                "[--engine persistent|wavefront|mega] [--gpus N] [--device D] [--out file.png] [--aov prefix] "
                "[--denoise file.png [--shrink k]] [--adaptive tau[,min[,step[,radius]]]] [--spp-map file.png] "
-               "[--twist deg,frames [--rebuild] [--temporal [--clip [gamma[,radius[,nmax]]]]]] [--octree host|device]\n"
+               "[--twist deg,frames [--rebuild] [--temporal [--clip [gamma[,radius[,nmax]]]] [--guided [min[,step[,tau[,cap]]]]]]] "
+               "[--octree host|device]\n"
                "  --octree: where the reference's octree is built, every time this run builds one (each frame of "
                "--twist too): host (default) or device (option octree_build)\n"
                "  --adaptive: radius 0..8 (default 0) keeps a pixel sampling while the variance test holds for "
@@ -342,7 +418,11 @@ int main(int argc, const char** argv)
                "  --temporal (with --twist, --seed sample): each frame draws its own samples (sample_base) and is "
                "blended with the reprojected accumulation of the frames before it, to <out>_temporal_000.png ...\n"
                "  --clip (with --temporal): the history is clipped to gamma standard deviations of the frame's own "
-               "(2 radius + 1)^2 window first (tmpt_temporal_clip; left out or 0 = its defaults)\n");
+               "(2 radius + 1)^2 window first (tmpt_temporal_clip; left out or 0 = its defaults)\n"
+               "  --guided (with --temporal): history-guided sampling -- per frame the motion pass, the sample plan "
+               "(tmpt_sample_plan) over the accumulated moments, the guided adaptive render (tmpt_render_guided: "
+               "spp_min min, default 2; step and tau, default the adaptive ones; cap samples at most, default spp) and "
+               "the blend with the moments carried along; --spp-map then writes one map per frame\n");
         return 1;
     }
     int w = atoi(argv[1]);
@@ -358,6 +438,11 @@ int main(int argc, const char** argv)
     const char* denoised = nullptr;
     const char* spp_map = nullptr;
     bool adaptive = false, twist = false, rebuild = false, temporal = false, have_shrink = false, clip = false;
+    bool guided = false;
+    int guided_cap = 0;
+    tmpt_adaptive_desc gd;
+    memset(&gd, 0, sizeof(gd));
+    gd.threshold = -1.0f;
     tmpt_temporal_clip_desc cd;
     memset(&cd, 0, sizeof(cd));
     float shrink = 0.0f;
@@ -427,6 +512,14 @@ int main(int argc, const char** argv)
                 return 1;
             }
         }
+        else if (!strcmp(argv[i], "--guided")) {
+            guided = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0 &&
+                sscanf(argv[++i], "%d,%d,%f,%d", &gd.spp_min, &gd.spp_step, &gd.threshold, &guided_cap) < 1) {
+                printf("ERROR: invalid --guided argument '%s' (MIN[,STEP[,TAU[,CAP]]])\n", argv[i]);
+                return 1;
+            }
+        }
         else { printf("ERROR: unknown option '%s'\n", argv[i]); return 1; }
     }
     float* tris = nullptr;
@@ -451,14 +544,21 @@ int main(int argc, const char** argv)
         printf("ERROR: --adaptive needs --seed sample, the persistent engine and one device (--gpus 1)\n");
         return 1;
     }
-    if (spp_map && !adaptive) { printf("ERROR: --spp-map needs --adaptive\n"); return 1; }
+    if (guided && !temporal) { printf("ERROR: --guided needs --temporal\n"); return 1; }
+    if (guided) {
+        if (gd.spp_min == 0) gd.spp_min = 2;
+        if (gd.threshold == 0.0f) gd.threshold = -1.0f;
+        if (guided_cap == 0) guided_cap = spp;
+        if (guided_cap < 2 || guided_cap > 1024) { printf("ERROR: --guided: CAP outside 2 .. 1024\n"); return 1; }
+    }
+    if (spp_map && !adaptive && !guided) { printf("ERROR: --spp-map needs --adaptive\n"); return 1; }
     if (rebuild && !twist) { printf("ERROR: --rebuild needs --twist\n"); return 1; }
     if (temporal && (!twist || rebuild || seed != TMPT_SEED_SAMPLE || engine != TMPT_ENGINE_PERSISTENT)) {
         printf("ERROR: --temporal needs --twist without --rebuild, --seed sample and the persistent engine\n");
         return 1;
     }
     if (clip && !temporal) { printf("ERROR: --clip needs --temporal\n"); return 1; }
-    if (temporal && (long long)(twist_frames - 1) * spp > 64512) {
+    if (temporal && (long long)(twist_frames - 1) * (guided ? guided_cap : spp) > 64512) {
         printf("ERROR: --temporal: (FRAMES - 1) * spp must not exceed 64512 (option sample_base)\n");
         return 1;
     }
@@ -489,7 +589,8 @@ int main(int argc, const char** argv)
     float box[6];
     tmpt_octree_bounds(bmin, bmax, box);
     if (twist) {  // the frames of one scene handle, each written by render_twist
-        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, temporal, clip ? &cd : nullptr, out)) {
+        if (render_twist(tris, n, &cam, &desc, device, twist_deg, twist_frames, rebuild, temporal, clip ? &cd : nullptr, out,
+                         guided ? &gd : nullptr, guided_cap, spp_map)) {
             printf("ERROR: %s\n", tmpt_last_error());
             return 1;
         }

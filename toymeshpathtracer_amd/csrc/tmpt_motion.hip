@@ -22,6 +22,9 @@
 // clipped to the mean +- gamma * sigma of the (2R+1)^2 window of the statistics
 // frame, which the block stages in LDS with its halo; optionally a second (aux)
 // frame through the same taps and blend factor.
+//
+// k_sample_plan (tmpt_sample_plan): k_temporal's fetch over the accumulated
+// moments frame, then the per-pixel prior of tmpt_render_guided.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -289,6 +292,92 @@ int temporal(Scene& s, const tmpt_temporal_desc* d, const float4* d_cur, const t
     const hipError_t se = hipStreamSynchronize(s.stream);
     if (se != hipSuccess) {
         set_error(std::string("tmpt_temporal: ") + hipGetErrorString(se));
+        return -1;
+    }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    s.render_ms = ms;
+    return 0;
+}
+
+// ---------------------------------------------------------------- the sample plan
+// k_sample_plan (tmpt_sample_plan): k_temporal's fetch, statement for statement,
+// over the accumulated moments frame, then the prior the guided render's test
+// reads -- {history luminance, the history's share of the blended variance, this
+// frame's blend factor, history length}.  One lane per pixel, a block's 32 x 8
+// pixels as k_temporal; no colour frame is read.  A kernel of its own, so that
+// k_temporal and k_temporal_clip keep their code as it is.
+__global__ void __launch_bounds__(256) k_sample_plan(const float4* __restrict__ motion,
+                                                     const float4* __restrict__ pmotion,
+                                                     const float4* __restrict__ hist, float4* __restrict__ out,
+                                                     TemporalArgs a)
+{
+    const int x = (int)blockIdx.x * kTpTX + (int)threadIdx.x % kTpTX;
+    const int y = (int)blockIdx.y * kTpTY + (int)threadIdx.x / kTpTX;
+    if (x >= a.W || y >= a.H) return;
+    const int64_t pi = (int64_t)y * a.W + x;
+    const float4 m0 = motion[2 * pi], m1 = motion[2 * pi + 1];  // {px, py, depth, depth_prev}, {u, v, tri, flags}
+    float4 pr = make_float4(0.0f, 0.0f, 1.0f, 0.0f);            // the null prior
+    const float mpx = m0.x, mpy = m0.y, dprev = m0.w;
+    const bool valid = (__float_as_uint(m1.w) & 2u) != 0 && mpx >= -1.0f && mpx < (float)a.W + 1.0f && mpy >= -1.0f &&
+                       mpy < (float)a.H + 1.0f;
+    if (valid) {
+        const float fx = mpx - 0.5f, fy = mpy - 0.5f;
+        const float x0 = floorf(fx), y0 = floorf(fy);
+        const float ax = fx - x0, ay = fy - y0;
+        const int ix = (int)x0, iy = (int)y0;
+        f3 asum = mk(0.0f, 0.0f, 0.0f);
+        float nsum = 0.0f, wsum = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int qx = ix + i, qy = iy + j;
+                const float wgt = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+                if (qx < 0 || qx >= a.W || qy < 0 || qy >= a.H) continue;
+                const int64_t q = (int64_t)qy * a.W + qx;
+                const float4 p0 = pmotion[2 * q], p1 = pmotion[2 * q + 1];
+                if (!(__float_as_uint(p1.w) & 1u)) continue;
+                if (fabsf(p0.z - dprev) > a.sigma_depth * dprev) continue;
+                const float4 hq = hist[q];
+                asum = asum + mk(hq.x * wgt, hq.y * wgt, hq.z * wgt);
+                nsum = nsum + hq.w * wgt;
+                wsum = wsum + wgt;
+            }
+        }
+        if (wsum > 0.0f) {
+            const float hY = asum.x / wsum, h2 = asum.y / wsum, hz = asum.z / wsum, nh = nsum / wsum;
+            const float ne = nh / hz;
+            const float vh = fmaxf(0.0f, h2 - hY * hY) / fmaxf(ne - 1.0f, 1.0f);
+            const float n = fminf(nh + 1.0f, a.n_max);
+            const float al = 1.0f / n, be = 1.0f - al;
+            pr = make_float4(hY, (be * be) * vh, al, nh);
+        }
+    }
+    out[pi] = pr;
+}
+
+// d (checked by the caller) holds the resolved n_max and sigma_depth; every
+// pointer on the device; d_out overlaps no input (the caller's check).
+int sample_plan(Scene& s, const tmpt_temporal_desc* d, const tmpt_motion_pixel* d_motion,
+                const tmpt_motion_pixel* d_pmotion, const float4* d_hist, float4* d_out)
+{
+    tmpt_render_desc wd{};
+    wd.flags = d->flags;
+    wd.wait_stream = d->wait_stream;
+    if (int rc = wait_caller_stream(s, &wd, "tmpt_sample_plan")) return rc;
+    if (ensure_counters(s)) return -1;  // the scene's timing events
+    hipEvent_t e0 = s.render_ev[0], e1 = s.render_ev[1];
+    TMPT_HIP(hipEventRecord(e0, s.stream));
+    const TemporalArgs a{d->width, d->height, d->n_max, d->sigma_depth};
+    const dim3 grid((unsigned)((d->width + kTpTX - 1) / kTpTX), (unsigned)((d->height + kTpTY - 1) / kTpTY));
+    k_sample_plan<<<grid, 256, 0, s.stream>>>(reinterpret_cast<const float4*>(d_motion),
+                                              reinterpret_cast<const float4*>(d_pmotion), d_hist, d_out, a);
+    TMPT_HIP(hipGetLastError());
+    (void)hipEventRecord(e1, s.stream);
+    const hipError_t se = hipStreamSynchronize(s.stream);
+    if (se != hipSuccess) {
+        set_error(std::string("tmpt_sample_plan: ") + hipGetErrorString(se));
         return -1;
     }
     float ms = 0;

@@ -170,10 +170,13 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
 // tmpt_adaptive.hip: adaptive sampling (tmpt_render_adaptive) of one shard; ad
 // holds the resolved spp_min, spp_step, threshold and radius (checked by the caller),
 // the three tiles are device pointers or null; d_mom: the moments tile of
-// tmpt_render_moments (`what` then names that call in errors), or null
+// tmpt_render_moments (`what` then names that call in errors), or null; d_prior:
+// the prior tile of tmpt_render_guided (the tile's float4 in slot order), or null
+// (the update kernels' no-prior instantiations: the calls as they were)
 int render_adaptive(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, const tmpt_adaptive_desc* ad,
                     float4* d_f32, uint32_t* d_u8, int32_t* d_spp, tmpt_adaptive_info* info, uint64_t* ray_count,
-                    float4* d_mom = nullptr, const char* what = "tmpt_render_adaptive");
+                    float4* d_mom = nullptr, const char* what = "tmpt_render_adaptive",
+                    const float4* d_prior = nullptr);
 
 // tmpt_denoise.hip: the a-trous filter (tmpt_denoise) over a whole frame, every
 // pointer on the device; d (checked by the caller) holds the resolved levels,
@@ -202,5 +205,10 @@ int temporal_clip(Scene& s, const tmpt_temporal_clip_desc* d, const float4* d_cu
                   const tmpt_motion_pixel* d_motion, const tmpt_motion_pixel* d_pmotion, const float4* d_hist,
                   const float4* d_aux_cur, const float4* d_aux_hist, float4* d_aux_out, float4* d_out32,
                   uint32_t* d_out8);
+// tmpt_motion.hip: the sample plan (tmpt_sample_plan) over a whole frame, every
+// pointer on the device; d holds the resolved n_max and sigma_depth; d_out
+// overlaps no input
+int sample_plan(Scene& s, const tmpt_temporal_desc* d, const tmpt_motion_pixel* d_motion,
+                const tmpt_motion_pixel* d_pmotion, const float4* d_hist, float4* d_out);
 
 }  // namespace tmpt
