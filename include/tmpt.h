@@ -69,7 +69,11 @@ extern "C" {
                               tmpt_render_multi -- no struct above changed;
                               still 9, additive: history-guided sampling -- tmpt_sample_plan (the
                               accumulated moments reprojected into a per-pixel prior) and
-                              tmpt_render_guided (tmpt_render_moments with that prior in its test) */
+                              tmpt_render_guided (tmpt_render_moments with that prior in its test);
+                              still 9, additive: device-resident batched queries -- tmpt_scene_hit_device with
+                              tmpt_hit_desc, the render options query_sort, query_top, query_max, query_chunk and
+                              query_grid, and the check hooks tmpt_query_keys and tmpt_query_plan -- no struct
+                              above changed */
 
 typedef struct tmpt_scene tmpt_scene; /* opaque, device-resident */
 
@@ -451,6 +455,24 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *   motion_tile      tmpt_render_motion: the 64 pixels a wave takes at a time -- 1: an 8 x 8 block,
  *                    0: 64 consecutive pixels of a row, -1 (default): the measured choice (the row); the
  *                    records are the same for every value
+ *   query_sort       tmpt_scene_hit_device: 1 = the rays of a batch are traced in the order of a 24-bit key of
+ *                    their origin's cell and direction (tmpt_query_keys states it), sorted on the device in
+ *                    chunks of query_chunk rays; 0 = in the order given; -1 (default): the measured rule
+ *                    ("Device-resident queries": off).  The answers are the same
+ *                    for every value
+ *   query_top        tmpt_scene_hit_device: 1 = the top levels of the BVH are read from an LDS copy, 0 = from
+ *                    global memory, -1 (default): the measured choice.  The answers are the same for every value
+ *   query_max        tmpt_scene_hit_device: cap in bytes on the scene's query scratch (overflow stacks, sort
+ *                    buffers; kept by the scene between calls; 0 = half of the free device memory).  A call
+ *                    whose scratch would pass it returns -12 with a message and changes nothing
+ *   query_chunk      test hook (2^22): rays per sorted chunk, 64 .. 2^22
+ *   query_grid       test hook (0 = the occupancy grid): cap on the blocks a query launch has
+ *   query_legacy     tool hook (0): 1 = tmpt_scene_hit_device runs tmpt_scene_hit's kernel on the caller's
+ *                    device data (d_hits required, d_uv must be NULL), for kernel-to-kernel timing
+ *   query_ms, query_sort_ms, query_chunks, query_sorted
+ *                    read-only, of the last tmpt_scene_hit_device: its device time between two events on the
+ *                    scene's stream; the keys' and the sorts' share of it (timed on the first 32 chunks, their
+ *                    mean taken for the rest); the chunks run (1 when unsorted); 1 if it sorted
  *   octree_build     tmpt_scene_build_octree: where the octree is built -- 0 or "host" (default): the
  *                    recursion on the host, uploaded; 1 or "device": a level-order build on the scene's
  *                    stream from the triangles the scene keeps on the device, nothing uploaded.  The
@@ -562,6 +584,67 @@ int tmpt_scene_hit(const tmpt_scene* scene, const float* rays, int64_t n, float 
  * dir.xyz, tmin, tmax}.  t is accepted in [tmin, tmax]. */
 int tmpt_scene_hit_ranged(const tmpt_scene* scene, const float* rays8, int64_t n, int32_t any_hit,
                           float* hits, int32_t* ids);
+
+/* The same queries on data that lives on the device: nothing is uploaded, copied back or
+ * allocated per call.  d_rays = n x 6 floats {orig.xyz, dir.xyz} with desc's one [tmin, tmax]
+ * (ranged = 0), or n x 8 {orig.xyz, dir.xyz, tmin, tmax} (ranged = 1, desc's tmin / tmax not read).
+ * All four pointers are device pointers on the scene's device, 4-byte aligned (a d_rays that is
+ * 16-byte aligned takes the wider loads).
+ *   d_ids[i]       as tmpt_scene_hit's ids[i]
+ *   d_hits[7 i..]  as tmpt_scene_hit's hits, written only where d_ids[i] >= 0 and untouched elsewhere;
+ *                  may be NULL: no hit record is formed
+ *   d_uv[2 i..]    (may be NULL) Moller-Trumbore's (u, v) of the hit (maths.cpp:339-380; the record's
+ *                  position is v0 (1 - u - v) + v1 u + v2 v), written where d_ids[i] >= 0, so a caller
+ *                  can interpolate vertex attributes without intersecting again
+ * The answers are tmpt_scene_hit's ray for ray and bit for bit -- closest ids, hit records, t bits;
+ * with the octree its answers for ties, root misses, cracks and flat triangles -- whatever the
+ * options query_sort, query_top, query_chunk and query_grid say, and the Domain paragraph above applies
+ * unchanged.  any_hit: only the bit d_ids[i] >= 0 is specified, as there; in addition, where a hit is
+ * reported, the record and (u, v) are those of triangle d_ids[i] for that ray.
+ * The work runs on the scene's own stream, after the work enqueued on desc->wait_stream when
+ * TMPT_FLAG_WAIT_STREAM is set, and the call returns when it is complete on the device, as the renders
+ * do.  tmpt_get_stats afterwards reports tie_queries, root_misses and crack_queries as after
+ * tmpt_scene_hit.  The scratch (overflow stacks; with query_sort the keys, the permutation and the
+ * sort's buffers) belongs to the scene, grows on demand, is reused and is freed with the scene: the
+ * option live_device_objects does not move when a call is repeated with the same arguments.  The
+ * progressive state, the octree and every render buffer are left alone; like tmpt_render_aov the
+ * call may run between two progressive passes.
+ * -22 with a message, checked in this order before any device call: a null scene; a null desc;
+ * n < 0; n > 0 with a null d_rays or d_ids; a flag other than TMPT_FLAG_WAIT_STREAM; ranged or
+ * any_hit outside 0 / 1.  A non-finite tmin or tmax (ranged = 0) is accepted, as tmpt_scene_hit
+ * accepts it: the range is compared as given (a NaN bound accepts no hit, tmax = +inf bounds nothing).
+ * n = 0 returns 0 and launches nothing.  -12: the scratch does not fit (option query_max); the scene
+ * is unchanged. */
+typedef struct {
+    int64_t  n;            /* rays */
+    int32_t  ranged;       /* 0: rays n x 6 and one [tmin, tmax]; 1: rays n x 8, tmin / tmax not read */
+    int32_t  any_hit;
+    float    tmin, tmax;
+    int32_t  flags;        /* TMPT_FLAG_WAIT_STREAM only; any other bit: -22 */
+    int32_t  reserved0;
+    uint64_t wait_stream;
+    int32_t  reserved[4];
+} tmpt_hit_desc;
+int tmpt_scene_hit_device(tmpt_scene* scene, const tmpt_hit_desc* desc, const float* d_rays,
+                          int32_t* d_ids, float* d_hits /* may be NULL */, float* d_uv /* may be NULL */);
+/* Check hook (host only, no device): the sort key of option query_sort for n rays of `stride`
+ * floats (6 or 8: {orig.xyz, dir.xyz[, tmin, tmax]}) and box = {min.xyz, max.xyz}, the root box of
+ * the scene's BVH.  Every operation is float32 and rounds once; per axis a:
+ *   inv[a] = 32.0f / fmaxf(box.max[a] - box.min[a], 1e-30f)
+ *   c[a]   = (int)fminf(fmaxf((o[a] - box.min[a]) * inv[a], 0.0f), 31.0f)
+ *   q[a]   = (int)fminf(fmaxf((d[a] + 1.0f) * 4.0f, 0.0f), 7.0f)
+ *   key    = morton3(c.x, c.y, c.z) << 9 | q.x << 6 | q.y << 3 | q.z
+ * (morton3 interleaves with x in the lowest bit of each triple: 24 bits in all); a ray with a NaN
+ * anywhere in its origin or direction gets 0xFFFFFF and sorts last.  The device's key kernel
+ * compiles the same function (csrc/tmpt_query_key.h).  -22 with a message, checked in this order:
+ * n < 0; a null rays or keys with n > 0; a stride other than 6 or 8; a null box. */
+int tmpt_query_keys(const float* rays, int64_t n, int32_t stride /* 6 or 8 */, const float box[6], uint32_t* keys);
+/* Check hook (host only, no device): the sizes of one tmpt_scene_hit_device call of n rays -- sorted
+ * (0 / 1), chunk = option query_chunk, grid_cap = option query_grid, resident = the blocks the device
+ * holds at once: out = {chunks, rays per chunk, rays of the last chunk, blocks of the largest
+ * launch, bytes of overflow stacks, bytes of sort buffers}.  -22: n < 0, sorted outside 0 / 1, a
+ * chunk outside 64 .. 2^22, grid_cap < 0, resident < 1, a null out. */
+int tmpt_query_plan(int64_t n, int32_t sorted, int64_t chunk, int64_t grid_cap, int64_t resident, int64_t out[6]);
 
 /* tbb::parallel_for(rows, TraceImageBody) (main.cpp:329-331, 180-246):
  * renders desc's shard into rgba_out (tmpt_tile_rows(desc) * width * 4 bytes).

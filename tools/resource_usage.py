@@ -24,7 +24,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "toymeshpathtracer_amd", "csrc")
 RENDER_UNITS = ("tmpt_mega.hip", "tmpt_hitscene.hip", "tmpt_wavefront.hip", "tmpt_rows.hip", "tmpt_render.hip",
-                "tmpt_shadow.hip")
+                "tmpt_shadow.hip", "tmpt_query.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero",
          f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}", "-O2", "-fno-slp-vectorize"]

@@ -7,6 +7,7 @@
 #  2. TSan: tools/san_driver.cpp, the same host code and the oracle linked into one
 #     program built with -fsanitize=thread, every threaded path run and checked against
 #     its sequential form.
+#  3. ASan + UBSan on that driver, and on tools/san_query.cpp (the device-resident queries' host side).
 # Usage: tools/san_check.sh [log]   (exit status 0 = clean)
 set -o pipefail
 cd "$(dirname "$0")/.."
@@ -39,5 +40,7 @@ TSAN_OPTIONS=halt_on_error=1:second_deadlock_stack=1 tools/_bin/san_driver_tsan 
 echo "== 3. ASan + UBSan: the same driver"
 build_driver tools/_bin/san_driver_asan -fsanitize=address,undefined -fno-sanitize-recover=undefined || exit 1
 ASAN_OPTIONS=abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 tools/_bin/san_driver_asan data 2>&1 || exit 1
+echo "== 4. ASan + UBSan: tools/san_query.cpp (the host side of tmpt_scene_hit_device, tmpt_query_keys, tmpt_query_plan)"
+tools/san_query.sh 2>&1 || exit 1
 echo "== clean"
 } > "$LOG" 2>&1

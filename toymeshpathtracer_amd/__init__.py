@@ -19,6 +19,8 @@ reference                   here
 (none: adaptive sampling)   :meth:`Scene.trace_adaptive` (per-pixel sample counts by a variance test)
 (none: noise-aware filter)  :meth:`Scene.trace_moments` (the frame with each pixel's luminance moments) and
                             :meth:`Scene.denoise_moments` (the filter steered by them: wavelet shrinkage)
+(none: device queries)      :meth:`Scene.hit_scene_device` (``HitScene`` over a torch tensor of rays on the scene's
+                            device: ids, hit records and (u, v) as tensors, no host round trip)
 (none: scene update)        :meth:`Scene.update` (new triangles in place: a device BVH refit, or a rebuild)
 (none: temporal)            :meth:`Scene.trace_motion` (:data:`MOTION_DTYPE` records: where each pixel's surface
                             was one frame ago) and :meth:`Scene.temporal` (the reprojected, accumulated history);
@@ -42,7 +44,7 @@ __all__ = [
     "Camera", "Scene", "Hit", "RenderStats", "load_scene", "write_png", "device_count",
     "SEED_ROW", "SEED_PIXEL", "SEED_SAMPLE", "ENGINE_WAVEFRONT", "ENGINE_MEGAKERNEL", "ENGINE_PERSISTENT", "lib_path", "TmptError",
     "tile_rows", "tile_row_to_y", "render_multi", "octree_bounds", "octree_digest", "octree_flags", "octree_arrays",
-    "AOV_DTYPE", "MOTION_DTYPE",
+    "AOV_DTYPE", "MOTION_DTYPE", "query_keys", "query_plan",
 ]
 
 SEED_ROW, SEED_PIXEL, SEED_SAMPLE = 0, 1, 2
@@ -127,6 +129,12 @@ class _TemporalClipDesc(ctypes.Structure):
                 ("n_max", ctypes.c_float), ("sigma_depth", ctypes.c_float), ("gamma", ctypes.c_float),
                 ("radius", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("wait_stream", ctypes.c_uint64),
                 ("reserved", ctypes.c_int32 * 4)]
+
+
+class _HitDesc(ctypes.Structure):  # tmpt_hit_desc, 56 bytes
+    _fields_ = [("n", ctypes.c_int64), ("ranged", ctypes.c_int32), ("any_hit", ctypes.c_int32),
+                ("tmin", ctypes.c_float), ("tmax", ctypes.c_float), ("flags", ctypes.c_int32),
+                ("reserved0", ctypes.c_int32), ("wait_stream", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
 class _AdaptiveDesc(ctypes.Structure):
@@ -235,7 +243,7 @@ EXPORTS = ("tmpt_load_obj", "tmpt_free", "tmpt_camera_init", "tmpt_camera_for_sc
            "tmpt_scene_dump_bvh", "tmpt_radix_sort", "tmpt_camera_rays", "tmpt_render_adaptive",
            "tmpt_scene_update", "tmpt_render_motion", "tmpt_temporal", "tmpt_render_moments",
            "tmpt_denoise_moments", "tmpt_temporal_clip", "tmpt_scene_dump_octree", "tmpt_octree_arrays",
-           "tmpt_sample_plan", "tmpt_render_guided")
+           "tmpt_sample_plan", "tmpt_render_guided", "tmpt_scene_hit_device", "tmpt_query_keys", "tmpt_query_plan")
 
 
 def _check(rc: int, what: str) -> None:
@@ -266,6 +274,33 @@ def fastdiv(divisor: int, x: np.ndarray):
     ms = np.zeros(2, dtype=np.uint32)
     _check(fn(divisor, x.ctypes.data, x.size, out.ctypes.data, ms.ctypes.data), "tmpt_fastdiv")
     return out, (int(ms[0]), int(ms[1]))
+
+
+def query_keys(rays, box) -> np.ndarray:
+    """The sort key of option ``query_sort`` (tmpt_query_keys, host only; include/tmpt.h
+    states it) for rays float32 [n, 6] or [n, 8] and box = the six floats {min.xyz,
+    max.xyz} of the BVH's root box: uint32 [n], 24 bits each, 0xFFFFFF for a ray with a
+    NaN in its origin or direction."""
+    fn = _sig("tmpt_query_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_void_p])
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim != 2 or rays.shape[1] not in (6, 8):
+        raise ValueError("query_keys: rays [n, 6] or [n, 8]")
+    box = np.ascontiguousarray(box, np.float32).reshape(-1)
+    if box.size != 6:
+        raise ValueError("query_keys: box = {min.xyz, max.xyz}")
+    keys = np.zeros(rays.shape[0], np.uint32)
+    _check(fn(rays.ctypes.data, rays.shape[0], rays.shape[1], box.ctypes.data, keys.ctypes.data), "query_keys")
+    return keys
+
+
+def query_plan(n: int, sorted: bool, chunk: int = 1 << 22, grid_cap: int = 0, resident: int = 1024) -> dict:
+    """The sizes of one :meth:`Scene.hit_scene_device` call (tmpt_query_plan, host only)."""
+    fn = _sig("tmpt_query_plan", ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_void_p])
+    out = np.zeros(6, np.int64)
+    _check(fn(n, int(sorted), chunk, grid_cap, resident, out.ctypes.data), "query_plan")
+    return dict(zip(("chunks", "chunk_n", "last_n", "grid", "ovf_bytes", "sort_bytes"), (int(v) for v in out)))
 
 
 def device_count() -> int:
@@ -603,6 +638,80 @@ class Scene:
             _check(_scene_hit(self._h, _fp(rays), n, t_min, t_max, int(any_hit), _fp(hits),
                               ids.ctypes.data_as(_i32p)), "hit_scene")
         return ids, hits
+
+    def hit_scene_device(self, rays, t_min: Optional[float] = None, t_max: Optional[float] = None,
+                         any_hit: bool = False, hits: bool = True, uv: bool = False, out=None,
+                         wait_stream="current"):
+        """:meth:`hit_scene_batch` on a torch tensor that lives on the scene's device
+        (tmpt_scene_hit_device): nothing is copied to or from the host and nothing
+        is allocated by the library per call.  ``rays``: a contiguous float32 tensor
+        [n, 6] with one [t_min, t_max], or [n, 8] (the range per ray) with both
+        ``None``, on ``cuda:<scene.device>``; anything else is a ``ValueError`` --
+        no silent copy or cast.  Returns ``(ids, hits, uv)`` on that device: ids
+        int32 [n]; hits float32 [n, 7] (pos, normal, t), zero-initialised, or
+        ``None`` (``hits=False``); uv float32 [n, 2], Moller-Trumbore's (u, v) of
+        the hit, zero-initialised, or ``None`` (``uv=False``).  Rows of rays that
+        missed are not written.  ``out=(ids, hits, uv)``: preallocated tensors of
+        those shapes (``None`` for either optional one); they decide which outputs
+        are made.  The answers are :meth:`hit_scene_batch`'s bit for bit, whatever
+        the options ``query_sort`` / ``query_top`` say.  The work starts after the
+        work enqueued on ``wait_stream`` ("current": torch's current stream on the
+        scene's device) and the call returns when it is complete on the device."""
+        what = "hit_scene_device"
+        if torch is None:
+            raise TmptError(f"{what}: needs torch (tensors on the scene's device); hit_scene_batch takes numpy arrays")
+        if (t_min is None) != (t_max is None):
+            raise ValueError(f"{what}: give both t_min and t_max, or neither (ranged rays [n, 8])")
+        ranged = t_min is None
+        dev = torch.device("cuda", self.device)
+
+        def tensor(t, name, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}: {name} must be a torch tensor, not {type(t).__name__}")
+            if t.device != dev:
+                raise ValueError(f"{what}: {name} is on {t.device}, the scene is on {dev}")
+            if t.dtype != dtype:
+                raise ValueError(f"{what}: {name} must be {dtype}, not {t.dtype}")
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{what}: {name} must have shape {list(shape)}, not {list(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous")
+
+        tensor(rays, "rays", torch.float32, None)
+        if rays.dim() != 2 or rays.shape[1] != (8 if ranged else 6):
+            raise ValueError(f"{what}: rays must have shape [n, {8 if ranged else 6}] "
+                             f"({'ranged' if ranged else 'with t_min and t_max'}), not {list(rays.shape)}")
+        n = int(rays.shape[0])
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError(f"{what}: out = (ids, hits, uv)")
+            ids, h, w = out
+            if ids is None:
+                raise ValueError(f"{what}: out's ids must be a tensor")
+            tensor(ids, "out ids", torch.int32, (n,))
+            if h is not None:
+                tensor(h, "out hits", torch.float32, (n, 7))
+            if w is not None:
+                tensor(w, "out uv", torch.float32, (n, 2))
+        else:
+            ids = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            h = torch.zeros((n, 7), dtype=torch.float32, device=dev) if hits else None
+            w = torch.zeros((n, 2), dtype=torch.float32, device=dev) if uv else None
+        fn = _sig("tmpt_scene_hit_device", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_HitDesc), ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
+        d = _HitDesc()
+        d.n, d.ranged, d.any_hit = n, int(ranged), int(bool(any_hit))
+        d.tmin, d.tmax = (0.0, 0.0) if ranged else (t_min, t_max)
+        ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+        if ws is not None:
+            d.flags |= FLAG_WAIT_STREAM
+            d.wait_stream = int(ws)
+        _check(fn(self._h, ctypes.byref(d), rays.data_ptr(), ids.data_ptr(), None if h is None else h.data_ptr(),
+                  None if w is None else w.data_ptr()), what)
+        return ids, h, w
+
+    #: the sort key of option ``query_sort`` (:func:`query_keys`; host only, needs no scene)
+    query_keys = staticmethod(query_keys)
 
     def hit_scene(self, orig, direction, t_min: float, t_max: float) -> Tuple[int, Optional[Hit]]:
         """Same contract as the reference: returns (-1, None) on a miss and

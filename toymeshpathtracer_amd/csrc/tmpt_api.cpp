@@ -16,6 +16,7 @@
 #include "tmpt_internal.h"
 #include "tmpt_traverse.h"
 #include "tmpt_render.h"
+#include "tmpt_query_key.h"
 
 namespace tmpt {
 
@@ -32,6 +33,9 @@ int render(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t
            uint64_t* ray_count, float4* d_sums = nullptr);
 // tmpt_render.hip: the camera pre-pass alone, its entries copied to host memory (tmpt_camera_rays)
 int camera_rays(Scene& s, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* out);
+int query_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
+                int32_t* d_ids, float* d_hits, float* d_uv, bool wait, uint64_t wait_stream);
+int query_wait(Scene& s, uint64_t wait_stream);
 int intersect_batch(Scene& s, const float* d_rays, int64_t n, float tmin, float tmax, bool any, bool ranged,
                     float* d_hits, int32_t* d_ids);
 
@@ -158,6 +162,12 @@ const OptionDef kOptions[] = {
     {"octree_build", false, 0, 1, &Options::octree_build, nullptr, nullptr},
     {"octree_dev_max", false, 0, 1e18, nullptr, nullptr, &Options::octree_dev_max},
     {"denoise_lds", false, -1, 1, &Options::denoise_lds, nullptr, nullptr},
+    {"query_sort", false, -1, 1, &Options::query_sort, nullptr, nullptr},
+    {"query_top", false, -1, 1, &Options::query_top, nullptr, nullptr},
+    {"query_max", false, 0, 1e18, nullptr, nullptr, &Options::query_max},
+    {"query_chunk", false, 64, 1 << 22, &Options::query_chunk, nullptr, nullptr},
+    {"query_grid", false, 0, 1 << 20, &Options::query_grid, nullptr, nullptr},
+    {"query_legacy", false, 0, 1, &Options::query_legacy, nullptr, nullptr},
     {"motion_tile", false, -1, 1, &Options::motion_tile, nullptr, nullptr},
 };
 
@@ -756,6 +766,11 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
         *value = (double)g_live_device_objects.load();
         return 0;
     }
+    // read-only, of the last tmpt_scene_hit_device: device time, the keys + sort share, chunks, whether it sorted
+    if (key && strcmp(key, "query_ms") == 0) return (*value = h->s.query_ms, 0);
+    if (key && strcmp(key, "query_sort_ms") == 0) return (*value = h->s.query_sort_ms, 0);
+    if (key && strcmp(key, "query_chunks") == 0) return (*value = (double)h->s.query_chunks, 0);
+    if (key && strcmp(key, "query_sorted") == 0) return (*value = (double)h->s.query_sorted, 0);
     if (key && strcmp(key, "bvh_cost") == 0) {  // read-only: the tree's surface-area cost, cached until an update
         Scene& s = const_cast<tmpt_scene*>(h)->s;
         if (!s.cost_known) {
@@ -816,6 +831,80 @@ int tmpt_scene_hit_ranged(const tmpt_scene* hc, const float* rays8, int64_t n, i
 {
     TMPT_GUARD_BEGIN
     return scene_hit(hc, rays8, n, 0.0f, 0.0f, true, any_hit, hits, ids);
+    TMPT_GUARD_END
+}
+
+int tmpt_scene_hit_device(tmpt_scene* h, const tmpt_hit_desc* d, const float* d_rays, int32_t* d_ids, float* d_hits,
+                          float* d_uv)
+{
+    TMPT_GUARD_BEGIN
+    if (!h) return bad("tmpt_scene_hit_device: null scene");
+    if (!d) return bad("tmpt_scene_hit_device: null descriptor");
+    if (d->n < 0) return bad("tmpt_scene_hit_device: n < 0");
+    if (d->n > 0 && (!d_rays || !d_ids)) return bad("tmpt_scene_hit_device: null d_rays or d_ids");
+    if (d->flags & ~TMPT_FLAG_WAIT_STREAM) return bad("tmpt_scene_hit_device: unknown flag (TMPT_FLAG_WAIT_STREAM only)");
+    if ((d->ranged != 0 && d->ranged != 1) || (d->any_hit != 0 && d->any_hit != 1))
+        return bad("tmpt_scene_hit_device: ranged and any_hit are 0 or 1");
+    // (a non-finite tmin / tmax is accepted, as tmpt_scene_hit accepts it)
+    if (d->n == 0) return 0;
+    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    Scene& s = h->s;
+    TMPT_HIP(hipSetDevice(s.device));
+    const bool wait = (d->flags & TMPT_FLAG_WAIT_STREAM) != 0;  // order after the caller's stream
+    int rc;
+    if (s.opt.query_legacy) {  // k_intersect on the caller's data (tools/hit_device_time.py)
+        if (!d_hits || d_uv) return bad("tmpt_scene_hit_device: query_legacy takes d_hits and no d_uv");
+        if (wait && query_wait(s, d->wait_stream)) return -1;
+        for (auto& e : s.query_ev) TMPT_HIP(e.ensure());
+        TMPT_HIP(hipEventRecord(s.query_ev[0], s.stream));
+        rc = intersect_batch(s, d_rays, d->n, d->tmin, d->tmax, d->any_hit != 0, d->ranged != 0, d_hits, d_ids);
+        if (!rc) TMPT_HIP(hipEventRecord(s.query_ev[1], s.stream));
+        if (!rc && hipStreamSynchronize(s.stream) != hipSuccess) rc = (set_error("tmpt_scene_hit_device: kernel failed"), -1);
+        if (!rc) {
+            float ms = 0.0f;
+            TMPT_HIP(hipEventElapsedTime(&ms, s.query_ev[0], s.query_ev[1]));
+            s.query_ms = ms, s.query_sort_ms = 0.0, s.query_chunks = 1, s.query_sorted = 0;
+            s.tie_queries = s.counters_host[kTieCounter];
+            s.root_misses = s.counters_host[kTieCounter + 1];
+            s.crack_queries = s.counters_host[kCrackCounter];
+        }
+    } else {
+        rc = query_batch(s, d_rays, d->n, d->tmin, d->tmax, d->any_hit != 0, d->ranged != 0, d_ids, d_hits, d_uv, wait,
+                         d->wait_stream);
+    }
+    if (!rc) rc = check_report(s, "tmpt_scene_hit_device");
+    return rc;
+    TMPT_GUARD_END
+}
+
+int tmpt_query_keys(const float* rays, int64_t n, int32_t stride, const float box[6], uint32_t* keys)
+{
+    TMPT_GUARD_BEGIN
+    if (n < 0) return bad("tmpt_query_keys: n < 0");
+    if (n > 0 && (!rays || !keys)) return bad("tmpt_query_keys: null rays or keys");
+    if (stride != 6 && stride != 8) return bad("tmpt_query_keys: stride is 6 or 8");
+    if (!box) return bad("tmpt_query_keys: null box");
+    for (int64_t i = 0; i < n; ++i) {
+        const float* r = rays + (int64_t)stride * i;
+        keys[i] = query_key(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), box);
+    }
+    return 0;
+    TMPT_GUARD_END
+}
+
+int tmpt_query_plan(int64_t n, int32_t sorted, int64_t chunk, int64_t grid_cap, int64_t resident, int64_t out[6])
+{
+    TMPT_GUARD_BEGIN
+    if (n < 0) return bad("tmpt_query_plan: n < 0");
+    if (sorted != 0 && sorted != 1) return bad("tmpt_query_plan: sorted is 0 or 1");
+    if (chunk < 64 || chunk > kQueryChunkMax) return bad("tmpt_query_plan: chunk outside 64 .. 2^22");
+    if (grid_cap < 0) return bad("tmpt_query_plan: grid_cap < 0");
+    if (resident < 1) return bad("tmpt_query_plan: resident < 1");
+    if (!out) return bad("tmpt_query_plan: null out");
+    const QueryPlan p = query_plan(n, sorted != 0, chunk, grid_cap, resident, kStackTotal - kSL, radix_sort_hist_words);
+    out[0] = p.chunks, out[1] = p.chunk_n, out[2] = p.last_n, out[3] = p.grid;
+    out[4] = (int64_t)p.ovf_bytes, out[5] = (int64_t)p.sort_bytes;
+    return 0;
     TMPT_GUARD_END
 }
 

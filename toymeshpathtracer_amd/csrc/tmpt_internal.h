@@ -314,6 +314,13 @@ constexpr int kShadowOrderDefault = 2;
 // queries and the AOV pass go by sample seeding's.
 constexpr int kPopCullSample = 1, kPopCullPixel = 1, kPopCullRow = 1;
 
+// tmpt_scene_hit_device's two measured defaults (options query_top / query_sort = -1;
+// DESIGN.md section 4, "Device-resident queries", has the table and the rule):
+// the LDS top levels, and the smallest batch that is sorted (0: never)
+constexpr int kQueryTopDefault = 1;
+constexpr int64_t kQuerySortMinN = 0;
+constexpr int kQuerySortTimed = 32;  // chunks of a sorted call whose keys + sort are timed (query_sort_ms)
+
 constexpr int kRowSpecMaxGroups = 8;  // speculative row engine: row groups (streams)
 constexpr int kRenderCounters = 48;   // ray / visit / round counters of one render
 constexpr int kWalkCounter = 42;      // [42] stack entries pop culling discarded, [43] of them followed by
@@ -401,6 +408,14 @@ struct Options {
     int octree_build = 0;     // tmpt_scene_build_octree: 0 = the host build (tmpt_octree.cpp), 1 = the level-order
                               // build on the device (tmpt_octree_dev.hip); the same octree word for word
     double octree_dev_max = 0.0;  // octree_build=device: cap on its scratch and result, bytes (0 = half of the free HBM)
+    int query_sort = -1;      // tmpt_scene_hit_device: rays traced in the order of a 24-bit origin-cell / direction key
+                              // (tmpt_query_key.h), in chunks (-1 = the measured rule, 0 off, 1 on)
+    int query_top = -1;       // tmpt_scene_hit_device: the top BVH4 levels read from LDS (-1 = the measured default)
+    double query_max = 0.0;   // tmpt_scene_hit_device: cap on the scene's query scratch, bytes (0 = half of the free HBM)
+    int query_chunk = 1 << 22;  // test hook: rays per sorted chunk
+    int query_grid = 0;       // test hook: cap on the blocks of a k_query launch (0 = the occupancy grid)
+    int query_legacy = 0;     // tool hook: 1 = tmpt_scene_hit_device launches k_intersect on the caller's device
+                              // data instead (tools/hit_device_time.py's kernel-only comparison; no uv)
     int denoise_lds = -1;     // tmpt_denoise: levels of stride 1 and 2 read an LDS tile + halo (1), every level
                               // reads global memory directly (0), or the measured choice per stride (-1)
 };
@@ -556,6 +571,16 @@ struct Scene {
     int64_t adapt_n = 0;
     DeviceBuffer<> adapt_buf;
     PinnedBuffer<uint32_t> adapt_host;
+    // tmpt_scene_hit_device (tmpt_query.hip query_batch): the overflow stacks and
+    // sort buffers of its launches (kept, grown, counted against query_max), its
+    // events (the call; keys + sort of the first kQuerySortTimed chunks), and the
+    // last call's read-only options
+    DeviceBuffer<> query_buf;
+    Event query_ev[2];
+    std::vector<Event> query_sort_ev;
+    double query_ms = 0.0, query_sort_ms = 0.0;
+    int64_t query_chunks = 0;
+    int32_t query_sorted = 0;
     int path_launches = 1;  // k_path launches of the last persistent render (pilot ordering: 2)
     Event path_ev[4];       // around the pilot / final k_path
     // statistics of the last render

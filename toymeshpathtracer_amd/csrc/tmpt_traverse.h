@@ -683,7 +683,7 @@ __device__ __forceinline__ void settle_any(const SceneView& sv, const TravRay& r
 // the random unit vector exactly cancels the normal).  Traversing it would
 // visit every node (NaN slab distances never cull), so it is answered as a
 // miss up front; it still counts as a ray.
-__device__ __forceinline__ bool ray_has_nan(f3 o, f3 d)
+TMPT_HD bool ray_has_nan(f3 o, f3 d)  // (host too: the query key's check hook, tmpt_query_key.h)
 {
     return __builtin_isnan(o.x) | __builtin_isnan(o.y) | __builtin_isnan(o.z) | __builtin_isnan(d.x) |
            __builtin_isnan(d.y) | __builtin_isnan(d.z);
