@@ -401,10 +401,18 @@ int tmpt_scene_create(const float* tris, int32_t n, int32_t device, tmpt_scene**
  *                    their main loop is done (-1 = auto, 0 = off: ties settled in the
  *                    main loop, 1 = on); the image and ray counts are the same either way
  *   redo_lanes       tie_defer: lanes per wave that take the re-traces (1..64, default 4)
- *   path_waves       waves per SIMD of the persistent path kernels (0 = auto, 4 or 5; 5: a 12-entry LDS
- *                    stack and 80 LDS top nodes, 30 KB of LDS per block and 96 VGPRs per lane).  Auto:
- *                    5 in sample seeding and the row engine's re-trace, 5 in pixel seeding from 3 pixels
- *                    per 4-wave lane
+ *   path_waves       waves per SIMD of the persistent path kernels (0 = auto, 4, 5 or 6; 5: a 12-entry LDS
+ *                    stack and 80 LDS top nodes, 30 KB of LDS per block and 96 VGPRs per lane; 6: the
+ *                    shadow split's kernels only -- a 12-entry stack and 64 top nodes, 26 KB and 80 VGPRs
+ *                    -- and what 5 runs wherever the split does not run: pixel and row seeding, a
+ *                    progressive or adaptive pass, the float sums, shadow_split=0, cam_pre=0, a scene
+ *                    whose shadow answers can need the octree).  Auto: 5 in sample seeding and the row
+ *                    engine's re-trace -- 6 where the split runs with deferred ties (tie_defer) and the
+ *                    pass has at least 150 samples per lane of the 5-wave grid --, 5 in pixel seeding
+ *                    from 3 pixels per 4-wave lane.  The image and every count are the same for every
+ *                    value
+ *   path_waves_used  read-only: the waves per SIMD the last tmpt_render's path kernel ran at (4, 5 or
+ *                    6; 0 where the row engines rendered)
  *   top_walk         persistent path kernels: at the end of a shading round, up to top_walk node
  *                    rounds for the lanes standing on a BVH node of the block's LDS copy of the top
  *                    levels (every query starts there), with no global load in them (-1 = the

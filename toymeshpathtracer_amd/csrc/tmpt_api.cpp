@@ -139,7 +139,7 @@ const OptionDef kOptions[] = {
     {"redo_cap", false, 0, 1 << 30, &Options::redo_cap, nullptr, nullptr},
     {"redo_inline", false, 0, 1, &Options::redo_inline, nullptr, nullptr},
     {"redo_lanes", false, 1, 64, &Options::redo_lanes, nullptr, nullptr},
-    {"path_waves", false, 0, 5, &Options::path_waves, nullptr, nullptr},
+    {"path_waves", false, 0, 6, &Options::path_waves, nullptr, nullptr},
     {"top_walk", false, -1, 8, &Options::top_walk, nullptr, nullptr},
     {"shadow_order", false, -1, 2, &Options::shadow_order, nullptr, nullptr},
     {"pop_cull", false, -1, 1, &Options::pop_cull, nullptr, nullptr},
@@ -200,8 +200,12 @@ int options_set(Options& o, const char* key, double v, bool allow_build)
             set_error(std::string("option '") + key + "' takes an integer");
             return -22;
         }
-        if ((strcmp(key, "row_occ") == 0 || strcmp(key, "path_waves") == 0) && v != 0 && v != 4 && v != 5) {
+        if (strcmp(key, "row_occ") == 0 && v != 0 && v != 4 && v != 5) {
             set_error(std::string("option '") + key + "' takes 0 (auto), 4 or 5");  // waves per SIMD
+            return -22;
+        }
+        if (strcmp(key, "path_waves") == 0 && v != 0 && v != 4 && v != 5 && v != 6) {
+            set_error(std::string("option '") + key + "' takes 0 (auto), 4 or 5, or 6 (the shadow split's 6-wave kernels)");  // waves per SIMD
             return -22;
         }
         if (strcmp(key, "aov_group") == 0 && v > 0 && ((long long)v & ((long long)v - 1)) != 0) {
@@ -748,6 +752,10 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
     }
     if (key && strcmp(key, "shadow_split_used") == 0) {  // read-only: passes of the last render the shadow split ran
         *value = (double)h->s.split_used;
+        return 0;
+    }
+    if (key && strcmp(key, "path_waves_used") == 0) {  // read-only: waves per SIMD of the last render's path kernel
+        *value = (double)h->s.path_waves_used;
         return 0;
     }
     if (key && strcmp(key, "shadow_split_resolve_ms") == 0) {  // read-only: k_split_resolve's time in that render

@@ -166,6 +166,15 @@ constexpr int kTopNodes = 120;  // BVH4 nodes held in LDS per path block (7.5 KB
 // occupancy API still said 5, and the launch's tail waited for blocks that
 // were never resident), 72-96 nodes measured alike.
 constexpr int kTopNodes5 = 80;
+// The 6-wave twins of the shadow split (OCC 6, SPLIT: no pending ray): six
+// blocks per CU.  The CU hands out its 160 KB of LDS in units of kLdsGranule
+// bytes -- the boundary round 6 measured fits no other unit: 31,744 B (25
+// units, 5 x 25 = 125 of 128) ran five blocks, 32,256 B (26, 130) did not,
+// whatever the occupancy query said -- so a sixth block needs 21 units or
+// fewer, 26,880 B, not 163,840 / 6.  A 12-entry stack (12 KB), the light terms
+// (10 KB) and 64 top nodes (4 KB) are 26,640 B (k_path asserts the bound).
+constexpr int kLdsGranule = 1280, kLdsBytes = 163840;
+constexpr int kTopNodes6 = 64;
 
 struct alignas(16) TriPre {
     float4 a;  // v0.xyz, e1.x
@@ -390,7 +399,8 @@ struct Options {
                               // overflows, and the frame is rendered again with the list grown)
     int redo_lanes = 4;       // tie_defer: lanes per wave that take re-traces in the launch's tail
     int path_waves = 0;       // path-kernel waves per SIMD (0 = auto: 5 in sample seeding, in pixel seeding
-                              // from 3 pixels per 4-wave lane; 4 or 5)
+                              // from 3 pixels per 4-wave lane; 4, 5 or 6 -- 6: the shadow split's twins,
+                              // 5 wherever there is no 6-wave kernel)
     int redo_inline = 1;      // test hook: 0 = the deferring kernel's waves leave every dropped sample
                               // to the k_redo launch (its fallback) instead of tracing them in their tail
     int top_walk = -1;        // path kernels: node rounds over the LDS-cached top levels at the end of a
@@ -520,6 +530,8 @@ struct Scene {
     // passes, and its kernels' times
     DeviceBuffer<> split_buf;
     int32_t split_used = 0, split_passes = 0;
+    // waves per SIMD the last render's path kernel was built for and launched at (0: no k_path ran)
+    int32_t path_waves_used = 0;
     // a shadow-split render in several passes of samples (render_split_passes):
     // the pixels' float sums carried from pass to pass (RenderArgs::prog of
     // its passes; kept, grown) and the passes' summed statistics

@@ -225,6 +225,22 @@ struct PathVariant {
 // seeding and the rows' full re-trace (OCC 5): 30 KB of LDS per block -- a
 // 12-entry LDS stack, the scattered ray's direction only, kTopNodes5 top nodes
 constexpr int kPathSL = 16, kPathSL5 = 12;
+// the 6-wave twins of the shadow split (OCC 6): the same 12 entries, kTopNodes6 top nodes
+constexpr int kPathSL6 = 12;
+// path_waves = 0 (auto) in sample seeding where the shadow split runs with the
+// deferring twin (TIES 1): 1 = its 6-wave form from kPathWaves6MinLoad samples
+// of the pass per lane of the 5-wave grid, 0 = always the 5-wave one (A/B
+// macro).  Whole renders of the bench frame, 5 / 6 waves, same box
+// (profiles/README_r13.md): N=1 (405 samples per lane) 143.41 / 140.87 ms,
+// 1/2 shard (202) 73.36 / 72.50, 1/4 (101) 38.78 / 38.52 -- -0.68 %, at the
+// edge of three times that run's spread --, 1/8 (51) 20.37 / 20.59 and 20.48 /
+// 20.55 in two runs: level or losing.  So from 150 per lane, between the 1/4
+// shard's load and the 1/2 shard's.
+#ifndef TMPT_PATH_WAVES6
+#define TMPT_PATH_WAVES6 1
+#endif
+constexpr int kPathWaves6Auto = TMPT_PATH_WAVES6;
+constexpr int64_t kPathWaves6MinLoad = 150;
 
 // The cadences, each with its A/B macro (tools/ab_build.sh, tools/ab_kpath.py).
 #ifndef TMPT_PATH_STEPS

@@ -520,6 +520,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     // ray (s_next) and the shadow branch of the shading round are not there.
     // A finished sample leaves its record (SplitRec) instead of a colour.
     static_assert(!SPLIT || (CAM && !SUMS && !LIST && PROF == 0), "SPLIT: the plain CAM sample kernels");
+    // OCC 6 (6 waves per SIMD: <= 80 VGPRs, kTopNodes6 top nodes): the SPLIT
+    // twins only -- without the shadow branch and the pending ray they fit
+    static_assert(OCC < 6 || (SPLIT && SL == kPathSL6), "OCC 6: the shadow split's twins");
+    // a SPLIT lane's queries are closest-hit queries at compile time
+    constexpr int QK = SPLIT ? kQueryClosest : kQueryRuntime;
     __shared__ uint32_t s_stack[SL * BLOCK];
     // SAMP 3, 4 (shadow-free speculation): no light terms, no pending next ray
     __shared__ float s_light[SAMP >= 3 ? 1 : kMaxDepth * BLOCK];
@@ -551,8 +556,13 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
     __shared__ uint8_t s_pair[HELP ? BLOCK : 1];
     {  // the top BVH4 levels (nodes are numbered level by level) in LDS
         // HELP: 4 nodes fewer, so s_pair keeps the block at 4 per CU
-        constexpr int kTop = OCC >= 5 ? kTopNodes5 : (HELP ? kTopNodes - 4 : kTopNodes);
+        constexpr int kTop = OCC >= 6 ? kTopNodes6 : OCC >= 5 ? kTopNodes5 : (HELP ? kTopNodes - 4 : kTopNodes);
         __shared__ uint4 s_top[kTop * 4];
+        // six co-resident blocks: the block's LDS in the CU's allocation units
+        // (16 B of slack for the one-word arrays' alignment)
+        static_assert(OCC < 6 || (sizeof(s_stack) + sizeof(s_light) + sizeof(s_next) + sizeof(s_pair) + sizeof(s_top) + 16 +
+                                  kLdsGranule - 1) / kLdsGranule * OCC <= kLdsBytes / kLdsGranule,
+                      "OCC 6: six blocks' LDS must fit the CU");
         const uint32_t ntop = (uint32_t)min(kTop, sv.n_nodes4);
         const uint4* g = reinterpret_cast<const uint4*>(sv.nodes4);
         for (uint32_t i = threadIdx.x; i < ntop * 4; i += BLOCK) s_top[i] = g[i];
@@ -1242,8 +1252,8 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                     if (top) {
                         bool done;
                         if (!COUNT) {
-                            done = trav_step4q2_mixed<false, BLOCK, SL, true, 1, SOA, false, FLAG, true>(sv, r, qany, ts, st,
-                                                                                                        cnt);
+                            done = trav_step4q2_mixed<false, BLOCK, SL, true, 1, SOA, false, FLAG, true, QK>(sv, r, qany, ts,
+                                                                                                            st, cnt);
                         } else {
                             TravCount c1;
                             done = trav_step4q2_mixed<COUNT, BLOCK, SL, true, 1, SOA, false, FLAG, true>(sv, r, qany, ts, st,
@@ -1332,9 +1342,11 @@ __global__ void __launch_bounds__(BLOCK, OCC) k_path(SceneView sv, RenderArgs a,
                 const bool stepping = in_query && ((ts.node < 0) == leaf_round);
                 bool done = false;
                 if (leaf_round) {
-                    if (stepping) done = trav_step4q2_mixed<false, BLOCK, SL, true, 2, SOA, false, FLAG>(sv, r, qany, ts, st, cnt);
+                    if (stepping)
+                        done = trav_step4q2_mixed<false, BLOCK, SL, true, 2, SOA, false, FLAG, false, QK>(sv, r, qany, ts, st, cnt);
                 } else {
-                    if (stepping) done = trav_step4q2_mixed<false, BLOCK, SL, true, 1, SOA, false, FLAG>(sv, r, qany, ts, st, cnt);
+                    if (stepping)
+                        done = trav_step4q2_mixed<false, BLOCK, SL, true, 1, SOA, false, FLAG, false, QK>(sv, r, qany, ts, st, cnt);
                 }
                 if (done) in_query = false;
                 if (stepping && ((kFull && pc.cost_out) || dp0 > 0.0f)) ++psteps;
@@ -1653,6 +1665,10 @@ constexpr PathVariant kPathVariants[] = {
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 0, F, 1, F, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 2, F, 1, F, 1},
     {F, kPathSL5, kSampleSteps, kShadeMin, 5, 0, 0, 1, F, 1, F, 1, F, 1},
+    // ... and those at 6 waves per SIMD (option path_waves 6; kPathSL6, kTopNodes6)
+    {F, kPathSL6, kSampleSteps, kShadeMin, 6, 0, 0, 1, F, 0, F, 1, F, 1},
+    {F, kPathSL6, kSampleSteps, kShadeMin, 6, 0, 0, 1, F, 2, F, 1, F, 1},
+    {F, kPathSL6, kSampleSteps, kShadeMin, 6, 0, 0, 1, F, 1, F, 1, F, 1},
     // ... and the passes over a list of pixels (LIST; tmpt_render_adaptive's
     // passes after the first): 4 or 5 waves, the three tie modes, at 5 waves
     // with the CAM twins; they read the AoS records (layout=soa too)
@@ -1839,12 +1855,17 @@ void launch_resolve_px(hipStream_t stream, const float4* sbuf, int64_t P, int32_
 
 // ============================================================ host side
 // (kBlk, kSL and the helpers up to make_args: shared with tmpt_aov.hip, tmpt_render.h)
+// co-resident blocks per CU of a kernel (at least 1)
+static int occupancy_blocks(const void* fn, int block, size_t dyn_lds)
+{
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, dyn_lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    return per_cu;
+}
+
 int occupancy_grid(const void* fn, int block, size_t dyn_lds, int device)
 {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, dyn_lds) != hipSuccess ||
-        per_cu < 1)
-        per_cu = 1;
+    int per_cu = occupancy_blocks(fn, block, dyn_lds), cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         cus < 1)
         cus = 256;
@@ -2170,8 +2191,33 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     const int grid4 = occupancy_grid((const void*)fn_base, kBlk, 0, s.device);
     const int grid5 = occupancy_grid((const void*)fn_probe5, kBlk, 0, s.device);
     const bool waves5p = !jt && !count && !prof &&
-                         (o.path_waves == 5 || (o.path_waves == 0 && a.slots >= 3 * (int64_t)grid4 * kBlk));
+                         (o.path_waves >= 5 || (o.path_waves == 0 && a.slots >= 3 * (int64_t)grid4 * kBlk));
     const int grid = waves5 || waves5p ? grid5 : grid4;
+    // Six waves per SIMD (option path_waves 6): only the shadow split's twins
+    // have 6-wave kernels (kPathVariants), so the render wants them only where
+    // the split can run, and runs the 5-wave kernels wherever it then does not
+    // (split_on below).  The load rules above and below (sample blocks, tail
+    // units, the deferral) keep going by the 5-wave grid; what is sized by the
+    // launch -- the stack spill area, the shadow queue's reservations -- goes
+    // by the larger of the two grids.
+    // Auto (path_waves 0): the deferring twin (TIES 1, pick_main below) from
+    // kPathWaves6MinLoad samples per 5-wave lane -- the loads it was measured
+    // at are in tmpt_path.h.
+    const bool want6 = waves5 && !prof && !list && o.shadow_split != 0 &&
+                       (o.path_waves == 6 ||
+                        (o.path_waves == 0 && kPathWaves6Auto != 0 &&
+                         a.slots * (int64_t)(a.smp_end - a.smp_begin) >= kPathWaves6MinLoad * (int64_t)grid5 * kBlk));
+    int grid6 = 0;
+    if (want6) {
+        PathVariant probe6 = probe5;
+        probe6.sl = kPathSL6;
+        probe6.occ = 6;
+        probe6.cam = 1;
+        probe6.split = 1;
+        PathFn fn_probe6;
+        if (int rc = find_path_kernel(probe6, "tmpt_render", fn_probe6)) return rc;
+        grid6 = occupancy_grid((const void*)fn_probe6, kBlk, 0, s.device);
+    }
     // Sample seeding: the work units are (pixel, block of blk samples).  The
     // block is the largest power of two up to 8 that still leaves >=
     // kUnitsPerLane units per resident lane.  Bench frame (1-row bands,
@@ -2312,8 +2358,9 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     const bool w5 = jt ? waves5 : waves5p;
     // stack spill areas for either kind of kernel's lanes (4 waves, 16 LDS
     // entries; 5 waves, 12)
-    size_t ovf_words = std::max((size_t)grid4 * (kStackTotal - kPathSL),
-                                (size_t)std::max(grid4, grid5) * (kStackTotal - kPathSL5)) * kBlk;
+    size_t ovf_words = std::max({(size_t)grid4 * (kStackTotal - kPathSL),
+                                 (size_t)std::max(grid4, grid5) * (kStackTotal - kPathSL5),
+                                 (size_t)grid6 * (kStackTotal - kPathSL6)}) * kBlk;
     // (k_shadow's lanes spill there after k_path's: more lanes, shorter LDS stacks)
     if (jt && o.shadow_split != 0) ovf_words = std::max(ovf_words, shadow_ovf_words(s.device));
     const size_t head_words = (size_t)kSeg * kCtr;
@@ -2442,7 +2489,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         // (split_sub: a pass of render_split_passes, whose carried sums are a.prog)
         const bool split_on = o.shadow_split != 0 && cam_on && !sums && pc.sbuf && !s.adapt_on &&
                               (s.split_sub || (!pass && !a.prog)) && !oct_shadow &&
-                              ensure_split(s, cam_n, (int64_t)grid5 * (kBlk / 64), sq_cap);
+                              ensure_split(s, cam_n, (int64_t)std::max(grid5, grid6) * (kBlk / 64), sq_cap);
         if (split_on) {
             uint32_t* ctl = s.split_buf.as<uint32_t>();
             pc.sq_ctl = ctl;
@@ -2458,14 +2505,40 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
         PathVariant v_main = variant(w5, help, flag ? (redo ? 1 : 2) : 0, sums, cam_on ? 1 : 0);
         v_main.split = split_on ? 1 : 0;
         PathFn fn_main;
-        if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
-        // the launch's grid is the launched kernel's co-resident block count
-        // (the deferred re-traces' completion count relies on it)
-        int grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
-        if ((size_t)grid_main * kBlk * (kStackTotal - kPathSL5) > ovf_words) {
+        int grid_main = 0;
+        // The kernel of v_main and its grid.  The split's twin at 6 waves per
+        // SIMD where the render wants it (want6) and six of its blocks are
+        // co-resident on a CU by the occupancy query; otherwise the 5-wave
+        // kernel: a kernel built for 80 VGPRs never runs at 5 waves.  The
+        // launch's grid is the launched kernel's co-resident block count (the
+        // deferred re-traces' completion count relies on it).
+        auto pick_main = [&]() -> int {
+            if (want6 && v_main.split && (o.path_waves == 6 || v_main.ties == 1)) {
+                PathVariant v6 = v_main;
+                v6.sl = kPathSL6;
+                v6.occ = 6;
+                PathFn fn6;
+                if (int rc = find_path_kernel(v6, "tmpt_render", fn6)) return rc;
+                if (occupancy_blocks((const void*)fn6, kBlk, 0) >= 6) {
+                    v_main = v6;
+                    fn_main = fn6;
+                    grid_main = occupancy_grid((const void*)fn6, kBlk, 0, s.device);
+                    return 0;
+                }
+            }
+            v_main.sl = w5 ? kPathSL5 : kPathSL;
+            v_main.occ = w5 ? 5 : prof ? 1 : 4;
+            if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
+            grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
+            return 0;
+        };
+        if (int rc = pick_main()) return rc;
+        // (the spill area of the launched grid at the launched kernel's LDS stack depth)
+        if ((size_t)grid_main * kBlk * (kStackTotal - v_main.sl) > ovf_words) {
             set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
             return -1;
         }
+        s.path_waves_used = v_main.occ;
         s.tie_path = !oct ? 0 : redo ? 2 : redo_nomem ? 3 : 1;
         s.path_launches = 1;
         for (int attempt = 0;; ++attempt) {
@@ -2493,8 +2566,12 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
                 if (!(n < (1ull << 31) && alloc_redo(s, (int64_t)n))) {
                     redo = false;
                     v_main.ties = 2;  // the same kernel but for the ties: answered in the main loop
-                    if (int rc = find_path_kernel(v_main, "tmpt_render", fn_main)) return rc;
-                    grid_main = occupancy_grid((const void*)fn_main, kBlk, 0, s.device);
+                    if (int rc = pick_main()) return rc;
+                    if ((size_t)grid_main * kBlk * (kStackTotal - v_main.sl) > ovf_words) {
+                        set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
+                        return -1;
+                    }
+                    s.path_waves_used = v_main.occ;
                     s.redo_samples = 0;
                     s.tie_path = 3;
                 }
@@ -2552,6 +2629,7 @@ int render_persistent(Scene& s, const RenderArgs& a, uint32_t* d_out, bool count
     PathFn fn;
     if (int rc = find_path_kernel(variant(w5, help, flag ? 2 : 0, false), "tmpt_render", fn)) return rc;
     const int grid_px = occupancy_grid((const void*)fn, kBlk, 0, s.device);
+    s.path_waves_used = w5 ? 5 : prof ? 1 : 4;
     if ((size_t)grid_px * kBlk * (kStackTotal - (waves5p ? kPathSL5 : kPathSL)) > ovf_words) {
         set_error("tmpt_render: internal: stack spill area sized for fewer lanes");
         return -1;
@@ -2781,6 +2859,7 @@ void reset_render_stats(Scene& s)
     s.cam_rays_used = 0;
     s.split_used = 0;
     s.split_passes = 0;
+    s.path_waves_used = 0;
     s.split_resolve_ms = 0.0;
 }
 
@@ -2834,7 +2913,16 @@ static int32_t split_pass_samples(Scene& s, const RenderArgs& a)
     probe5.ties = 1;
     PathFn fn;
     if (find_path_kernel(probe5, "tmpt_render", fn)) return 0;
-    const int64_t waves = (int64_t)occupancy_grid((const void*)fn, kBlk, 0, s.device) * (kBlk / 64);
+    int64_t waves = (int64_t)occupancy_grid((const void*)fn, kBlk, 0, s.device) * (kBlk / 64);
+    if (o.path_waves == 6 || (o.path_waves == 0 && kPathWaves6Auto != 0)) {  // the 6-wave twins' larger grid
+        PathVariant probe6 = probe5;
+        probe6.sl = kPathSL6;
+        probe6.occ = 6;
+        probe6.cam = 1;
+        probe6.split = 1;
+        if (find_path_kernel(probe6, "tmpt_render", fn)) return 0;
+        waves = std::max(waves, (int64_t)occupancy_grid((const void*)fn, kBlk, 0, s.device) * (kBlk / 64));
+    }
     const size_t budget = split_budget(s);
     uint32_t cap = 0;
     auto fits = [&](int64_t c) {

@@ -215,6 +215,10 @@ __device__ __forceinline__ void trav_init(TravState& ts, float tmax)
     ts.bu = ts.bv = 0.0f;
 }
 
+// The query kind of trav_step4q2_mixed and trav_pop (template parameter QK):
+// decided by the run-time `any`, or a closest-hit query at compile time.
+constexpr int kQueryRuntime = 0, kQueryClosest = 1;
+
 // The next entry off the stack into ts.node (a clean link: the key is masked
 // off here, once); true when the stack is empty (the query is finished).
 // Pop culling (option pop_cull, SceneView::key_mask): a closest-hit lane discards
@@ -228,12 +232,14 @@ __device__ __forceinline__ void trav_init(TravState& ts, float tmax)
 // no key and discards nothing.  With culling off key_mask is 0: every key
 // reads as 0, which exceeds no bt >= 0.  KIND 1 / 2 (voted rounds): branch-free
 // while the stack is within its LDS part, both candidate entries read at once.
-template <bool COUNT, int KIND, bool NEG, int BLOCK, int SL>
+// QK (the query kind, below): kQueryClosest fixes the closest-hit limit at
+// compile time and `any` is not read.
+template <bool COUNT, int KIND, bool NEG, int QK = kQueryRuntime, int BLOCK, int SL>
 __device__ __forceinline__ bool trav_pop(const SceneView& sv, bool any, TravState& ts, TravStack<BLOCK, SL>& st,
                                          TravCount& cnt)
 {
     const uint32_t km = NEG ? 0u : sv.key_mask;
-    const float lim = any ? INFINITY : ts.bt * kTfarSlack;
+    const float lim = QK == kQueryClosest ? ts.bt * kTfarSlack : any ? INFINITY : ts.bt * kTfarSlack;
     auto is_stale = [&](uint32_t e) { return !NEG && __uint_as_float(entry_key(e, km)) > lim; };
     if (KIND != 0 && ts.sp <= SL) {
         const uint32_t e1 = st.lds[(uint32_t)max(ts.sp - 1, 0) * BLOCK];
@@ -286,8 +292,21 @@ __device__ __forceinline__ bool trav_pop(const SceneView& sv, bool any, TravStat
 // shrink it there); the path engines' range kMinT..kMaxT never needs it.
 // TOPONLY (with KIND 1): the caller guarantees ts.node < st.ntop, so only the
 // LDS read of the node is emitted, no global load (k_path's top-walk rounds).
+// QK: the query kind.  kQueryRuntime (the default): `any` decides at run time.
+// kQueryClosest: a closest-hit query by construction (k_path's SPLIT twins,
+// whose lanes never trace a shadow ray) -- the caller passes `any` false, the
+// sort key is tn itself, the pop limit is ts.bt * kTfarSlack and nothing reads
+// sv.any_w.  The run-time form computes a closest-hit key as fma(0, tf, tn),
+// which does not fold without fast-math and leaves a v_fmac with a zero
+// multiplier per child on the chain between the cull compare and the sort.
+// For every child that passes (tn <= tf_slack) that fma's value is tn: tf is
+// finite there -- a min with ts.bt <= kMaxT from above, and >= tn / kTfarSlack
+// >= 0 from below, so 0 * tf is a zero, never NaN -- and tn >= +0 (the max
+// with tlo = +0 in every non-NEG caller; NEG pushes no key), so zero + tn is
+// tn bit for bit (+0 + -0 is +0 in round-to-nearest).  Keys, pushes, visit
+// order and answers are those of the run-time form with `any` false.
 template <bool COUNT, int BLOCK, int SL, bool TOPC = false, int KIND = 0, bool SOA = false, bool NEG = false,
-          bool FLAG = false, bool TOPONLY = false>
+          bool FLAG = false, bool TOPONLY = false, int QK = kQueryRuntime>
 __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const TravRay& r, bool any,
                                                    TravState& ts, TravStack<BLOCK, SL>& st,
                                                    TravCount& cnt, float tlo = 0.0f, float tmin = kMinT,
@@ -355,13 +374,13 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
         // child the ray stays in longest goes first, with a large negative
         // any_w the child it leaves last.  Only the order of the visits
         // depends on it; which children pass does not.
-        const float w = any ? sv.any_w : 0.0f;
+        const float w = QK == kQueryClosest ? 0.0f : any ? sv.any_w : 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float tn = fmaxf(fmaxf(tnx[k], tny[k]), fmaxf(tnz[k], tlo));
             float tf = fminf(fminf(tfx[k], tfy[k]), fminf(tfz[k], ts.bt));
             const float tf_slack = NEG ? tf + fabsf(tf) * (kTfarSlack - 1.0f) : tf * kTfarSlack;
-            key[k] = tn <= tf_slack ? __builtin_fmaf(w, tf, tn) : INFINITY;
+            key[k] = tn <= tf_slack ? (QK == kQueryClosest ? tn : __builtin_fmaf(w, tf, tn)) : INFINITY;
         }
         {  // nearest child next; the others pushed pairwise-ordered only
             const bool s01 = key[1] < key[0], s23 = key[3] < key[2];
@@ -478,7 +497,7 @@ __device__ __forceinline__ bool trav_step4q2_mixed(const SceneView& sv, const Tr
             }
         }
     }
-    return trav_pop<COUNT, KIND, NEG>(sv, any, ts, st, cnt);
+    return trav_pop<COUNT, KIND, NEG, QK>(sv, any, ts, st, cnt);
 }
 
 // ---------------------------------------------------------------- reference octree
