@@ -46,7 +46,55 @@ and the three octree counters, a HitScene batch tie_queries and root_misses,
 tmpt_render_adaptive the summed rays, redo_samples, the octree counters and
 tie_path; denoise, camera_rays, radix_sort, the octree rebuild and the refused
 calls none.
+
+The kinds added after the first 25 (the entry points the handle gained since:
+KINDS from moments_uniform on; COVERS maps every kind to the Scene methods and
+options it exercises, and tests/test_call_kinds_cover.py holds Scene's public
+methods to that map).  Their fixed inputs -- the two frames of a sequence the
+image-to-image kinds read (temporal_inputs), the guided render's prior
+(guided_prior) -- are made once per (definition, size) on fresh scenes and
+marked read-only: data, as denoise_inputs is, not part of any scene's history.
+  moments_uniform, moments_adaptive, guided   tmpt_render_moments / _guided are
+      tmpt_render_adaptive "in every rule": ADAPTIVE_STATS and the info fields, pinned to
+      the adaptive restatements over the oracle's per-sample colours with the moments of
+      noise_aware_restate.moments_expect at each pixel's count.  guided's marker -- some
+      pixel stops at 2, some runs on -- holds in the restatement alone on both
+      definitions (test_call_kinds_pins.py shows it without a GPU)
+  motion_host_prev   the host prev_tris form, which fills Scene::motion_prev; the
+      statistics the header lists for the pass (MOTION_STATS); pinned to
+      temporal_restate's pieces with the oracle octree's triangle where a centre ray is
+      tied (motion_expect: the scenes here have the octree, the restatement's scan none)
+  temporal, temporal_clip_aux, sample_plan, denoise_moments   host arrays, so the clip and
+      the plan go through Scene::clip_stage; "the other fields keep the last render's"
+      (include/tmpt.h), so no statistic is compared; pinned to temporal_restate.blend,
+      temporal_clip_restate.clip, guided_restate.plan, noise_aware_restate.np_denoise_moments
+  hit_device_closest, hit_device_any_sorted   a torch tensor of World.hit_rays on the
+      scene's device, HIT_STATS, the read-only option query_sorted as the route marker;
+      pinned as hit_closest / hit_any_ranged are, (u, v) to Moller-Trumbore's for the
+      returned triangle (test_gpu_hit_device.mt_uv)
+  sample_waves6   path_waves=6 under the shadow split: (path_waves_used,
+      shadow_split_used) = (6, 1) on coincident64, its own definition, and (5, 0) on
+      suzanne, whose flat triangles leave no split to run at six waves
+  sample_based   option sample_base=24, put back to 0 afterwards: both changes drop the
+      jump tables (Scene::jt_spp) and end a pending progressive sequence; pinned to samples
+      [24, 24 + spp) of the oracle's per-sample colours
+  update_refit_back, update_rebuild_back   an update to World.moved and back, bounds=
+      building the octree again (on the device: profiles/call_order_durations.log has the
+      host build's cost); route marker update_kind.  The result is the BVH dump
+      (nodes canonical, records raw: update_refit_back's docstring says why not raw
+      nodes across scenes, and what is compared raw instead) and the octree dump raw,
+      pinned to a fresh scene's
+  octree_device_rebuild   octree_rebuild under octree_build=device, with the octree
+      dump, raw, against a fresh host-built scene's word for word
 Left out, and why:
+  every statistic after temporal, temporal_clip_aux, sample_plan and denoise_moments:
+                     the header promises render_ms alone, a time
+  shadow_rays after motion_host_prev: the header's list for the pass does not name it
+  every statistic after the update kinds: the header names none (update_ms is a time,
+                     bvh_cost is test_gpu_scene_update.py::test_bvh_cost's)
+  any-hit ids, records and (u, v) of hit_device_any_sorted: only the hit bit is
+                     specified across routes (include/tmpt.h); that a reported record
+                     is the reported triangle's is test_gpu_hit_device.py's
   render_ms, extend_ms, shadow_ms, redo_ms, build_ms, octree_build_ms  times
   redo_late, redo_launches, redo_rays  how many re-traces the main launch's tail
                      took before it ended: residency and timing
@@ -68,6 +116,7 @@ Left out, and why:
   the build's fields (bvh_nodes ...): the scene's, not a call's
 """
 import contextlib
+import dataclasses
 import functools
 import math
 
@@ -77,15 +126,20 @@ import adaptive_nb_restate
 import adaptive_restate
 import bvh_check
 import geometry_cases as G
+import guided_restate
+import noise_aware_restate
 import oracle
 import ref_cases
 import render_restate
+import temporal_clip_restate
+import temporal_restate
 import toymeshpathtracer_amd as tm
-from call_order import Kind, Result
+from call_order import Kind, Result, first_difference
 from cam_rays_restate import camera_samples_expect
 from conftest import data
 from test_gpu_denoise import np_denoise
 from test_gpu_denoise import pack as pack_denoised
+from test_gpu_hit_device import mt_uv
 
 f32 = np.float32
 
@@ -100,7 +154,9 @@ COUNT_STATS = RENDER_STATS + ("node_visits", "tri_tests", "shadow_node_visits", 
 AOV_STATS = ("extend_rays", "shadow_rays", "extend_launches") + OCTREE_COUNTS
 ADAPTIVE_STATS = ("extend_rays", "shadow_rays", "redo_samples", "tie_path") + OCTREE_COUNTS
 HIT_STATS = ("tie_queries", "root_misses")
+MOTION_STATS = ("extend_rays", "extend_launches") + OCTREE_COUNTS
 ROUTE_OPTIONS = ("cam_rays_used", "shadow_split_used")
+WAVES_OPTIONS = ROUTE_OPTIONS + ("path_waves_used",)
 
 OSEED = {tm.SEED_ROW: oracle.SEED_ROW, tm.SEED_PIXEL: oracle.SEED_PIXEL, tm.SEED_SAMPLE: oracle.SEED_SAMPLE}
 
@@ -127,6 +183,23 @@ class World:
     def osc_index(self):
         """The oracle's octree scene with ties to the lowest index: an instrumented render's rule."""
         return oracle.Scene(self.tris, accel=oracle.ACCEL_OCTREE, tie=oracle.TIE_INDEX, bmin=self.bmin, bmax=self.bmax)
+
+    @functools.cached_property
+    def moved(self):
+        """The pose of one frame ago, and the update kinds' other triangles: every third
+        triangle moved by 0.01 along all three axes (test_gpu_hit_device.py's `moved`)."""
+        t = self.tris.copy()
+        t[::3] += f32(0.01)
+        t.setflags(write=False)
+        return t
+
+    def prev_camera(self, w, h):
+        """The camera of one frame ago: this frame's, moved by a fixed small offset --
+        2 % of the bounds' diagonal along (1, 0.5, 0.25)."""
+        c = self.camera(w, h)
+        off = f32(0.02) * f32(np.linalg.norm(np.asarray(self.bmax, f32) - np.asarray(self.bmin, f32))) * \
+            np.array([1.0, 0.5, 0.25], f32)
+        return dataclasses.replace(c, origin=(c.origin + off).astype(f32), lower_left=(c.lower_left + off).astype(f32))
 
     @functools.cached_property
     def hit_rays(self):
@@ -193,6 +266,84 @@ def denoise_inputs(world_name, size):
     rad.setflags(write=False)
     aov.setflags(write=False)
     return rad, aov
+
+
+@functools.lru_cache(maxsize=None)
+def temporal_inputs(world_name, size):
+    """The inputs of the image-to-image kinds (temporal, temporal_clip_aux, sample_plan,
+    denoise_moments): two frames of a sequence per size, computed once on fresh scenes --
+    data, not part of any history.  Frame 0: the pose (World.moved) and the camera
+    (World.prev_camera) of one frame ago, its radiance and moments at spp and its motion
+    records.  Frame 1: the world's triangles and camera at sample_base = spp -- radiance,
+    moments, AOV records, the motion records back to frame 0 -- and `stat`, the mean of the
+    two radiance frames (a statistics frame that is neither the current frame nor the history)."""
+    wd = world(world_name)
+    w, h, spp = size
+    cam, pcam = wd.camera(w, h), wd.prev_camera(w, h)
+    with tm.Scene(wd.moved, bounds=(wd.bmin, wd.bmax)) as sc:
+        rad0, mom0 = sc.trace_moments(pcam, w, h, spp)[:2]
+        mot0, _ = sc.trace_motion(pcam, pcam, w, h)
+    with wd.scene() as sc:
+        with options(sc, sample_base=spp):
+            rad1, mom1 = sc.trace_moments(cam, w, h, spp)[:2]
+            aov1, _ = sc.trace_aov(cam, w, h, spp)
+        mot1, _ = sc.trace_motion(cam, pcam, w, h, prev_triangles=wd.moved)
+    out = dict(rad0=rad0, mom0=mom0, mot0=mot0, rad1=rad1, mom1=mom1, aov1=aov1, mot1=mot1,
+               stat=((rad0 + rad1) * f32(0.5)).astype(f32))
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+GUIDED_N_MAX = 3.0  # guided_restate.synthetic_prior's n_max: tmpt_temporal's default
+
+
+@functools.lru_cache(maxsize=None)
+def guided_prior(world_name, size_wh):
+    """The guided kind's prior: guided_restate.synthetic_prior over the frame's per-sample
+    colours 4 .. 7 (the only ones it reads), each a 1-spp radiance frame at sample_base = k of
+    a fresh scene -- data, computed once per size.  At the base size pin() holds it to the same
+    prior over the oracle's per-sample colours."""
+    wd = world(world_name)
+    w, h = size_wh
+    col = np.zeros((h, w, 8, 3), f32)
+    with wd.scene() as sc:
+        for k in range(4, 8):
+            with options(sc, sample_base=k):
+                col[:, :, k] = sc.trace_radiance(wd.camera(w, h), w, h, 1)[0][..., :3]
+    return guided_restate.synthetic_prior(col, GUIDED_N_MAX)
+
+
+def motion_expect(wd, cam, prev_cam, w, h, prev_tris):
+    """temporal_restate.motion for a scene WITH the octree: the restatement's centre rays, hit
+    position and projection, with the closest hit's triangle taken from the oracle's octree
+    scene (visit-order ties, the root test, flat triangles: include/tmpt.h "as tmpt_scene_hit
+    answers it") where that differs from the restatement's lowest-index scan -- t, u and v are
+    then the restated triangle test's for that triangle.  Where no centre ray is tied (suzanne)
+    this is temporal_restate.motion word for word, which test_call_kinds_pins.py asserts."""
+    T = temporal_restate
+    tris = np.asarray(wd.tris, f32).reshape(-1, 3, 3)
+    prev = np.asarray(prev_tris, f32).reshape(-1, 3, 3)
+    o, d = T.centre_rays(cam, w, h)
+    d = d.reshape(-1, 3)
+    ids, t, u, v = T.scan(o, d, tris)
+    rays = np.concatenate([np.broadcast_to(o, d.shape), d], 1).astype(f32)
+    oids, _ = wd.osc.hit_batch(rays, float(T.TMIN), float(T.TMAX))
+    for k in np.unique(oids[(oids != ids) & (oids >= 0)]):
+        sel = np.nonzero((oids == k) & (oids != ids))[0]
+        one, t[sel], u[sel], v[sel] = T.scan(o, d[sel], tris[k:k + 1])
+        assert (one == 0).all(), f"the restated triangle test rejects the oracle's triangle {k}"
+    miss = oids < 0
+    t[miss], u[miss], v[miss] = 0, 0, 0
+    hit = ~miss
+    tp = prev[np.maximum(oids, 0)]
+    px, py, dp, valid = T.project(prev_cam, T.hit_pos(tp[:, 0], tp[:, 1], tp[:, 2], u, v), w, h)
+    valid &= hit
+    rec = np.zeros(h * w, T.MOTION_DTYPE)
+    rec["px"], rec["py"], rec["depth_prev"] = (np.where(valid, a, T.ZERO) for a in (px, py, dp))
+    rec["depth"], rec["u"], rec["v"], rec["tri_id"] = t, u, v, oids
+    rec["flags"] = hit.astype(np.uint32) | (valid.astype(np.uint32) << 1)
+    return rec.reshape(h, w)
 
 
 # ----------------------------------------------------------------------------- the calls
@@ -433,6 +584,181 @@ def arg_errors(scene, size):
     return Result(route=route)
 
 
+# ----------------------------------------------------------------------------- the calls added since the matrix
+def _moments(scene, size, call, *args, **kw):
+    """trace_moments / trace_guided -> Result; the statistics are tmpt_render_adaptive's (include/tmpt.h:
+    "every rule of tmpt_render_adaptive" / "the statistics are unchanged")."""
+    w, h, spp = size
+    rad, mom, img, cnt, rays, info = call(scene.world.camera(w, h), w, h, *args, **kw)
+    stats, route, seen = _stats(scene, ADAPTIVE_STATS)
+    stats.update(passes=info["passes"], samples=info["samples"], pass_pixels=tuple(info["pass_pixels"]))
+    return Result({"radiance": rad, "moments": mom, "image": img, "spp_map": cnt}, rays, stats, route, seen)
+
+
+def moments_uniform(scene, size):
+    """trace_moments(spp_min=None) at spp: the uniform schedule, one pass."""
+    return _moments(scene, size, scene.trace_moments, size[2])
+
+
+def moments_adaptive(scene, size):
+    """trace_moments(cap = spp + 8, 4, 4, 0.02, radius=1, band_rows=4): adaptive_nb's schedule with the moments."""
+    return _moments(scene, size, scene.trace_moments, size[2] + 8, *ADAPTIVE, radius=1, band_rows=4)
+
+
+GUIDED = (2, 4, 0.02)  # spp_min, spp_step, threshold; the cap is spp + 8
+
+
+def guided(scene, size):
+    """trace_guided(cap = spp + 8, the size's fixed prior (guided_prior), 2, 4, 0.02).  The prior
+    the call was given rides in the result, for pin()."""
+    prior = guided_prior(scene.world.name, tuple(size[:2]))
+    res = _moments(scene, size, scene.trace_guided, size[2] + 8, prior, *GUIDED)
+    res.arrays["prior"] = prior
+    return res
+
+
+def motion_host_prev(scene, size):
+    """trace_motion with the previous camera (World.prev_camera) and the previous pose as a HOST
+    array (World.moved): the form that fills Scene::motion_prev."""
+    w, h, _ = size
+    wd = scene.world
+    rec, rays = scene.trace_motion(wd.camera(w, h), wd.prev_camera(w, h), w, h, prev_triangles=wd.moved)
+    stats, _, seen = _stats(scene, MOTION_STATS, route=())
+    return Result({"records": rec}, rays, stats, {}, seen)
+
+
+def temporal(scene, size):
+    """temporal on host arrays: frame 1 of temporal_inputs over frame 0 as the history."""
+    f = temporal_inputs(scene.world.name, tuple(size))
+    out, img = scene.temporal(f["rad1"], f["mot1"], f["mot0"], f["rad0"])
+    return Result({"frame": out, "image": img})
+
+
+CLIP = dict(gamma=0.5, radius=2)
+
+
+def temporal_clip_aux(scene, size):
+    """temporal_clip(gamma=0.5, radius=2, stat=, aux=, aux_history=) on host arrays: seven frames
+    through Scene::clip_stage, the moments frames as the aux pair."""
+    f = temporal_inputs(scene.world.name, tuple(size))
+    out, img, aux = scene.temporal_clip(f["rad1"], f["mot1"], f["mot0"], f["rad0"], stat=f["stat"], aux=f["mom1"],
+                                        aux_history=f["mom0"], **CLIP)
+    return Result({"frame": out, "image": img, "aux": aux})
+
+
+def sample_plan(scene, size):
+    """sample_plan on host arrays (staged through clip_stage too): frame 0's moments as the history."""
+    f = temporal_inputs(scene.world.name, tuple(size))
+    return Result({"prior": scene.sample_plan(f["mot1"], f["mot0"], f["mom0"])})
+
+
+def denoise_moments(scene, size):
+    """denoise_moments, levels=3, over frame 1 of temporal_inputs (radiance, AOV records, moments)."""
+    f = temporal_inputs(scene.world.name, tuple(size))
+    with options(scene, denoise_lds=-1):
+        out, img = scene.denoise_moments(f["rad1"], f["aov1"], f["mom1"], size[2], levels=DENOISE_LEVELS)
+    return Result({"filtered": out, "image": img})
+
+
+def _device(scene, a):
+    return tm.torch.from_numpy(np.array(a)).to(f"cuda:{scene.device}")  # (a writable copy: the fixed rays are read-only)
+
+
+def hit_device_closest(scene, size):
+    """hit_scene_device, closest hits of the world's 256 rays as a device tensor, uv=True,
+    query_sort=0 (query_top at its default)."""
+    rays, (tmin, tmax), _ = scene.world.hit_rays
+    with options(scene, query_sort=0):
+        ids, hits, uv = (t.cpu().numpy() for t in scene.hit_scene_device(_device(scene, rays), tmin, tmax, uv=True))
+        stats, route, seen = _stats(scene, HIT_STATS, route=("query_sorted",))
+    return Result({"ids": ids, "hits": hits, "uv": uv}, None, stats, route, seen)
+
+
+def hit_device_any_sorted(scene, size):
+    """hit_scene_device, any_hit=True, a range per ray, query_sort=1: the hit bits (nothing else
+    of an any-hit answer is defined across routes)."""
+    _, _, r8 = scene.world.hit_rays
+    with options(scene, query_sort=1):
+        ids, _, _ = scene.hit_scene_device(_device(scene, r8), any_hit=True, hits=False)
+        stats, route, seen = _stats(scene, HIT_STATS, route=("query_sorted",))
+    return Result({"hit": (ids.cpu().numpy() >= 0).astype(np.uint8)}, None, stats, route, seen)
+
+
+def sample_waves6(scene, size):
+    """SEED_SAMPLE with path_waves=6 under the shadow split: the six-wave path twins.  Its own
+    definition is coincident64; suzanne's flat triangles keep the fused kernel at five waves."""
+    w, h, spp = size
+    with options(scene, cam_pre=-1, shadow_split=1, shadow_split_pass=0, path_waves=6):
+        img, rays = scene.trace_image(scene.world.camera(w, h), w, h, spp, seed_mode=tm.SEED_SAMPLE)
+        stats, route, seen = _stats(scene, RENDER_STATS, route=WAVES_OPTIONS)
+    return Result({"image": img}, rays, stats, route, seen)
+
+
+SAMPLE_BASE = 24
+
+
+def sample_based(scene, size):
+    """SEED_SAMPLE with option sample_base=24: samples [24, 24 + spp) of every pixel's stream.
+    The option goes back to 0 afterwards, which drops the jump tables."""
+    return _image(scene, size, tm.SEED_SAMPLE, sample_base=SAMPLE_BASE)
+
+
+def _octree_arrays(scene):
+    o = scene.dump_octree()
+    return {"octree_nodes": o["nodes"], "octree_refs": o["refs"], "octree_grid": o["grid"]}, tuple(o["info"].items())
+
+
+def _update_back(scene, mode):
+    wd = scene.world
+    before = scene.dump_bvh()
+    with options(scene, octree_build=1):  # the host recursion over coincident64 costs 0.13 s a build
+        try:
+            scene.update(wd.moved, mode)
+        finally:
+            scene.update(wd.tris, mode, bounds=(wd.bmin, wd.bmax))
+    route = {"update_kind": int(scene.get_option("update_kind"))}
+    dump = scene.dump_bvh()
+    arrays, route["octree_info"] = _octree_arrays(scene)
+    if mode == "refit":
+        route["raw_nodes"] = first_difference(dump["nodes"], before["nodes"]) or "unchanged"
+    arrays.update(nodes=bvh_check.canonical(dump), tris=dump["tris"])
+    return Result(arrays, None, {}, route, {"info": dump["info"]})
+
+
+def update_refit_back(scene, size):
+    """update(World.moved, "refit"), then update(the world's triangles, "refit", bounds=), the
+    octree coming back through the device build (option octree_build=device, put back: word
+    for word the host build's, which octree_rebuild runs and the pin compares with): the
+    result is the BVH dump and the octree dump.  The triangle records and the octree raw; the
+    nodes renumbered breadth-first (bvh_check.canonical), since two builds of one scene number
+    their nodes differently within a level (octree_rebuild's docstring) and the baseline's
+    scene is another build -- and, raw, against the SAME scene's dump from before the two
+    refits (route marker raw_nodes: "unchanged", test_gpu_scene_update.py::test_identity)."""
+    return _update_back(scene, "refit")
+
+
+def update_rebuild_back(scene, size):
+    """The same with "rebuild": the nodes canonical, the triangle records and the octree raw."""
+    return _update_back(scene, "rebuild")
+
+
+def octree_device_rebuild(scene, size):
+    """octree_rebuild's two builds under option octree_build=device (put back afterwards): the
+    BVH dump as octree_rebuild returns it, and the octree dump raw."""
+    wd = scene.world
+    lo, hi = tm.octree_bounds(wd.bmin, wd.bmax)
+    with options(scene, octree_build=1):
+        try:
+            scene.build_octree(lo + f32(0.25), hi + f32(0.25))
+        finally:
+            scene.build_octree(lo, hi)
+    dump = scene.dump_bvh()
+    arrays, oct_info = _octree_arrays(scene)
+    arrays.update(nodes=bvh_check.canonical(dump), tris=dump["tris"])
+    stats, _, seen = _stats(scene, ("octree_flat",), route=())
+    return Result(arrays, None, stats, {"octree_info": oct_info}, seen)
+
+
 KINDS = {k.name: k for k in (
     Kind("row_stream", row_stream), Kind("row_iter", row_iter), Kind("row_mega", row_mega),
     Kind("pixel_ordered", pixel_ordered), Kind("pixel_chains", pixel_chains),
@@ -446,14 +772,67 @@ KINDS = {k.name: k for k in (
     Kind("adaptive", adaptive), Kind("adaptive_nb", adaptive_nb), Kind("denoise", denoise),
     Kind("hit_closest", hit_closest), Kind("hit_any_ranged", hit_any_ranged), Kind("camera_rays", camera_rays),
     Kind("radix_sort", radix_sort), Kind("octree_rebuild", octree_rebuild), Kind("arg_errors", arg_errors),
-    Kind("prepass_fallback", prepass_fallback, sample=True))}
+    Kind("prepass_fallback", prepass_fallback, sample=True),
+    Kind("moments_uniform", moments_uniform), Kind("moments_adaptive", moments_adaptive), Kind("guided", guided),
+    Kind("motion_host_prev", motion_host_prev), Kind("temporal", temporal), Kind("temporal_clip_aux", temporal_clip_aux),
+    Kind("sample_plan", sample_plan), Kind("denoise_moments", denoise_moments),
+    Kind("hit_device_closest", hit_device_closest), Kind("hit_device_any_sorted", hit_device_any_sorted),
+    Kind("sample_waves6", sample_waves6, world="coincident64", sample=True),
+    Kind("sample_based", sample_based, sample=True),
+    Kind("update_refit_back", update_refit_back), Kind("update_rebuild_back", update_rebuild_back),
+    Kind("octree_device_rebuild", octree_device_rebuild))}
 
 #: the seeding of the kinds that return a frame of tmpt_render's
 IMAGE_SEED = {"row_stream": tm.SEED_ROW, "row_iter": tm.SEED_ROW, "row_mega": tm.SEED_ROW,
               "pixel_ordered": tm.SEED_PIXEL, "pixel_chains": tm.SEED_PIXEL, "pixel_wavefront": tm.SEED_PIXEL,
               "pixel_mega": tm.SEED_PIXEL, "sample_default": tm.SEED_SAMPLE, "sample_split_passes": tm.SEED_SAMPLE,
               "sample_fused_w4": tm.SEED_SAMPLE, "sample_deferred": tm.SEED_SAMPLE, "sample_soa_count": tm.SEED_SAMPLE,
-              "prepass_fallback": tm.SEED_SAMPLE}
+              "prepass_fallback": tm.SEED_SAMPLE, "sample_waves6": tm.SEED_SAMPLE}
+
+#: kind -> the public Scene methods and the options (include/tmpt.h "Scene options") it exercises;
+#: tests/test_call_kinds_cover.py holds toymeshpathtracer_amd.Scene's public methods to it
+COVERS = {
+    "row_stream": (("trace_image",), ("rowspec", "rowspec_stream")),
+    "row_iter": (("trace_image",), ("rowspec", "rowspec_stream")),
+    "row_mega": (("trace_image",), ()),
+    "pixel_ordered": (("trace_image",), ("pilot", "pixel_chains")),
+    "pixel_chains": (("trace_image",), ("pilot", "pixel_chains")),
+    "pixel_wavefront": (("trace_image",), ()),
+    "pixel_mega": (("trace_image",), ()),
+    "sample_default": (("trace_image",), ("cam_pre", "shadow_split", "shadow_split_pass", "path_waves")),
+    "sample_split_passes": (("trace_image",), ("cam_pre", "shadow_split", "shadow_split_pass", "path_waves")),
+    "sample_fused_w4": (("trace_image",), ("shadow_split", "cam_pre", "path_waves", "sample_block")),
+    "sample_deferred": (("trace_image",), ("tie_defer", "redo_inline", "shadow_split")),
+    "sample_soa_count": (("trace_image",), ()),
+    "aov": (("trace_aov",), ()),
+    "radiance_sample": (("trace_radiance",), ()),
+    "radiance_pixel": (("trace_radiance",), ()),
+    "adaptive": (("trace_adaptive",), ()),
+    "adaptive_nb": (("trace_adaptive",), ()),
+    "denoise": (("denoise",), ("denoise_lds",)),
+    "hit_closest": (("hit_scene_batch",), ()),
+    "hit_any_ranged": (("hit_scene_batch",), ()),
+    "camera_rays": (("camera_rays",), ()),
+    "radix_sort": (("radix_sort",), ()),
+    "octree_rebuild": (("build_octree", "dump_bvh"), ()),
+    "arg_errors": (("trace_image", "trace_adaptive"), ()),
+    "prepass_fallback": (("trace_image",), ("cam_pre", "cam_pre_max")),
+    "moments_uniform": (("trace_moments",), ()),
+    "moments_adaptive": (("trace_moments",), ()),
+    "guided": (("trace_guided",), ()),
+    "motion_host_prev": (("trace_motion",), ()),
+    "temporal": (("temporal",), ()),
+    "temporal_clip_aux": (("temporal_clip",), ()),
+    "sample_plan": (("sample_plan",), ()),
+    "denoise_moments": (("denoise_moments",), ("denoise_lds",)),
+    "hit_device_closest": (("hit_scene_device",), ("query_sort", "query_sorted")),
+    "hit_device_any_sorted": (("hit_scene_device",), ("query_sort", "query_sorted")),
+    "sample_waves6": (("trace_image",), ("cam_pre", "shadow_split", "shadow_split_pass", "path_waves", "path_waves_used")),
+    "sample_based": (("trace_image",), ("sample_base",)),
+    "update_refit_back": (("update", "dump_bvh", "dump_octree"), ("update_kind", "octree_build")),
+    "update_rebuild_back": (("update", "dump_bvh", "dump_octree"), ("update_kind", "octree_build")),
+    "octree_device_rebuild": (("build_octree", "dump_bvh", "dump_octree"), ("octree_build",)),
+}
 
 
 # ----------------------------------------------------------------------------- the pins
@@ -519,6 +898,45 @@ def _marker(name, res, size, world_name):
         assert s["node_visits"] > 0 and s["tri_tests"] > 0 and s["shadow_node_visits"] > 0
     elif name == "prepass_fallback":
         assert r["cam_rays_used"] == 0, r
+    elif name == "hit_device_closest":
+        assert r["query_sorted"] == 0, r
+    elif name == "hit_device_any_sorted":
+        assert r["query_sorted"] == 1, r
+    elif name == "sample_waves6":  # suzanne: flat triangles, no split to run at six waves (include/tmpt.h path_waves)
+        want = (6, 1) if world_name == "coincident64" else (5, 0)
+        assert (r["path_waves_used"], r["shadow_split_used"]) == want, r
+    elif name == "update_refit_back":
+        assert r["update_kind"] == 1 and r["raw_nodes"] == "unchanged", r
+    elif name == "update_rebuild_back":
+        assert r["update_kind"] == 2, r
+
+
+def _pin_moments(res, size, want):
+    """A trace_moments / trace_guided result against (spp map, radiance, rays, pass_pixels) of a
+    restatement over the frame's per-sample colours `col`: every output, the moments at each
+    pixel's own count."""
+    n_p, rad, total, pass_pixels, col = want
+    assert np.array_equal(res.arrays["spp_map"], n_p)
+    render_restate.same_bits(res.arrays["radiance"][..., :3], rad, "radiance")
+    assert (res.arrays["radiance"][..., 3].view(np.uint32) == f32(1).view(np.uint32)).all()
+    render_restate.same_bits(res.arrays["moments"], noise_aware_restate.moments_expect(col, n_p), "moments")
+    assert np.array_equal(res.arrays["image"], render_restate.pack(res.arrays["radiance"]))
+    assert res.rays == total and list(res.stats["pass_pixels"]) == pass_pixels
+    assert res.stats["samples"] == int(n_p.sum()) and res.stats["passes"] == len(pass_pixels)
+
+
+def _pin_dumps(res, wd):
+    """The BVH and octree dumps of a result against a fresh (host-built) scene's."""
+    with wd.scene() as sc:
+        first, oct_first = sc.dump_bvh(), sc.dump_octree()
+    assert np.array_equal(res.arrays["tris"], first["tris"])
+    assert np.array_equal(res.arrays["nodes"], bvh_check.canonical(first))
+    for key in ("nodes", "refs", "grid"):
+        d = first_difference(res.arrays["octree_" + key], oct_first[key])
+        assert d is None, f"octree {key}: {d}"
+    assert res.route["octree_info"] == tuple(oct_first["info"].items()) and oct_first["info"]["nodes"] > 0
+    if "info" in res.seen:
+        assert res.seen["info"] == first["info"], (res.seen["info"], first["info"])
 
 
 def _pin_adaptive(res, wd, size, radius, band_rows):
@@ -600,5 +1018,83 @@ def pin(name, res, world_name, size):
     elif name == "arg_errors":
         for key, text in ARG_ERRORS:
             assert text in res.route[key], (key, res.route[key])
+    elif name == "moments_uniform":
+        col, rays = sample_colours(wd.name, (w, h), spp + 8)
+        rad, total = render_restate.radiance_sum(col, rays, spp)
+        _pin_moments(res, size, (np.full((h, w), spp, np.int32), rad, total, [w * h], col))
+    elif name == "moments_adaptive":
+        col, rays = sample_colours(wd.name, (w, h), spp + 8)
+        want = adaptive_nb_restate.adaptive_nb_expect(col, rays, *ADAPTIVE, 1, 4)
+        _pin_moments(res, size, want + (col,))
+        assert res.stats["passes"] >= 2 and len(np.unique(want[0])) >= 2, (res.stats["passes"], np.unique(want[0]))
+    elif name == "guided":
+        col, rays = sample_colours(wd.name, (w, h), spp + 8)
+        prior = guided_restate.synthetic_prior(col[:, :, :8], GUIDED_N_MAX)
+        render_restate.same_bits(res.arrays["prior"], prior, "the prior the call was given")
+        want = guided_restate.guided_expect(col, rays, *GUIDED, prior)
+        _pin_moments(res, size, want + (col,))
+        assert (want[0] == GUIDED[0]).any() and (want[0] > GUIDED[0]).any(), np.unique(want[0])
+    elif name == "motion_host_prev":
+        want = motion_expect(wd, cam, wd.prev_camera(w, h).as_array(), w, h, wd.moved)
+        got = res.arrays["records"]
+        assert got.dtype == tm.MOTION_DTYPE and got.shape == want.shape
+        for field in tm.MOTION_DTYPE.names:
+            d = first_difference(np.ascontiguousarray(got[field]), np.ascontiguousarray(want[field]))
+            assert d is None, f"motion {field}: {d}"
+        assert res.rays == w * h and res.stats["extend_rays"] == w * h and res.stats["extend_launches"] == 1
+        assert ((want["flags"] & 2) != 0).any()
+    elif name == "temporal":
+        f = temporal_inputs(wd.name, tuple(size))
+        want = temporal_restate.blend(f["rad1"], f["mot1"], f["mot0"], f["rad0"])
+        render_restate.same_bits(res.arrays["frame"], want, "temporal")
+        assert np.array_equal(res.arrays["image"], temporal_restate.pack(want))
+        assert (want[..., 3] > 1).any() and (want[..., 3] == 1).any()  # histories taken up, and restarts
+    elif name == "temporal_clip_aux":
+        f = temporal_inputs(wd.name, tuple(size))
+        want, want_aux = temporal_clip_restate.clip(f["rad1"], f["mot1"], f["mot0"], f["rad0"], stat=f["stat"],
+                                                    aux=f["mom1"], aux_hist=f["mom0"], **CLIP)
+        render_restate.same_bits(res.arrays["frame"], want, "temporal_clip")
+        render_restate.same_bits(res.arrays["aux"], want_aux, "temporal_clip aux")
+        assert np.array_equal(res.arrays["image"], temporal_restate.pack(want))
+        assert (want[..., 3] > 1).any()
+    elif name == "sample_plan":
+        f = temporal_inputs(wd.name, tuple(size))
+        want = guided_restate.plan(f["mot1"], f["mot0"], f["mom0"])
+        render_restate.same_bits(res.arrays["prior"], want, "sample_plan")
+        assert (want[..., 3] > 0).any()  # not the null prior everywhere
+    elif name == "denoise_moments":
+        f = temporal_inputs(wd.name, tuple(size))
+        want = noise_aware_restate.np_denoise_moments(f["rad1"], f["aov1"], f["mom1"], spp, levels=DENOISE_LEVELS)
+        render_restate.same_bits(res.arrays["filtered"], want, "denoise_moments")
+        assert np.array_equal(res.arrays["image"], pack_denoised(want))
+    elif name == "hit_device_closest":
+        rays, (tmin, tmax), _ = wd.hit_rays
+        oids, ohits = wd.osc.hit_batch(rays, tmin, tmax)
+        ids, hits, uv = res.arrays["ids"], res.arrays["hits"], res.arrays["uv"]
+        assert np.array_equal(ids, oids), np.nonzero(ids != oids)[0][:8]
+        render_restate.same_bits(hits[ids >= 0], ohits[ids >= 0], "hit records")
+        assert not hits[ids < 0].any() and not uv[ids < 0].any()  # rows of missed rays are not written
+        render_restate.same_bits(uv, mt_uv(rays, wd.tris, ids), "(u, v) against Moller-Trumbore's for the returned triangle")
+        assert (ids >= 0).sum() >= 64 and (ids < 0).any()
+    elif name == "hit_device_any_sorted":
+        _, _, r8 = wd.hit_rays
+        want = np.zeros(len(r8), np.uint8)
+        for lo, hi in {(float(a), float(b)) for a, b in r8[:, 6:8]}:
+            sel = np.nonzero((r8[:, 6] == f32(lo)) & (r8[:, 7] == f32(hi)))[0]
+            want[sel] = wd.osc.hit_batch(r8[sel, :6], lo, hi)[0] >= 0
+        assert np.array_equal(res.arrays["hit"], want), np.nonzero(res.arrays["hit"] != want)[0][:8]
+        assert want.sum() >= 64 and (want == 0).any()
+    elif name == "sample_based":
+        col, rays = sample_colours(wd.name, (w, h), SAMPLE_BASE + spp)
+        rad, total = render_restate.radiance_sum(col[:, :, SAMPLE_BASE:], rays[:, :, SAMPLE_BASE:])
+        assert res.rays == total, (res.rays, total)
+        d = first_difference(res.arrays["image"], render_restate.pack(rad))
+        assert d is None, f"samples [{SAMPLE_BASE}, {SAMPLE_BASE + spp}): {d}"
+        assert not np.array_equal(res.arrays["image"], oracle_frame(wd.name, tuple(size), tm.SEED_SAMPLE)[0])
+    elif name in ("update_refit_back", "update_rebuild_back"):
+        _pin_dumps(res, wd)
+    elif name == "octree_device_rebuild":
+        _pin_dumps(res, wd)
+        assert res.stats["octree_flat"] == int((res.arrays["tris"][:-1, 9] & 1).sum())
     else:
         raise AssertionError(f"no pin for {name}")

@@ -6,7 +6,7 @@ where it was after every scene that is closed -- whatever calls the scene took,
 failed and fallen-back ones included -- and must not move when a call is
 repeated (the kept buffers are kept, the temporaries released).
 
-The calls are tests/call_kinds.py's 25 kinds on its two scene definitions at
+The calls are tests/call_kinds.py's 40 kinds on its two scene definitions at
 TINY (7x3x2) and BASE (40x22x6).  Every "does not fit" goes through an option
 cap; nothing exhausts device memory and no call here faults."""
 import gc

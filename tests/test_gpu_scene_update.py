@@ -311,6 +311,9 @@ def test_fresh_results_of_the_new_triangles(fresh, wname):
         assert fresh[wname]["sample_default"].seen["octree_flat"] == 0
 
 
+OWN_DUMP = ("octree_rebuild", "octree_device_rebuild", "update_refit_back")
+
+
 @pytest.mark.parametrize("mode", ["refit", "rebuild"])
 @pytest.mark.parametrize("wname", K.WORLDS)
 def test_every_kind_after_an_update(fresh, wname, mode):
@@ -326,10 +329,14 @@ def test_every_kind_after_an_update(fresh, wname, mode):
       sample_soa_count  node_visits, tri_tests, shadow_node_visits, shadow_tri_tests count the
                         steps of the walk over this tree; they must be positive.  Its bytes,
                         rays and every other statistic are compared with the fresh scene's
-      octree_rebuild    its result IS the BVH dump: it must be the scene's own dump from
+      octree_rebuild, octree_device_rebuild, update_refit_back (OWN_DUMP)
+                        their result holds the BVH dump: it must be the scene's own dump from
                         straight after the update (which test_refit_equals_the_restatement pins
                         to the restated refit), the flat marks the kind clears and sets again
-                        included; its statistic is compared with the fresh scene's"""
+                        included; the rest of the result (the statistic, the octree dump, the
+                        route markers) is compared with the fresh scene's.  update_rebuild_back
+                        builds the tree anew: its dump, and the dumps of the kinds after it,
+                        are the fresh scene's"""
     old, wd = K.world(wname), new_world(wname)
     bad = []
     visits = ("node_visits", "tri_tests", "shadow_node_visits", "shadow_tri_tests")
@@ -345,8 +352,10 @@ def test_every_kind_after_an_update(fresh, wname, mode):
                 assert all(got.stats[v] > 0 for v in visits), got.stats
                 keep = lambda r: Result(r.arrays, r.rays, {k: v for k, v in r.stats.items() if k not in visits}, r.route)
                 got, want = keep(got), keep(want)
-            if mode == "refit" and name == "octree_rebuild":
-                want = Result({"nodes": B.canonical(own), "tris": own["tris"]}, want.rays, want.stats, want.route)
+            if mode == "refit" and name in OWN_DUMP:
+                want = Result(dict(want.arrays, nodes=B.canonical(own), tris=own["tris"]), want.rays, want.stats, want.route)
+            if name == "update_rebuild_back":  # from here on the tree is a build of the new triangles
+                own = sc.dump_bvh()
             bad += [f"{name} after a {mode} on {wname}: {d}" for d in compare(got, want)]
     assert not bad, "\n".join(bad[:20])
 
