@@ -524,6 +524,108 @@ def _current_stream(device: int):
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _wait_stream(device: int, wait_stream):
+    """A method's ``wait_stream`` as a hipStream_t or None: "current" is torch's current stream."""
+    return _current_stream(device) if isinstance(wait_stream, str) else wait_stream
+
+
+def _tile_desc(device, out, wait_stream, width, height, spp, seed_mode, band_rows, shard, num_shards,
+               engine=ENGINE_PERSISTENT, flags=0, spp_begin=0, spp_count=0) -> _Desc:
+    """The descriptor of one shard's render; with ``out`` (device pointers) the
+    device form, ordered after ``wait_stream``."""
+    if out is None:
+        return _desc(width, height, spp, seed_mode, band_rows, shard, num_shards, engine, flags, spp_begin, spp_count)
+    return _desc(width, height, spp, seed_mode, band_rows, shard, num_shards, engine, flags | FLAG_OUT_DEVICE, spp_begin,
+                 spp_count, _wait_stream(device, wait_stream))
+
+
+def _device_form(d, device: int, wait_stream) -> None:
+    """A whole-frame descriptor's flags for device pointers, ordered after ``wait_stream``."""
+    d.flags = FLAG_OUT_DEVICE
+    ws = _wait_stream(device, wait_stream)
+    if ws is not None:
+        d.flags |= FLAG_WAIT_STREAM
+        d.wait_stream = int(ws)
+
+
+def _dptr(p):
+    """A device pointer (an int, or None) as a C argument."""
+    return None if p is None else ctypes.c_void_p(int(p))
+
+
+def _hptr(a):
+    """A numpy array (or None) as a C argument."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _out_frame(what: str, out, h: int, w: int, tail: str = "") -> np.ndarray:
+    """The float32 frame [h, w, 4] a whole-frame method writes: ``out``, checked, or a new one."""
+    res = np.zeros((h, w, 4), np.float32) if out is None else out
+    if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
+            and res.flags.c_contiguous):
+        raise ValueError(f"{what}: out must be a contiguous float32 array [h, w, 4]{tail}")
+    return res
+
+
+def _frames(what: str, frames, width, height, out, msg: str):
+    """The input frames of a whole-frame method, (value, dtype) each, the radiance
+    first.  Device pointers (ints) pass, ``width`` and ``height`` giving the size;
+    arrays are made contiguous and must be [h, w, 4] (float32) or [h, w] (records)
+    of one frame.  Returns (device form?, h, w, frames)."""
+    if isinstance(frames[0][0], int):
+        if width is None or height is None or out is None:
+            raise ValueError(f"{what}: device pointers need width, height and out")
+        return True, int(height), int(width), [f for f, _ in frames]
+    arrays = [np.ascontiguousarray(f, t) for f, t in frames]
+    h, w = arrays[0].shape[:2]
+    if any(a.shape != ((h, w, 4) if a.dtype == np.float32 else (h, w)) for a in arrays):
+        raise ValueError(f"{what}: {msg} of one whole frame")
+    return False, h, w, arrays
+
+
+def _filter_call(what: str, call, d, device: int, dev: bool, frames, out, wait_stream):
+    """``call(d, *inputs, float out, rgba8 out)`` of denoise, denoise_moments and
+    temporal, whose float output may be their radiance: returns (float32[h, w, 4],
+    rgba8[h, w, 4]), or (None, None) in the device form."""
+    if dev:
+        _device_form(d, device, wait_stream)
+        f32, u8 = out
+        _check(call(ctypes.byref(d), *[ctypes.c_void_p(int(p)) for p in frames], _dptr(f32), _dptr(u8)), what)
+        return None, None
+    res = _out_frame(what, out, d.height, d.width, " (it may be radiance itself)")
+    img = np.zeros((d.height, d.width, 4), np.uint8)
+    _check(call(ctypes.byref(d), *[_hptr(a) for a in frames], _hptr(res), _hptr(img)), what)
+    return res, img
+
+
+def _adaptive_desc(spp_min, spp_step, threshold, radius):
+    ad = _AdaptiveDesc()
+    ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
+    return ctypes.byref(ad)
+
+
+#: per output of the adaptive family, in ABI order: a pixel's shape and type
+_TILES = {"f32": ((4,), np.float32), "u8": ((4,), np.uint8), "i32": ((), np.int32)}
+
+
+def _adaptive_call(what: str, fn, head, kinds, d, out):
+    """The tail trace_adaptive, trace_moments and trace_guided share: ``head`` the
+    arguments before the outputs, ``kinds`` the outputs' :data:`_TILES`, ``out``
+    their device pointers or None (then arrays are made).  Returns (*arrays or
+    Nones, rays, info)."""
+    rays, inf = ctypes.c_uint64(), _AdaptiveInfo()
+    if out is not None:
+        arrays, ptrs = [None] * len(kinds), [_dptr(p) for p in out]
+    else:
+        rows = int(_tile_rows(ctypes.byref(d)))
+        arrays = [np.zeros((rows, d.width) + _TILES[k][0], _TILES[k][1]) for k in kinds]
+        ptrs = [_hptr(a) for a in arrays]
+    _check(fn(*head, *ptrs[:len(kinds)], ctypes.byref(inf), ctypes.byref(rays)), what)
+    info = {"passes": int(inf.passes), "samples": int(inf.samples),
+            "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
+    return (*arrays, int(rays.value), info)
+
+
 def tile_rows(width, height, band_rows=0, shard=0, num_shards=1) -> int:
     return int(_tile_rows(ctypes.byref(_desc(width, height, 1, 0, band_rows, shard, num_shards))))
 
@@ -702,7 +804,7 @@ class Scene:
         d = _HitDesc()
         d.n, d.ranged, d.any_hit = n, int(ranged), int(bool(any_hit))
         d.tmin, d.tmax = (0.0, 0.0) if ranged else (t_min, t_max)
-        ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
+        ws = _wait_stream(self.device, wait_stream)
         if ws is not None:
             d.flags |= FLAG_WAIT_STREAM
             d.wait_stream = int(ws)
@@ -739,24 +841,12 @@ class Scene:
         the frame is complete on the device.
         ``spp_begin``/``spp_count``: one progressive pass (persistent engine,
         pixel or sample seeding) -- see :meth:`trace_progressive`."""
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, seed_mode, band_rows, shard, num_shards, engine,
-                  (FLAG_COUNT_VISITS if count_visits else 0) | (FLAG_OUT_DEVICE if out is not None else 0),
-                  spp_begin, spp_count, ws)
-        rows = int(_tile_rows(ctypes.byref(d)))
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, seed_mode, band_rows, shard, num_shards, engine,
+                       FLAG_COUNT_VISITS if count_visits else 0, spp_begin, spp_count)
+        img = np.zeros((int(_tile_rows(ctypes.byref(d))), width, 4), np.uint8) if out is None else None
         rays = ctypes.c_uint64()
         cam = camera._to_c()
-        if out is not None:
-            _check(_render(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.c_void_p(int(out)),
-                           ctypes.byref(rays)), "trace_image")
-            return None, int(rays.value)
-        img = np.zeros((rows, width, 4), np.uint8)
-        _check(_render(self._h, ctypes.byref(cam), ctypes.byref(d), img.ctypes.data_as(ctypes.c_void_p),
+        _check(_render(self._h, ctypes.byref(cam), ctypes.byref(d), _hptr(img) if out is None else _dptr(out),
                        ctypes.byref(rays)), "trace_image")
         return img, int(rays.value)
 
@@ -789,23 +879,11 @@ class Scene:
         ``out`` (a device pointer with tile_rows*width*32 bytes, 16-byte aligned;
         then records is None) and ``wait_stream`` as in :meth:`trace_image`.
         Render option ``aov_group`` sets the lanes that share a pixel."""
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        rows = int(_tile_rows(ctypes.byref(d)))
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards)
+        rec = np.zeros((int(_tile_rows(ctypes.byref(d))), width), AOV_DTYPE) if out is None else None
         rays = ctypes.c_uint64()
         cam = camera._to_c()
-        if out is not None:
-            _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.c_void_p(int(out)),
-                               ctypes.byref(rays)), "trace_aov")
-            return None, int(rays.value)
-        rec = np.zeros((rows, width), AOV_DTYPE)
-        _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), rec.ctypes.data_as(ctypes.c_void_p),
+        _check(_render_aov(self._h, ctypes.byref(cam), ctypes.byref(d), _hptr(rec) if out is None else _dptr(out),
                            ctypes.byref(rays)), "trace_aov")
         return rec, int(rays.value)
 
@@ -820,27 +898,18 @@ class Scene:
         for the float tile (16-byte aligned), or a pair (float tile, rgba8 tile
         or None); the arrays returned are then None.  ``wait_stream`` as in
         :meth:`trace_image`."""
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, seed_mode, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        rows = int(_tile_rows(ctypes.byref(d)))
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, seed_mode, band_rows, shard, num_shards)
         rays = ctypes.c_uint64()
         cam = camera._to_c()
+        rad = img = None
         if out is not None:
             f32, u8 = out if isinstance(out, (tuple, list)) else (out, None)
-            _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.c_void_p(int(f32)),
-                                    None if u8 is None else ctypes.c_void_p(int(u8)), ctypes.byref(rays)),
-                   "trace_radiance")
-            return None, None, int(rays.value)
-        rad = np.zeros((rows, width, 4), np.float32)
-        img = np.zeros((rows, width, 4), np.uint8)
-        _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), rad.ctypes.data_as(ctypes.c_void_p),
-                                img.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)), "trace_radiance")
+            ptrs = ctypes.c_void_p(int(f32)), _dptr(u8)
+        else:
+            rows = int(_tile_rows(ctypes.byref(d)))
+            rad, img = np.zeros((rows, width, 4), np.float32), np.zeros((rows, width, 4), np.uint8)
+            ptrs = _hptr(rad), _hptr(img)
+        _check(_render_radiance(self._h, ctypes.byref(cam), ctypes.byref(d), *ptrs, ctypes.byref(rays)), "trace_radiance")
         return rad, img, int(rays.value)
 
     def trace_adaptive(self, camera: Camera, width: int, height: int, spp: int, spp_min: int = 0, spp_step: int = 0,
@@ -874,37 +943,10 @@ class Scene:
         fn = _sig("tmpt_render_adaptive", ctypes.c_int,
                   [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_AdaptiveInfo), _u64p])
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        ad = _AdaptiveDesc()
-        ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
-        rows = int(_tile_rows(ctypes.byref(d)))
-        rays = ctypes.c_uint64()
-        inf = _AdaptiveInfo()
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards)
         cam = camera._to_c()
-
-        def info():
-            return {"passes": int(inf.passes), "samples": int(inf.samples),
-                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
-
-        if out is not None:
-            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
-            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.byref(ad), ptr[0], ptr[1], ptr[2],
-                      ctypes.byref(inf), ctypes.byref(rays)), "trace_adaptive")
-            return None, None, None, int(rays.value), info()
-        rad = np.zeros((rows, width, 4), np.float32)
-        img = np.zeros((rows, width, 4), np.uint8)
-        cnt = np.zeros((rows, width), np.int32)
-        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ctypes.byref(ad), rad.ctypes.data_as(ctypes.c_void_p),
-                  img.ctypes.data_as(ctypes.c_void_p), cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf),
-                  ctypes.byref(rays)), "trace_adaptive")
-        return rad, img, cnt, int(rays.value), info()
+        head = (self._h, ctypes.byref(cam), ctypes.byref(d), _adaptive_desc(spp_min, spp_step, threshold, radius))
+        return _adaptive_call("trace_adaptive", fn, head, ("f32", "u8", "i32"), d, out)
 
     def denoise(self, radiance, aov, spp: int, levels: int = 0, normal_exp: int = -1, sigma_depth: float = 0.0,
                 sigma_direct: float = 0.0, out=None, width: Optional[int] = None, height: Optional[int] = None,
@@ -920,40 +962,13 @@ class Scene:
         device pointers (ints, 16-byte aligned), ``width`` and ``height`` give
         the size and ``out`` = (float frame pointer or None, rgba8 pointer or
         None) -- the float output may be the input itself; returns (None, None)."""
-        dev = isinstance(radiance, int)
+        dev, h, w, frames = _frames("denoise", [(radiance, np.float32), (aov, AOV_DTYPE)], width, height, out,
+                                    "radiance [h, w, 4] and aov [h, w]")
         d = _DenoiseDesc()
-        if dev:
-            if width is None or height is None or out is None:
-                raise ValueError("denoise: device pointers need width, height and out")
-            h, w = int(height), int(width)
-        else:
-            radiance = np.ascontiguousarray(radiance, np.float32)
-            aov = np.ascontiguousarray(aov, AOV_DTYPE)
-            h, w = radiance.shape[:2]
-            if radiance.shape != (h, w, 4) or aov.shape != (h, w):
-                raise ValueError("denoise: radiance [h, w, 4] and aov [h, w] of one whole frame")
         d.width, d.height, d.spp, d.levels, d.normal_exp = w, h, spp, levels, normal_exp
         d.sigma_depth, d.sigma_direct = sigma_depth, sigma_direct
-        if dev:
-            d.flags = FLAG_OUT_DEVICE
-            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
-            if ws is not None:
-                d.flags |= FLAG_WAIT_STREAM
-                d.wait_stream = int(ws)
-            f32, u8 = out
-            _check(_denoise(self._h, ctypes.byref(d), ctypes.c_void_p(radiance), ctypes.c_void_p(int(aov)),
-                            None if f32 is None else ctypes.c_void_p(int(f32)),
-                            None if u8 is None else ctypes.c_void_p(int(u8))), "denoise")
-            return None, None
-        res = np.zeros((h, w, 4), np.float32) if out is None else out
-        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
-                and res.flags.c_contiguous):
-            raise ValueError("denoise: out must be a contiguous float32 array [h, w, 4] (it may be radiance itself)")
-        img = np.zeros((h, w, 4), np.uint8)
-        _check(_denoise(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
-                        aov.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
-                        img.ctypes.data_as(ctypes.c_void_p)), "denoise")
-        return res, img
+        return _filter_call("denoise", lambda d, *p: _denoise(self._h, d, *p), d, self.device, dev, frames, out,
+                            wait_stream)
 
     def trace_moments(self, camera: Camera, width: int, height: int, spp: int, spp_min: Optional[int] = None,
                       spp_step: int = 0, threshold: float = -1.0, radius: int = 0, band_rows: int = 0, shard: int = 0,
@@ -975,41 +990,11 @@ class Scene:
                   [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(_AdaptiveInfo),
                    _u64p])
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        ad = None
-        if spp_min is not None:
-            ad = _AdaptiveDesc()
-            ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
-            ad = ctypes.byref(ad)
-        rows = int(_tile_rows(ctypes.byref(d)))
-        rays = ctypes.c_uint64()
-        inf = _AdaptiveInfo()
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards)
         cam = camera._to_c()
-
-        def info():
-            return {"passes": int(inf.passes), "samples": int(inf.samples),
-                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
-
-        if out is not None:
-            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
-            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, ptr[0], ptr[1], ptr[2], ptr[3],
-                      ctypes.byref(inf), ctypes.byref(rays)), "trace_moments")
-            return None, None, None, None, int(rays.value), info()
-        rad = np.zeros((rows, width, 4), np.float32)
-        mom = np.zeros((rows, width, 4), np.float32)
-        img = np.zeros((rows, width, 4), np.uint8)
-        cnt = np.zeros((rows, width), np.int32)
-        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, rad.ctypes.data_as(ctypes.c_void_p),
-                  mom.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p),
-                  cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf), ctypes.byref(rays)), "trace_moments")
-        return rad, mom, img, cnt, int(rays.value), info()
+        ad = None if spp_min is None else _adaptive_desc(spp_min, spp_step, threshold, radius)
+        return _adaptive_call("trace_moments", fn, (self._h, ctypes.byref(cam), ctypes.byref(d), ad),
+                              ("f32", "f32", "u8", "i32"), d, out)
 
     def denoise_moments(self, radiance, aov, moments, spp: int, shrink: float = 0.0, levels: int = 0,
                         normal_exp: int = -1, sigma_depth: float = 0.0, sigma_direct: float = 0.0, out=None,
@@ -1026,42 +1011,13 @@ class Scene:
         fn = _sig("tmpt_denoise_moments", ctypes.c_int,
                   [ctypes.c_void_p, ctypes.POINTER(_DenoiseDesc), ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
-        dev = isinstance(radiance, int)
+        dev, h, w, frames = _frames("denoise_moments", [(radiance, np.float32), (aov, AOV_DTYPE), (moments, np.float32)],
+                                    width, height, out, "radiance and moments [h, w, 4] and aov [h, w]")
         d = _DenoiseDesc()
-        if dev:
-            if width is None or height is None or out is None:
-                raise ValueError("denoise_moments: device pointers need width, height and out")
-            h, w = int(height), int(width)
-        else:
-            radiance = np.ascontiguousarray(radiance, np.float32)
-            aov = np.ascontiguousarray(aov, AOV_DTYPE)
-            moments = np.ascontiguousarray(moments, np.float32)
-            h, w = radiance.shape[:2]
-            if radiance.shape != (h, w, 4) or aov.shape != (h, w) or moments.shape != (h, w, 4):
-                raise ValueError("denoise_moments: radiance and moments [h, w, 4] and aov [h, w] of one whole frame")
         d.width, d.height, d.spp, d.levels, d.normal_exp = w, h, spp, levels, normal_exp
         d.sigma_depth, d.sigma_direct = sigma_depth, sigma_direct
-        if dev:
-            d.flags = FLAG_OUT_DEVICE
-            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
-            if ws is not None:
-                d.flags |= FLAG_WAIT_STREAM
-                d.wait_stream = int(ws)
-            f32, u8 = out
-            _check(fn(self._h, ctypes.byref(d), shrink, ctypes.c_void_p(radiance), ctypes.c_void_p(int(aov)),
-                      ctypes.c_void_p(int(moments)), None if f32 is None else ctypes.c_void_p(int(f32)),
-                      None if u8 is None else ctypes.c_void_p(int(u8))), "denoise_moments")
-            return None, None
-        res = np.zeros((h, w, 4), np.float32) if out is None else out
-        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
-                and res.flags.c_contiguous):
-            raise ValueError("denoise_moments: out must be a contiguous float32 array [h, w, 4] (it may be radiance "
-                             "itself)")
-        img = np.zeros((h, w, 4), np.uint8)
-        _check(fn(self._h, ctypes.byref(d), shrink, radiance.ctypes.data_as(ctypes.c_void_p),
-                  aov.ctypes.data_as(ctypes.c_void_p), moments.ctypes.data_as(ctypes.c_void_p),
-                  res.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p)), "denoise_moments")
-        return res, img
+        return _filter_call("denoise_moments", lambda d, *p: fn(self._h, d, shrink, *p), d, self.device, dev, frames, out,
+                            wait_stream)
 
     def trace_motion(self, camera: Camera, prev_camera: Camera, width: int, height: int, prev_triangles=None,
                      band_rows: int = 0, shard: int = 0, num_shards: int = 1, out=None, wait_stream="current"):
@@ -1080,29 +1036,20 @@ class Scene:
         fn = _sig("tmpt_render_motion", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_Camera),
                                                        ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int32,
                                                        ctypes.POINTER(_Desc), ctypes.c_void_p, _u64p])
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, 1, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        rows = int(_tile_rows(ctypes.byref(d)))
+        d = _tile_desc(self.device, out, wait_stream, width, height, 1, SEED_SAMPLE, band_rows, shard, num_shards)
         rays = ctypes.c_uint64()
         cam, pcam = camera._to_c(), prev_camera._to_c()
         if out is not None:
-            prev = None if prev_triangles is None else ctypes.c_void_p(int(prev_triangles))
-            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), prev, self.n, ctypes.byref(d),
+            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), _dptr(prev_triangles), self.n, ctypes.byref(d),
                       ctypes.c_void_p(int(out)), ctypes.byref(rays)), "trace_motion")
             return None, int(rays.value)
-        prev, pn = None, 0
+        pt, pn = None, 0
         if prev_triangles is not None:
             pt = np.ascontiguousarray(np.asarray(prev_triangles, np.float32).reshape(-1, 9))
-            prev, pn = pt.ctypes.data_as(ctypes.c_void_p), pt.shape[0]
-        rec = np.zeros((rows, width), MOTION_DTYPE)
-        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), prev, pn, ctypes.byref(d),
-                  rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)), "trace_motion")
+            pn = pt.shape[0]
+        rec = np.zeros((int(_tile_rows(ctypes.byref(d))), width), MOTION_DTYPE)
+        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(pcam), _hptr(pt), pn, ctypes.byref(d), _hptr(rec),
+                  ctypes.byref(rays)), "trace_motion")
         return rec, int(rays.value)
 
     def temporal(self, radiance, motion, prev_motion, history, n_max: float = 0.0, sigma_depth: float = 0.0,
@@ -1124,45 +1071,12 @@ class Scene:
         fn = _sig("tmpt_temporal", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_TemporalDesc), ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p])
-        dev = isinstance(radiance, int)
+        dev, h, w, frames = _frames("temporal", [(radiance, np.float32), (motion, MOTION_DTYPE),
+                                                 (prev_motion, MOTION_DTYPE), (history, np.float32)], width, height, out,
+                                    "radiance and history [h, w, 4], motion and prev_motion [h, w]")
         d = _TemporalDesc()
-        if dev:
-            if width is None or height is None or out is None:
-                raise ValueError("temporal: device pointers need width, height and out")
-            h, w = int(height), int(width)
-        else:
-            radiance = np.ascontiguousarray(radiance, np.float32)
-            history = np.ascontiguousarray(history, np.float32)
-            motion = np.ascontiguousarray(motion, MOTION_DTYPE)
-            prev_motion = np.ascontiguousarray(prev_motion, MOTION_DTYPE)
-            h, w = radiance.shape[:2]
-            if (radiance.shape != (h, w, 4) or history.shape != (h, w, 4) or motion.shape != (h, w)
-                    or prev_motion.shape != (h, w)):
-                raise ValueError("temporal: radiance and history [h, w, 4], motion and prev_motion [h, w] of one "
-                                 "whole frame")
         d.width, d.height, d.n_max, d.sigma_depth = w, h, n_max, sigma_depth
-        if dev:
-            d.flags = FLAG_OUT_DEVICE
-            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
-            if ws is not None:
-                d.flags |= FLAG_WAIT_STREAM
-                d.wait_stream = int(ws)
-            f32, u8 = out
-            _check(fn(self._h, ctypes.byref(d), ctypes.c_void_p(radiance), ctypes.c_void_p(int(motion)),
-                      ctypes.c_void_p(int(prev_motion)), ctypes.c_void_p(int(history)),
-                      None if f32 is None else ctypes.c_void_p(int(f32)),
-                      None if u8 is None else ctypes.c_void_p(int(u8))), "temporal")
-            return None, None
-        res = np.zeros((h, w, 4), np.float32) if out is None else out
-        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
-                and res.flags.c_contiguous):
-            raise ValueError("temporal: out must be a contiguous float32 array [h, w, 4] (it may be radiance itself)")
-        img = np.zeros((h, w, 4), np.uint8)
-        _check(fn(self._h, ctypes.byref(d), radiance.ctypes.data_as(ctypes.c_void_p),
-                  motion.ctypes.data_as(ctypes.c_void_p), prev_motion.ctypes.data_as(ctypes.c_void_p),
-                  history.ctypes.data_as(ctypes.c_void_p), res.ctypes.data_as(ctypes.c_void_p),
-                  img.ctypes.data_as(ctypes.c_void_p)), "temporal")
-        return res, img
+        return _filter_call("temporal", lambda d, *p: fn(self._h, d, *p), d, self.device, dev, frames, out, wait_stream)
 
     def temporal_clip(self, radiance, motion, prev_motion, history, gamma: float = 0.0, radius: int = 0,
                       n_max: float = 0.0, sigma_depth: float = 0.0, stat=None, aux=None, aux_history=None, out=None,
@@ -1188,50 +1102,27 @@ class Scene:
                   + [ctypes.c_void_p] * 10)
         if (aux is None) != (aux_history is None):
             raise ValueError("temporal_clip: aux and aux_history go together")
-        dev = isinstance(radiance, int)
+        given = {"radiance": (radiance, np.float32), "motion": (motion, MOTION_DTYPE),
+                 "prev_motion": (prev_motion, MOTION_DTYPE), "history": (history, np.float32), "stat": (stat, np.float32),
+                 "aux": (aux, np.float32), "aux_history": (aux_history, np.float32)}
+        given = {k: v for k, v in given.items() if v[0] is not None}  # stat and the aux pair may be absent
+        dev, h, w, frames = _frames("temporal_clip", list(given.values()), width, height, out,
+                                    "radiance, history, stat, aux and aux_history [h, w, 4], motion and "
+                                    "prev_motion [h, w]")
+        f = dict(zip(given, frames))
         d = _TemporalClipDesc()
-        if dev:
-            if width is None or height is None or out is None:
-                raise ValueError("temporal_clip: device pointers need width, height and out")
-            h, w = int(height), int(width)
-        else:
-            radiance = np.ascontiguousarray(radiance, np.float32)
-            history = np.ascontiguousarray(history, np.float32)
-            motion = np.ascontiguousarray(motion, MOTION_DTYPE)
-            prev_motion = np.ascontiguousarray(prev_motion, MOTION_DTYPE)
-            h, w = radiance.shape[:2]
-            frames = [radiance, history]
-            if stat is not None:
-                stat = np.ascontiguousarray(stat, np.float32)
-                frames.append(stat)
-            if aux is not None:
-                aux = np.ascontiguousarray(aux, np.float32)
-                aux_history = np.ascontiguousarray(aux_history, np.float32)
-                frames += [aux, aux_history]
-            if (any(f.shape != (h, w, 4) for f in frames) or motion.shape != (h, w) or prev_motion.shape != (h, w)):
-                raise ValueError("temporal_clip: radiance, history, stat, aux and aux_history [h, w, 4], motion and "
-                                 "prev_motion [h, w] of one whole frame")
         d.width, d.height, d.n_max, d.sigma_depth, d.gamma, d.radius = w, h, n_max, sigma_depth, gamma, radius
-        ptr = lambda p: None if p is None else ctypes.c_void_p(int(p))
+        res = img = aux_res = None
         if dev:
-            d.flags = FLAG_OUT_DEVICE
-            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
-            if ws is not None:
-                d.flags |= FLAG_WAIT_STREAM
-                d.wait_stream = int(ws)
-            f32, u8, ao = out
-            _check(fn(self._h, ctypes.byref(d), ptr(radiance), ptr(stat), ptr(motion), ptr(prev_motion), ptr(history),
-                      ptr(aux), ptr(aux_history), ptr(ao), ptr(f32), ptr(u8)), "temporal_clip")
-            return None, None, None
-        res = np.zeros((h, w, 4), np.float32) if out is None else out
-        if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
-                and res.flags.c_contiguous):
-            raise ValueError("temporal_clip: out must be a contiguous float32 array [h, w, 4]")
-        img = np.zeros((h, w, 4), np.uint8)
-        aux_res = None if aux is None else np.zeros((h, w, 4), np.float32)
-        host = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-        _check(fn(self._h, ctypes.byref(d), host(radiance), host(stat), host(motion), host(prev_motion), host(history),
-                  host(aux), host(aux_history), host(aux_res), host(res), host(img)), "temporal_clip")
+            _device_form(d, self.device, wait_stream)
+            ptr, (f32, u8, ao) = _dptr, out
+        else:
+            ptr, f32, u8 = _hptr, _out_frame("temporal_clip", out, h, w), np.zeros((h, w, 4), np.uint8)
+            ao = None if aux is None else np.zeros((h, w, 4), np.float32)
+            res, img, aux_res = f32, u8, ao
+        order = ("radiance", "stat", "motion", "prev_motion", "history", "aux", "aux_history")  # the C signature's
+        frames = [f.get(k) for k in order] + [ao, f32, u8]
+        _check(fn(self._h, ctypes.byref(d), *[ptr(x) for x in frames]), "temporal_clip")
         return res, img, aux_res
 
     def sample_plan(self, motion, prev_motion, moments_history, n_max: float = 0.0, sigma_depth: float = 0.0, out=None,
@@ -1292,18 +1183,11 @@ class Scene:
             if moments_history.shape != (h, w, 4) or motion.shape != (h, w) or prev_motion.shape != (h, w):
                 raise ValueError("sample_plan: moments_history [h, w, 4], motion and prev_motion [h, w] of one whole "
                                  "frame")
-            res = np.zeros((h, w, 4), np.float32) if out is None else out
-            if not (isinstance(res, np.ndarray) and res.dtype == np.float32 and res.shape == (h, w, 4)
-                    and res.flags.c_contiguous):
-                raise ValueError("sample_plan: out must be a contiguous float32 array [h, w, 4]")
+            res = _out_frame("sample_plan", out, h, w)
             ptrs = [a.ctypes.data for a in (motion, prev_motion, moments_history, res)]
         d.width, d.height, d.n_max, d.sigma_depth = w, h, n_max, sigma_depth
         if dev:
-            d.flags = FLAG_OUT_DEVICE
-            ws = _current_stream(self.device) if isinstance(wait_stream, str) else wait_stream
-            if ws is not None:
-                d.flags |= FLAG_WAIT_STREAM
-                d.wait_stream = int(ws)
+            _device_form(d, self.device, wait_stream)
         _check(fn(self._h, ctypes.byref(d), *[ctypes.c_void_p(p) for p in ptrs]), "sample_plan")
         return res
 
@@ -1329,15 +1213,7 @@ class Scene:
                   [ctypes.c_void_p, ctypes.POINTER(_Camera), ctypes.POINTER(_Desc), ctypes.POINTER(_AdaptiveDesc),
                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                    ctypes.POINTER(_AdaptiveInfo), _u64p])
-        if out is None:
-            ws = None
-        elif isinstance(wait_stream, str):
-            ws = _current_stream(self.device)
-        else:
-            ws = wait_stream
-        d = _desc(width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards, ENGINE_PERSISTENT,
-                  FLAG_OUT_DEVICE if out is not None else 0, 0, 0, ws)
-        rows = int(_tile_rows(ctypes.byref(d)))
+        d = _tile_desc(self.device, out, wait_stream, width, height, spp, SEED_SAMPLE, band_rows, shard, num_shards)
         tile = None  # the prior's rows of this shard, kept alive over the call
         if prior is not None:
             if tuple(prior.shape) != (height, width, 4):
@@ -1360,34 +1236,12 @@ class Scene:
         p_ptr = None
         if tile is not None:
             p_ptr = ctypes.c_void_p(tile.data_ptr() if hasattr(tile, "data_ptr") else tile.ctypes.data)
-        ad = None
-        if spp_min is not None:
-            ad = _AdaptiveDesc()
-            ad.spp_min, ad.spp_step, ad.threshold, ad.radius = spp_min, spp_step, threshold, radius
-            ad = ctypes.byref(ad)
-        rays = ctypes.c_uint64()
-        inf = _AdaptiveInfo()
+        ad = None if spp_min is None else _adaptive_desc(spp_min, spp_step, threshold, radius)
         cam = camera._to_c()
-
-        def info():
-            return {"passes": int(inf.passes), "samples": int(inf.samples),
-                    "pass_pixels": [int(v) for v in inf.pass_pixels[:inf.passes]]}
-
-        if out is not None:
-            if tile is not None and ws is None:
-                torch.cuda.current_stream(self.device).synchronize()  # the gathered rows are ready
-            ptr = [None if p is None else ctypes.c_void_p(int(p)) for p in out]
-            _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, p_ptr, ptr[0], ptr[1], ptr[2], ptr[3],
-                      ctypes.byref(inf), ctypes.byref(rays)), "trace_guided")
-            return None, None, None, None, int(rays.value), info()
-        rad = np.zeros((rows, width, 4), np.float32)
-        mom = np.zeros((rows, width, 4), np.float32)
-        img = np.zeros((rows, width, 4), np.uint8)
-        cnt = np.zeros((rows, width), np.int32)
-        _check(fn(self._h, ctypes.byref(cam), ctypes.byref(d), ad, p_ptr, rad.ctypes.data_as(ctypes.c_void_p),
-                  mom.ctypes.data_as(ctypes.c_void_p), img.ctypes.data_as(ctypes.c_void_p),
-                  cnt.ctypes.data_as(ctypes.c_void_p), ctypes.byref(inf), ctypes.byref(rays)), "trace_guided")
-        return rad, mom, img, cnt, int(rays.value), info()
+        if out is not None and tile is not None and not d.flags & FLAG_WAIT_STREAM:
+            torch.cuda.current_stream(self.device).synchronize()  # the gathered rows are ready
+        return _adaptive_call("trace_guided", fn, (self._h, ctypes.byref(cam), ctypes.byref(d), ad, p_ptr),
+                              ("f32", "f32", "u8", "i32"), d, out)
 
     def camera_rays(self, camera: Camera, width: int, height: int, spp: int, spp_begin: int = 0,
                     spp_count: int = 0, band_rows: int = 0, shard: int = 0, num_shards: int = 1) -> np.ndarray:

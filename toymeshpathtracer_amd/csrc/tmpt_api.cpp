@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <new>
+#include <stdexcept>
 #include <chrono>
 #include <string>
 #include <thread>
@@ -177,6 +178,33 @@ const OptionDef* find_option(const char* key)
         if (strcmp(d.name, key) == 0) return &d;
     return nullptr;
 }
+
+// The read-only keys of tmpt_scene_get_option, looked up before kOptions
+// (bvh_cost, computed on first use, is the call's own case).
+struct ReadOnlyKey {
+    const char* name;
+    double (*get)(const Scene&);
+};
+const ReadOnlyKey kReadOnly[] = {
+    // the scene's layout under pop_key_cap
+    {"pop_key_bits", [](const Scene& s) { return (double)pop_key_bits(s.bvh.link_bits, s.opt.pop_key_cap); }},
+    // of the last render: it ran the camera pre-pass, the passes the shadow split ran, the path
+    // kernel's waves per SIMD, k_split_resolve's time
+    {"cam_rays_used", [](const Scene& s) { return (double)s.cam_rays_used; }},
+    {"shadow_split_used", [](const Scene& s) { return (double)s.split_used; }},
+    {"path_waves_used", [](const Scene& s) { return (double)s.path_waves_used; }},
+    {"shadow_split_resolve_ms", [](const Scene& s) { return (double)s.split_resolve_ms; }},
+    // of the last tmpt_scene_update: 0 none since creation, 1 refit, 2 rebuild; its device time
+    {"update_kind", [](const Scene& s) { return (double)s.update_kind; }},
+    {"update_ms", [](const Scene& s) { return (double)s.update_ms; }},
+    // the process's live tmpt_device.h owners
+    {"live_device_objects", [](const Scene&) { return (double)g_live_device_objects.load(); }},
+    // of the last tmpt_scene_hit_device: device time, the keys + sort share, chunks, whether it sorted
+    {"query_ms", [](const Scene& s) { return (double)s.query_ms; }},
+    {"query_sort_ms", [](const Scene& s) { return (double)s.query_sort_ms; }},
+    {"query_chunks", [](const Scene& s) { return (double)s.query_chunks; }},
+    {"query_sorted", [](const Scene& s) { return (double)s.query_sorted; }},
+};
 }  // namespace
 
 int options_set(Options& o, const char* key, double v, bool allow_build)
@@ -301,6 +329,226 @@ int bad(const char* msg)
 {
     set_error(msg);
     return -22;
+}
+
+// "<call>: <what>": an argument refused (-22), a device operation failed (-1)
+int no(const char* name, const std::string& what) { return bad((std::string(name) + ": " + what).c_str()); }
+int failed(const char* name, const char* what) { return (set_error(std::string(name) + ": " + what), -1); }
+
+// ---------------------------------------------------------------- descriptor checks
+// main.cpp:258-280 argument ranges: a frame's sides, and its spp where the call reads one
+bool bad_side(int32_t v) { return v < 1 || v > 10000; }
+int check_frame(const char* name, int32_t width, int32_t height, const int32_t* spp)
+{
+    if (bad_side(width)) return no(name, "invalid width");
+    if (bad_side(height)) return no(name, "invalid height");
+    if (spp && (*spp < 1 || *spp > 1024)) return no(name, "invalid samplesPerPixel");
+    return 0;
+}
+
+// What one frame call asks of its tmpt_render_desc.  A null message: the field is not looked at.
+enum SppRule {
+    kSppUnread,       // spp_begin / spp_count are not looked at
+    kSppRange,        // any pass inside 0 .. spp
+    kSppProgressive,  // that, and a partial pass needs the persistent engine and pixel or sample seeding
+    kSppZero,         // both 0: `spp_msg` says why
+};
+struct DescRules {
+    bool spp;                // spp is read
+    unsigned seeds;          // bit TMPT_SEED_* set: allowed
+    const char* seed_msg;    // the refusal, with the call's own reason
+    unsigned engines;        // bit TMPT_ENGINE_* set: allowed
+    const char* engine_msg;
+    SppRule spp_rule;
+    const char* spp_msg;
+    bool no_visits;          // TMPT_FLAG_COUNT_VISITS is refused
+};
+constexpr unsigned kSeedAny = 1u << TMPT_SEED_ROW | 1u << TMPT_SEED_PIXEL | 1u << TMPT_SEED_SAMPLE;
+constexpr unsigned kSeedSample = 1u << TMPT_SEED_SAMPLE;
+constexpr unsigned kEngineAny = 1u << TMPT_ENGINE_WAVEFRONT | 1u << TMPT_ENGINE_MEGAKERNEL | 1u << TMPT_ENGINE_PERSISTENT;
+constexpr unsigned kEnginePersistent = 1u << TMPT_ENGINE_PERSISTENT;
+constexpr const char* kMustPersist = "engine must be TMPT_ENGINE_PERSISTENT";
+
+// The checks of a render descriptor, in the order every call has had them: sizes,
+// seeding, engine, the sample range, the visit flag.  The shard comes before the
+// sample range where a pass is allowed and last where it is not.
+int check_render_desc(const char* name, const tmpt_render_desc* d, const DescRules& r)
+{
+    if (int rc = check_frame(name, d->width, d->height, r.spp ? &d->spp : nullptr)) return rc;
+    const auto allowed = [](unsigned mask, int32_t v) { return v >= 0 && v < 32 && (mask >> v & 1u) != 0; };
+    if (r.seed_msg && !allowed(r.seeds, d->seed_mode)) return no(name, r.seed_msg);
+    if (r.engine_msg && !allowed(r.engines, d->engine)) return no(name, r.engine_msg);
+    const bool bad_shard = d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards);
+    if (r.spp_rule != kSppZero && bad_shard) return no(name, "invalid shard");
+    if (r.spp_rule == kSppZero) {
+        if (d->spp_begin != 0 || d->spp_count != 0) return no(name, r.spp_msg);
+    } else if (r.spp_rule != kSppUnread) {
+        if (d->spp_begin < 0 || d->spp_begin >= d->spp || d->spp_count < 0 || d->spp_count > d->spp - d->spp_begin)
+            return no(name, "invalid spp_begin / spp_count");
+        const bool progressive = d->spp_begin > 0 || (d->spp_count > 0 && d->spp_count < d->spp);
+        if (r.spp_rule == kSppProgressive && progressive &&
+            (d->engine != TMPT_ENGINE_PERSISTENT || d->seed_mode == TMPT_SEED_ROW))
+            return no(name, "progressive spp needs the persistent engine and pixel or sample seeding");
+    }
+    if (r.no_visits && (d->flags & TMPT_FLAG_COUNT_VISITS)) return no(name, "TMPT_FLAG_COUNT_VISITS is not supported");
+    if (bad_shard) return no(name, "invalid shard");
+    return 0;
+}
+
+// Device pointers: each of `quads` on 16 bytes, each of `words` on 4 (a null pointer passes)
+bool aligned(std::initializer_list<const void*> quads, std::initializer_list<const void*> words = {})
+{
+    uintptr_t q = 0, w = 0;
+    for (const void* p : quads) q |= reinterpret_cast<uintptr_t>(p);
+    for (const void* p : words) w |= reinterpret_cast<uintptr_t>(p);
+    return (q & 15u) == 0 && (w & 3u) == 0;
+}
+
+// The whole-frame descriptors (tmpt_denoise, tmpt_temporal, tmpt_sample_plan, tmpt_temporal_clip)
+int check_frame_flags(const char* name, int32_t flags)
+{
+    return flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM) ? no(name, "unknown flag") : 0;
+}
+
+// tmpt_temporal's defaults ("Temporal accumulation"), tmpt_sample_plan's too;
+// tmpt_denoise_moments' default shrink and tmpt_temporal_clip's defaults: the grid points the rules of
+// tools/noise_aware_sweep.py and tools/temporal_clip_sweep.py chose (profiles/temporal_clip_sweep.log,
+// DESIGN.md section 4, "Noise-aware filter" and "History clipping")
+constexpr float kTemporalNMax = 3.0f, kTemporalSigmaDepth = 0.05f;
+constexpr float kShrinkDefault = 2.0f;
+constexpr float kClipNMax = 3.0f, kClipGamma = 0.5f;
+constexpr int32_t kClipRadius = 1;
+
+// n_max and sigma_depth of a temporal descriptor: 0 takes the default, then the ranges
+int temporal_defaults(const char* name, float n_max_default, float* n_max, float* sigma_depth)
+{
+    if (*n_max == 0.0f) *n_max = n_max_default;
+    if (*sigma_depth == 0.0f) *sigma_depth = kTemporalSigmaDepth;
+    if (!(*n_max >= 1.0f) || !(*n_max <= 3.0e38f)) return no(name, "n_max must be finite and at least 1 (0 = default)");
+    if (!(*sigma_depth >= 0.0f) || !(*sigma_depth <= 3.0e38f))
+        return no(name, "sigma_depth must be finite and not negative (0 = default)");
+    return 0;
+}
+
+// No output frame may overlap an input frame whose neighbours the kernel reads (frames of
+// `bytes` each; a null frame is absent)
+struct NamedFrame {
+    const void* p;
+    const char* name;
+};
+int check_overlap(const char* name, size_t bytes, std::initializer_list<NamedFrame> outs,
+                  std::initializer_list<NamedFrame> ins)
+{
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    for (const NamedFrame& o : outs)
+        for (const NamedFrame& i : ins)
+            if (o.p && i.p && at(o.p) < at(i.p) + bytes && at(i.p) < at(o.p) + bytes)
+                return no(name, std::string(o.name) + " overlaps " + i.name + " (its neighbours are read)");
+    return 0;
+}
+
+// ---------------------------------------------------------------- staging
+// A frame call's pointers are the caller's device memory (TMPT_FLAG_OUT_DEVICE: they
+// pass through, nothing is copied) or host memory: then every frame gets a slot of
+// one device buffer -- the call's own, freed on return, or one the scene keeps and
+// grows -- inputs are copied in, the kernels run on the slots, and fetch() copies
+// the outputs back.  The caller reserves room for the frames it will name (a null
+// one is absent and takes none) before it names them; slots start on 16 bytes.
+class Staging {
+public:
+    struct Frame {
+        const void* p;
+        size_t bytes;
+    };
+    explicit Staging(bool device) : device_(device) {}
+    // false: out of device memory.  `kept`: the scene's buffer (synchronise its stream
+    // first); `scratch_bytes`: room for a scratch() slot, in either form
+    template <typename T>
+    bool reserve(std::initializer_list<Frame> frames, DeviceBuffer<T>& kept, size_t scratch_bytes = 0)
+    {
+        size_t total = slot(scratch_bytes);
+        for (const Frame& f : frames)
+            if (!device_ && f.p) total += slot(f.bytes);
+        if (!kept.reserve(total)) return false;
+        base_ = reinterpret_cast<char*>(kept.get());
+        cap_ = kept.bytes();
+        return true;
+    }
+    bool reserve(std::initializer_list<Frame> frames, size_t scratch_bytes = 0)
+    {
+        return reserve(frames, own_, scratch_bytes);
+    }
+    // a slot nobody copies (a tile the kernels write and the caller did not ask for), in either form
+    template <typename T>
+    T* scratch(size_t bytes)
+    {
+        if (used_ + slot(bytes) > cap_) throw std::length_error("Staging: more slots than reserved");
+        char* p = base_ + used_;
+        used_ += slot(bytes);
+        return reinterpret_cast<T*>(p);
+    }
+    // an input frame: copied into its slot (null stays null)
+    template <typename T>
+    const T* in(const void* p, size_t bytes)
+    {
+        if (device_ || !p || !bytes) return static_cast<const T*>(p);
+        T* d = scratch<T>(bytes);
+        if (ok_) ok_ = hipMemcpy(d, p, bytes, hipMemcpyHostToDevice) == hipSuccess;
+        return d;
+    }
+    bool uploaded() const { return ok_; }
+    // an output frame: a slot that fetch() copies to `p` (null stays null) ...
+    template <typename T>
+    T* out(void* p, size_t bytes)
+    {
+        return device_ || !p ? static_cast<T*>(p) : out_at<T>(p, scratch<T>(bytes), bytes);
+    }
+    // ... or the slot of a staged input, for a kernel that filters in place
+    template <typename T>
+    T* out_at(void* p, const T* staged, size_t bytes)
+    {
+        if (device_ || !p) return static_cast<T*>(p);
+        back_.push_back({p, staged, bytes});
+        return const_cast<T*>(staged);
+    }
+    bool fetch() const
+    {
+        for (const Back& b : back_)
+            if (b.bytes && hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        return true;
+    }
+
+private:
+    struct Back {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    };
+    static size_t slot(size_t bytes) { return (bytes + 15) & ~(size_t)15; }  // slots start on 16 bytes
+    const bool device_;
+    DeviceBuffer<> own_;
+    char* base_ = nullptr;
+    size_t cap_ = 0, used_ = 0;
+    bool ok_ = true;
+    std::vector<Back> back_;
+};
+
+// Before a frame call's device work: a stale error of an earlier failed call cleared
+// (launch checks read it), the scene's device made current
+int enter(const Scene& s)
+{
+    (void)hipGetLastError();
+    TMPT_HIP(hipSetDevice(s.device));
+    return 0;
+}
+
+// After a frame call's run: the checked build's report (the render calls make one, the
+// whole-frame filters none), then the staged outputs
+int finish(int rc, Scene& s, const char* name, const Staging& st, bool report)
+{
+    if (!rc && report) rc = check_report(s, name);
+    if (!rc && !st.fetch()) rc = failed(name, "readback failed");
+    return rc;
 }
 }  // namespace
 
@@ -742,43 +990,8 @@ int tmpt_scene_get_option(const tmpt_scene* h, const char* key, double* value)
 {
     TMPT_GUARD_BEGIN
     if (!h || !value) return bad("tmpt_scene_get_option: null argument");
-    if (key && strcmp(key, "pop_key_bits") == 0) {  // read-only: the scene's layout under pop_key_cap
-        *value = (double)pop_key_bits(h->s.bvh.link_bits, h->s.opt.pop_key_cap);
-        return 0;
-    }
-    if (key && strcmp(key, "cam_rays_used") == 0) {  // read-only: the last render ran the camera pre-pass
-        *value = (double)h->s.cam_rays_used;
-        return 0;
-    }
-    if (key && strcmp(key, "shadow_split_used") == 0) {  // read-only: passes of the last render the shadow split ran
-        *value = (double)h->s.split_used;
-        return 0;
-    }
-    if (key && strcmp(key, "path_waves_used") == 0) {  // read-only: waves per SIMD of the last render's path kernel
-        *value = (double)h->s.path_waves_used;
-        return 0;
-    }
-    if (key && strcmp(key, "shadow_split_resolve_ms") == 0) {  // read-only: k_split_resolve's time in that render
-        *value = h->s.split_resolve_ms;
-        return 0;
-    }
-    if (key && strcmp(key, "update_kind") == 0) {  // read-only: 0 none since creation, 1 refit, 2 rebuild
-        *value = (double)h->s.update_kind;
-        return 0;
-    }
-    if (key && strcmp(key, "update_ms") == 0) {  // read-only: device time of the last tmpt_scene_update
-        *value = h->s.update_ms;
-        return 0;
-    }
-    if (key && strcmp(key, "live_device_objects") == 0) {  // read-only: the process's live tmpt_device.h owners
-        *value = (double)g_live_device_objects.load();
-        return 0;
-    }
-    // read-only, of the last tmpt_scene_hit_device: device time, the keys + sort share, chunks, whether it sorted
-    if (key && strcmp(key, "query_ms") == 0) return (*value = h->s.query_ms, 0);
-    if (key && strcmp(key, "query_sort_ms") == 0) return (*value = h->s.query_sort_ms, 0);
-    if (key && strcmp(key, "query_chunks") == 0) return (*value = (double)h->s.query_chunks, 0);
-    if (key && strcmp(key, "query_sorted") == 0) return (*value = (double)h->s.query_sorted, 0);
+    for (const ReadOnlyKey& k : kReadOnly)
+        if (key && strcmp(key, k.name) == 0) return (*value = k.get(h->s), 0);
     if (key && strcmp(key, "bvh_cost") == 0) {  // read-only: the tree's surface-area cost, cached until an update
         Scene& s = const_cast<tmpt_scene*>(h)->s;
         if (!s.cost_known) {
@@ -941,40 +1154,18 @@ int tmpt_render(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d
                 uint8_t* rgba_out, uint64_t* ray_count)
 {
     TMPT_GUARD_BEGIN
-    if (!h || !cam || !d || !rgba_out) return bad("tmpt_render: null argument");
-    // main.cpp:258-280 argument ranges
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_render: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_render: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render: invalid samplesPerPixel");
-    if (d->seed_mode != TMPT_SEED_ROW && d->seed_mode != TMPT_SEED_PIXEL && d->seed_mode != TMPT_SEED_SAMPLE)
-        return bad("tmpt_render: invalid seed_mode");
-    if (d->engine != TMPT_ENGINE_WAVEFRONT && d->engine != TMPT_ENGINE_MEGAKERNEL &&
-        d->engine != TMPT_ENGINE_PERSISTENT)
-        return bad("tmpt_render: invalid engine");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_render: invalid shard");
-    if (d->spp_begin < 0 || d->spp_begin >= d->spp || d->spp_count < 0 ||
-        d->spp_count > d->spp - d->spp_begin)
-        return bad("tmpt_render: invalid spp_begin / spp_count");
-    const bool progressive = d->spp_begin > 0 || (d->spp_count > 0 && d->spp_count < d->spp);
-    if (progressive && (d->engine != TMPT_ENGINE_PERSISTENT || d->seed_mode == TMPT_SEED_ROW))
-        return bad("tmpt_render: progressive spp needs the persistent engine and pixel or sample seeding");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    const char* const fn = "tmpt_render";
+    if (!h || !cam || !d || !rgba_out) return no(fn, "null argument");
+    if (int rc = check_render_desc(fn, d, {true, kSeedAny, "invalid seed_mode", kEngineAny, "invalid engine",
+                                           kSppProgressive, nullptr, false}))
+        return rc;
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const int32_t rows = tmpt_tile_rows(d);
-    const size_t bytes = (size_t)rows * (size_t)d->width * 4;
-    const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    DeviceBuffer<uint32_t> own;
-    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render: out of device memory");
-    uint32_t* d_out = dev_out ? (uint32_t*)rgba_out : own.get();
-    int rc = render(s, cam, d, d_out, ray_count);
-    if (!rc) rc = check_report(s, "tmpt_render");
-    if (!rc && !dev_out && bytes) {
-        if (hipMemcpy(rgba_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = (set_error("tmpt_render: readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * 4;
+    Staging st((d->flags & TMPT_FLAG_OUT_DEVICE) != 0);
+    if (!st.reserve({{rgba_out, bytes}})) return no(fn, "out of device memory");
+    const int rc = render(s, cam, d, st.out<uint32_t>(rgba_out, bytes), ray_count);
+    return finish(rc, s, fn, st, true);
     TMPT_GUARD_END
 }
 
@@ -982,52 +1173,34 @@ int tmpt_render_aov(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_des
                     uint64_t* ray_count)
 {
     TMPT_GUARD_BEGIN
-    if (!h || !cam || !d || !out) return bad("tmpt_render_aov: null argument");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_aov: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_aov: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_aov: invalid samplesPerPixel");
-    if (d->seed_mode != TMPT_SEED_SAMPLE)
-        return bad("tmpt_render_aov: seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a camera ray is a "
-                   "function of pixel and sample)");
-    if (d->spp_begin != 0 || d->spp_count != 0)
-        return bad("tmpt_render_aov: spp_begin / spp_count must be 0 (the pass is not progressive)");
-    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_aov: TMPT_FLAG_COUNT_VISITS is not supported");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_render_aov: invalid shard");
+    const char* const fn = "tmpt_render_aov";
+    if (!h || !cam || !d || !out) return no(fn, "null argument");
+    if (int rc = check_render_desc(fn, d, {true, kSeedSample,
+                                           "seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a camera ray is a "
+                                           "function of pixel and sample)",
+                                           0, nullptr, kSppZero,
+                                           "spp_begin / spp_count must be 0 (the pass is not progressive)", true}))
+        return rc;
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev_out && (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
-        return bad("tmpt_render_aov: a device output must be 16-byte aligned");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev_out && !aligned({out})) return no(fn, "a device output must be 16-byte aligned");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
+    if (int rc = enter(s)) return rc;
     const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * sizeof(tmpt_aov_pixel);
-    DeviceBuffer<tmpt_aov_pixel> own;
-    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render_aov: out of device memory");
-    tmpt_aov_pixel* d_out = dev_out ? out : own.get();
-    int rc = render_aov(s, cam, d, d_out, ray_count);
-    if (!rc) rc = check_report(s, "tmpt_render_aov");
-    if (!rc && !dev_out && bytes) {
-        if (hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = (set_error("tmpt_render_aov: readback failed"), -1);
-    }
-    return rc;
+    Staging st(dev_out);
+    if (!st.reserve({{out, bytes}})) return no(fn, "out of device memory");
+    const int rc = render_aov(s, cam, d, st.out<tmpt_aov_pixel>(out, bytes), ray_count);
+    return finish(rc, s, fn, st, true);
     TMPT_GUARD_END
 }
 
 int tmpt_camera_rays(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d, uint32_t* out)
 {
     TMPT_GUARD_BEGIN
-    if (!h || !cam || !d || !out) return bad("tmpt_camera_rays: null argument");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_camera_rays: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_camera_rays: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_camera_rays: invalid samplesPerPixel");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_camera_rays: invalid shard");
-    if (d->spp_begin < 0 || d->spp_begin >= d->spp || d->spp_count < 0 || d->spp_count > d->spp - d->spp_begin)
-        return bad("tmpt_camera_rays: invalid spp_begin / spp_count");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    const char* const fn = "tmpt_camera_rays";
+    if (!h || !cam || !d || !out) return no(fn, "null argument");
+    if (int rc = check_render_desc(fn, d, {true, 0, nullptr, 0, nullptr, kSppRange, nullptr, false})) return rc;
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
+    if (int rc = enter(s)) return rc;
     return camera_rays(s, cam, d, out);
     TMPT_GUARD_END
 }
@@ -1036,46 +1209,27 @@ int tmpt_render_radiance(tmpt_scene* h, const tmpt_camera* cam, const tmpt_rende
                          uint8_t* rgba8_out, uint64_t* ray_count)
 {
     TMPT_GUARD_BEGIN
-    if (!h || !cam || !d || !rgba32f_out) return bad("tmpt_render_radiance: null argument");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_radiance: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_radiance: invalid height");
-    if (d->spp < 1 || d->spp > 1024) return bad("tmpt_render_radiance: invalid samplesPerPixel");
-    if (d->seed_mode != TMPT_SEED_PIXEL && d->seed_mode != TMPT_SEED_SAMPLE)
-        return bad("tmpt_render_radiance: seed_mode must be TMPT_SEED_PIXEL or TMPT_SEED_SAMPLE (row seeding keeps no "
-                   "float sum per pixel)");
-    if (d->engine != TMPT_ENGINE_PERSISTENT)
-        return bad("tmpt_render_radiance: engine must be TMPT_ENGINE_PERSISTENT");
-    if (d->spp_begin != 0 || d->spp_count != 0)
-        return bad("tmpt_render_radiance: spp_begin / spp_count must be 0 (whole renders only)");
-    if (d->flags & TMPT_FLAG_COUNT_VISITS)
-        return bad("tmpt_render_radiance: TMPT_FLAG_COUNT_VISITS is not supported");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_render_radiance: invalid shard");
+    const char* const fn = "tmpt_render_radiance";
+    if (!h || !cam || !d || !rgba32f_out) return no(fn, "null argument");
+    if (int rc = check_render_desc(fn, d, {true, 1u << TMPT_SEED_PIXEL | kSeedSample,
+                                           "seed_mode must be TMPT_SEED_PIXEL or TMPT_SEED_SAMPLE (row seeding keeps no "
+                                           "float sum per pixel)",
+                                           kEnginePersistent, kMustPersist, kSppZero,
+                                           "spp_begin / spp_count must be 0 (whole renders only)", true}))
+        return rc;
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev_out && (reinterpret_cast<uintptr_t>(rgba32f_out) & 15u) != 0)
-        return bad("tmpt_render_radiance: a device rgba32f_out must be 16-byte aligned");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev_out && !aligned({rgba32f_out})) return no(fn, "a device rgba32f_out must be 16-byte aligned");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width;
-    // the kernels write both tiles: device buffers of the library's own stand in
-    // for host outputs and for an rgba8_out the caller does not want
-    float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
-    uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
-    DeviceBuffer<float4> own_f;
-    DeviceBuffer<uint32_t> own_8;
-    if (px && ((!d_f && !own_f.alloc(px * sizeof(float4))) || (!d_8 && !own_8.alloc(px * 4))))
-        return bad("tmpt_render_radiance: out of device memory");
-    if (own_f) d_f = own_f;
-    if (own_8) d_8 = own_8;
-    int rc = render(s, cam, d, d_8, ray_count, d_f);
-    if (!rc) rc = check_report(s, "tmpt_render_radiance");
-    if (!rc && !dev_out && px) {
-        if (hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess ||
-            (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error("tmpt_render_radiance: readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width, fb = px * sizeof(float4), wb = px * 4;
+    // the kernels write both tiles: a slot of the library's own stands in for an
+    // rgba8_out the caller does not want, in the device form too
+    Staging st(dev_out);
+    if (!st.reserve({{rgba32f_out, fb}, {rgba8_out, wb}}, rgba8_out ? 0 : wb)) return no(fn, "out of device memory");
+    float4* d_f = st.out<float4>(rgba32f_out, fb);
+    uint32_t* d_8 = rgba8_out ? st.out<uint32_t>(rgba8_out, wb) : st.scratch<uint32_t>(wb);
+    const int rc = render(s, cam, d, d_8, ray_count, d_f);
+    return finish(rc, s, fn, st, true);
     TMPT_GUARD_END
 }
 
@@ -1090,19 +1244,13 @@ static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const t
                          uint8_t* rgba8_out, int32_t* spp_out, tmpt_adaptive_info* info, uint64_t* ray_count,
                          bool guided = false, const float* prior = nullptr)
 {
-    const auto no = [name](const char* msg) { return bad((std::string(name) + ": " + msg).c_str()); };
-    if (!h || !cam || !d) return no("null argument");
-    if (d->width < 1 || d->width > 10000) return no("invalid width");
-    if (d->height < 1 || d->height > 10000) return no("invalid height");
-    if (d->spp < 1 || d->spp > 1024) return no("invalid samplesPerPixel");
-    if (d->seed_mode != TMPT_SEED_SAMPLE)
-        return no("seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a sample is a "
-                  "function of pixel and sample)");
-    if (d->engine != TMPT_ENGINE_PERSISTENT) return no("engine must be TMPT_ENGINE_PERSISTENT");
-    if (d->spp_begin != 0 || d->spp_count != 0)
-        return no("spp_begin / spp_count must be 0 (the call makes its own passes)");
-    if (d->flags & TMPT_FLAG_COUNT_VISITS) return no("TMPT_FLAG_COUNT_VISITS is not supported");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards)) return no("invalid shard");
+    if (!h || !cam || !d) return no(name, "null argument");
+    if (int rc = check_render_desc(name, d, {true, kSeedSample,
+                                             "seed_mode must be TMPT_SEED_SAMPLE (the only seeding where a sample is a "
+                                             "function of pixel and sample)",
+                                             kEnginePersistent, kMustPersist, kSppZero,
+                                             "spp_begin / spp_count must be 0 (the call makes its own passes)", true}))
+        return rc;
     tmpt_adaptive_desc r;  // the defaults, in one place ("Adaptive sampling")
     memset(&r, 0, sizeof(r));
     if (ad) r = *ad;
@@ -1111,67 +1259,43 @@ static int adaptive_call(const char* name, bool with_mom, tmpt_scene* h, const t
     if (r.spp_min == 0) r.spp_min = std::min(24, d->spp);
     if (r.spp_step == 0) r.spp_step = 8;
     if (!(r.threshold >= -3.0e38f) || !(r.threshold <= 3.0e38f))
-        return no("threshold must be finite (negative = default)");
+        return no(name, "threshold must be finite (negative = default)");
     if (r.threshold < 0.0f) r.threshold = 0.015f;
-    if (r.spp_min < 2 || r.spp_min > d->spp) return no("spp_min outside 2 .. spp (0 = default)");
-    if (r.spp_step < 1) return no("spp_step must not be negative (0 = default)");
-    if (r.radius < 0 || r.radius > 8) return no("radius outside 0 .. 8 (0 = no neighbourhood rule)");
+    if (r.spp_min < 2 || r.spp_min > d->spp) return no(name, "spp_min outside 2 .. spp (0 = default)");
+    if (r.spp_step < 1) return no(name, "spp_step must not be negative (0 = default)");
+    if (r.radius < 0 || r.radius > 8) return no(name, "radius outside 0 .. 8 (0 = no neighbourhood rule)");
     if (1 + (d->spp - r.spp_min + r.spp_step - 1) / r.spp_step > 64)
-        return no("spp_min / spp_step give a schedule of more than 64 passes");
+        return no(name, "spp_min / spp_step give a schedule of more than 64 passes");
     if (guided) {
         if (!rgba32f_out && !moments_out && !rgba8_out && !spp_out)
-            return no("no output (rgba32f_out, moments_out, rgba8_out and spp_out are all null)");
+            return no(name, "no output (rgba32f_out, moments_out, rgba8_out and spp_out are all null)");
     } else if (with_mom) {
-        if (!moments_out) return no("moments_out is required");
+        if (!moments_out) return no(name, "moments_out is required");
     } else if (!rgba32f_out && !rgba8_out && !spp_out) {
-        return no("no output (rgba32f_out, rgba8_out and spp_out are all null)");
+        return no(name, "no output (rgba32f_out, rgba8_out and spp_out are all null)");
     }
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev_out && (((reinterpret_cast<uintptr_t>(rgba32f_out) | reinterpret_cast<uintptr_t>(moments_out)) & 15u) != 0 ||
-                    ((reinterpret_cast<uintptr_t>(rgba8_out) | reinterpret_cast<uintptr_t>(spp_out)) & 3u) != 0))
-        return no(with_mom ? "device outputs must be aligned (rgba32f_out and moments_out 16 bytes, rgba8_out and "
-                             "spp_out 4)"
-                           : "device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
-                             "spp_out 4)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(prior) & 15u) != 0) return no("a device prior must be 16-byte aligned");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev_out && !aligned({rgba32f_out, moments_out}, {rgba8_out, spp_out}))
+        return no(name, with_mom ? "device outputs must be aligned (rgba32f_out and moments_out 16 bytes, rgba8_out and "
+                                   "spp_out 4)"
+                                 : "device outputs must be aligned (rgba32f_out 16 bytes, rgba8_out and "
+                                   "spp_out 4)");
+    if (dev_out && !aligned({prior})) return no(name, "a device prior must be 16-byte aligned");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width;
-    // host outputs are staged in device tiles of the library's own
-    float4* d_f = dev_out ? reinterpret_cast<float4*>(rgba32f_out) : nullptr;
-    float4* d_m = dev_out ? reinterpret_cast<float4*>(moments_out) : nullptr;
-    uint32_t* d_8 = dev_out ? reinterpret_cast<uint32_t*>(rgba8_out) : nullptr;
-    int32_t* d_n = dev_out ? spp_out : nullptr;
-    DeviceBuffer<float4> own_f, own_m;
-    DeviceBuffer<uint32_t> own_8;
-    DeviceBuffer<int32_t> own_n;
-    if (!dev_out && px &&
-        ((rgba32f_out && !own_f.alloc(px * sizeof(float4))) || (moments_out && !own_m.alloc(px * sizeof(float4))) ||
-         (rgba8_out && !own_8.alloc(px * 4)) || (spp_out && !own_n.alloc(px * 4))))
-        return no("out of device memory");
-    if (own_f) d_f = own_f;
-    if (own_m) d_m = own_m;
-    if (own_8) d_8 = own_8;
-    if (own_n) d_n = own_n;
-    const float4* d_p = reinterpret_cast<const float4*>(prior);
-    DeviceBuffer<float4> own_p;
-    if (prior && !dev_out && px) {  // a host prior: staged beside the outputs' tiles
-        if (!own_p.alloc(px * sizeof(float4))) return no("out of device memory");
-        if (hipMemcpy(own_p, prior, px * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess)
-            return (set_error(std::string(name) + ": upload failed"), -1);
-        d_p = own_p;
-    }
-    int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count, d_m, name, d_p);
-    if (!rc) rc = check_report(s, name);
-    if (!rc && !dev_out && px) {
-        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_f, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (moments_out && hipMemcpy(moments_out, d_m, px * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (rgba8_out && hipMemcpy(rgba8_out, d_8, px * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (spp_out && hipMemcpy(spp_out, d_n, px * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error(std::string(name) + ": readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    const size_t px = (size_t)tmpt_tile_rows(d) * (size_t)d->width, fb = px * sizeof(float4), wb = px * 4;
+    // host form: the outputs the caller asked for, and its prior beside them
+    Staging st(dev_out);
+    if (!st.reserve({{rgba32f_out, fb}, {moments_out, fb}, {rgba8_out, wb}, {spp_out, wb}, {prior, fb}}))
+        return no(name, "out of device memory");
+    const float4* d_p = st.in<float4>(prior, fb);
+    if (!st.uploaded()) return failed(name, "upload failed");
+    float4* d_f = st.out<float4>(rgba32f_out, fb);
+    float4* d_m = st.out<float4>(moments_out, fb);
+    uint32_t* d_8 = st.out<uint32_t>(rgba8_out, wb);
+    int32_t* d_n = st.out<int32_t>(spp_out, wb);
+    const int rc = render_adaptive(s, cam, d, &r, d_f, d_8, d_n, info, ray_count, d_m, name, d_p);
+    return finish(rc, s, name, st, true);
 }
 
 int tmpt_render_adaptive(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_desc* d,
@@ -1204,79 +1328,50 @@ int tmpt_render_guided(tmpt_scene* h, const tmpt_camera* cam, const tmpt_render_
     TMPT_GUARD_END
 }
 
-// tmpt_denoise_moments' default shrink: the grid point tools/noise_aware_sweep.py's rule
-// picks ("Noise-aware filter")
-constexpr float kShrinkDefault = 2.0f;
-
 // tmpt_denoise and tmpt_denoise_moments: one body.  `name` is the call's name in
 // errors; with_mom: the moments frame is required and shrink is read.
 static int denoise_call(const char* name, bool with_mom, tmpt_scene* h, const tmpt_denoise_desc* d, float shrink,
                         const float* rgba32f_in, const tmpt_aov_pixel* aov, const float* moments, float* rgba32f_out,
                         uint8_t* rgba8_out)
 {
-    const auto no = [name](const char* msg) { return bad((std::string(name) + ": " + msg).c_str()); };
     // the descriptor first, before anything that needs a scene or a device
-    if (!d) return no("null descriptor");
-    if (d->width < 1 || d->width > 10000) return no("invalid width");
-    if (d->height < 1 || d->height > 10000) return no("invalid height");
-    if (d->spp < 1 || d->spp > 1024) return no("invalid samplesPerPixel");
-    if (d->levels < 0 || d->levels > 6) return no("levels out of range (1..6, 0 = 5)");
-    if (d->normal_exp < -1 || d->normal_exp > 8) return no("normal_exp out of range (0..8, -1 = 5)");
+    if (!d) return no(name, "null descriptor");
+    if (int rc = check_frame(name, d->width, d->height, &d->spp)) return rc;
+    if (d->levels < 0 || d->levels > 6) return no(name, "levels out of range (1..6, 0 = 5)");
+    if (d->normal_exp < -1 || d->normal_exp > 8) return no(name, "normal_exp out of range (0..8, -1 = 5)");
     if (!(d->sigma_depth >= 0.0f) || !(d->sigma_depth <= 3.0e38f))
-        return no("sigma_depth must be finite and not negative (0 = auto)");
+        return no(name, "sigma_depth must be finite and not negative (0 = auto)");
     if (!(d->sigma_direct >= 0.0f) || !(d->sigma_direct <= 3.0e38f))
-        return no("sigma_direct must be finite and not negative (0 = default)");
+        return no(name, "sigma_direct must be finite and not negative (0 = default)");
     if (with_mom && (!(shrink >= 0.0f) || !(shrink <= 3.4028235e38f)))
-        return no("shrink must be finite and not negative (0 = default)");
-    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
-    if (!rgba32f_out && !rgba8_out) return no("no output (rgba32f_out and rgba8_out are both null)");
-    if (!h || !rgba32f_in || !aov || (with_mom && !moments)) return no("null argument");
+        return no(name, "shrink must be finite and not negative (0 = default)");
+    if (int rc = check_frame_flags(name, d->flags)) return rc;
+    if (!rgba32f_out && !rgba8_out) return no(name, "no output (rgba32f_out and rgba8_out are both null)");
+    if (!h || !rgba32f_in || !aov || (with_mom && !moments)) return no(name, "null argument");
     const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev && (((reinterpret_cast<uintptr_t>(rgba32f_in) | reinterpret_cast<uintptr_t>(aov) |
-                  reinterpret_cast<uintptr_t>(moments) | reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
-                (reinterpret_cast<uintptr_t>(rgba8_out) & 3u) != 0))
-        return no("device pointers must be 16-byte aligned (rgba8_out: 4)");
+    if (dev && !aligned({rgba32f_in, aov, moments, rgba32f_out}, {rgba8_out}))
+        return no(name, "device pointers must be 16-byte aligned (rgba8_out: 4)");
     if (shrink == 0.0f) shrink = kShrinkDefault;
     tmpt_denoise_desc r = *d;  // the defaults, in one place
     if (r.levels == 0) r.levels = 5;
     if (r.normal_exp < 0) r.normal_exp = 5;
     if (r.sigma_depth == 0.0f) r.sigma_depth = 1.0f / (float)r.height;
     if (r.sigma_direct == 0.0f) r.sigma_direct = 0.05f;
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const size_t n = (size_t)r.width * (size_t)r.height;
-    const float4* d_in = reinterpret_cast<const float4*>(rgba32f_in);
-    const tmpt_aov_pixel* d_aov = aov;
-    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
-    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
-    DeviceBuffer<float4> own_in;
-    DeviceBuffer<tmpt_aov_pixel> own_aov;
-    DeviceBuffer<uint32_t> own_8;
-    const float4* d_mom = reinterpret_cast<const float4*>(moments);
-    DeviceBuffer<float4> own_mom;
-    if (!dev) {  // host pointers: staged on the device; the float result is filtered in place there
-        if (!own_in.alloc(n * sizeof(float4)) || !own_aov.alloc(n * sizeof(tmpt_aov_pixel)) ||
-            (rgba8_out && !own_8.alloc(n * 4)) || (with_mom && !own_mom.alloc(n * sizeof(float4))))
-            return no("out of device memory");
-        if (hipMemcpy(own_in, rgba32f_in, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_aov, aov, n * sizeof(tmpt_aov_pixel), hipMemcpyHostToDevice) != hipSuccess ||
-            (with_mom && hipMemcpy(own_mom, moments, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess))
-            return (set_error(std::string(name) + ": upload failed"), -1);
-        d_in = own_in;
-        d_aov = own_aov;
-        d_mom = own_mom;
-        d_o32 = rgba32f_out ? own_in.get() : nullptr;
-        d_o8 = own_8;
-    }
-    int rc = with_mom ? denoise_moments(s, &r, shrink, d_in, d_aov, d_mom, d_o32, d_o8)
-                      : denoise(s, &r, d_in, d_aov, d_o32, d_o8);
-    if (!rc && !dev) {
-        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error(std::string(name) + ": readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4), ab = n * sizeof(tmpt_aov_pixel);
+    Staging st(dev);
+    if (!st.reserve({{rgba32f_in, fb}, {aov, ab}, {moments, fb}, {rgba8_out, n * 4}}))
+        return no(name, "out of device memory");
+    const float4* d_in = st.in<float4>(rgba32f_in, fb);
+    const tmpt_aov_pixel* d_aov = st.in<tmpt_aov_pixel>(aov, ab);
+    const float4* d_mom = st.in<float4>(moments, fb);
+    if (!st.uploaded()) return failed(name, "upload failed");
+    float4* d_o32 = st.out_at<float4>(rgba32f_out, d_in, fb);  // host form: filtered in place in the staged input
+    uint32_t* d_o8 = st.out<uint32_t>(rgba8_out, n * 4);
+    const int rc = with_mom ? denoise_moments(s, &r, shrink, d_in, d_aov, d_mom, d_o32, d_o8)
+                            : denoise(s, &r, d_in, d_aov, d_o32, d_o8);
+    return finish(rc, s, name, st, false);
 }
 
 int tmpt_denoise(tmpt_scene* h, const tmpt_denoise_desc* d, const float* rgba32f_in, const tmpt_aov_pixel* aov,
@@ -1299,43 +1394,30 @@ int tmpt_render_motion(tmpt_scene* h, const tmpt_camera* cam, const tmpt_camera*
                        int32_t prev_n, const tmpt_render_desc* d, tmpt_motion_pixel* out, uint64_t* ray_count)
 {
     TMPT_GUARD_BEGIN
+    const char* const fn = "tmpt_render_motion";
     // everything that needs no scene first, so that it is refused without a device
-    if (!cam || !prev_cam || !d || !out) return bad("tmpt_render_motion: null argument");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_render_motion: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_render_motion: invalid height");
-    if (d->num_shards > 1 && (d->shard < 0 || d->shard >= d->num_shards))
-        return bad("tmpt_render_motion: invalid shard");
-    if (d->flags & TMPT_FLAG_COUNT_VISITS) return bad("tmpt_render_motion: TMPT_FLAG_COUNT_VISITS is not supported");
+    if (!cam || !prev_cam || !d || !out) return no(fn, "null argument");
+    if (int rc = check_render_desc(fn, d, {false, 0, nullptr, 0, nullptr, kSppUnread, nullptr, true})) return rc;
     const bool dev_out = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev_out && (reinterpret_cast<uintptr_t>(out) & 15u) != 0)
-        return bad("tmpt_render_motion: a device output must be 16-byte aligned");
-    if (!h) return bad("tmpt_render_motion: null scene");
+    if (dev_out && !aligned({out})) return no(fn, "a device output must be 16-byte aligned");
+    if (!h) return no(fn, "null scene");
     Scene& s = h->s;
     if (prev_tris && prev_n != s.bvh.n)
-        return bad("tmpt_render_motion: prev_n differs from the scene's triangle count (the previous pose has the "
-                   "scene's triangles, slot for slot)");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
-    TMPT_HIP(hipSetDevice(s.device));
-    const float* d_prev = prev_tris;
+        return no(fn, "prev_n differs from the scene's triangle count (the previous pose has the "
+                      "scene's triangles, slot for slot)");
+    if (int rc = enter(s)) return rc;
+    Staging pose(dev_out), st(dev_out);
+    const size_t pb = prev_tris ? sizeof(float) * 9 * (size_t)prev_n : 0;
     if (prev_tris && !dev_out) {  // a host pose: into the scene's kept buffer
-        const size_t pb = sizeof(float) * 9 * (size_t)prev_n;
         TMPT_HIP(hipStreamSynchronize(s.stream));
-        if (pb && !s.motion_prev.reserve(pb)) return bad("tmpt_render_motion: out of device memory");
-        if (pb && hipMemcpy(s.motion_prev, prev_tris, pb, hipMemcpyHostToDevice) != hipSuccess)
-            return (set_error("tmpt_render_motion: upload failed"), -1);
-        d_prev = s.motion_prev;
+        if (!pose.reserve({{prev_tris, pb}}, s.motion_prev)) return no(fn, "out of device memory");
     }
+    const float* d_prev = pose.in<float>(prev_tris, pb);
+    if (!pose.uploaded()) return failed(fn, "upload failed");
     const size_t bytes = (size_t)tmpt_tile_rows(d) * (size_t)d->width * sizeof(tmpt_motion_pixel);
-    DeviceBuffer<tmpt_motion_pixel> own;
-    if (!dev_out && bytes && !own.alloc(bytes)) return bad("tmpt_render_motion: out of device memory");
-    tmpt_motion_pixel* d_out = dev_out ? out : own.get();
-    int rc = render_motion(s, cam, prev_cam, d_prev, d, d_out, ray_count);
-    if (!rc) rc = check_report(s, "tmpt_render_motion");
-    if (!rc && !dev_out && bytes) {
-        if (hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = (set_error("tmpt_render_motion: readback failed"), -1);
-    }
-    return rc;
+    if (!st.reserve({{out, bytes}})) return no(fn, "out of device memory");
+    const int rc = render_motion(s, cam, prev_cam, d_prev, d, st.out<tmpt_motion_pixel>(out, bytes), ray_count);
+    return finish(rc, s, fn, st, true);
     TMPT_GUARD_END
 }
 
@@ -1344,68 +1426,35 @@ int tmpt_temporal(tmpt_scene* h, const tmpt_temporal_desc* d, const float* rgba3
                   uint8_t* rgba8_out)
 {
     TMPT_GUARD_BEGIN
+    const char* const fn = "tmpt_temporal";
     // the descriptor first, before anything that needs a scene or a device
-    if (!d) return bad("tmpt_temporal: null descriptor");
-    if (d->width < 1 || d->width > 10000) return bad("tmpt_temporal: invalid width");
-    if (d->height < 1 || d->height > 10000) return bad("tmpt_temporal: invalid height");
-    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return bad("tmpt_temporal: null argument");
-    if (!rgba32f_out && !rgba8_out) return bad("tmpt_temporal: no output (rgba32f_out and rgba8_out are both null)");
-    tmpt_temporal_desc r = *d;  // the defaults, in one place ("Temporal accumulation")
-    if (r.n_max == 0.0f) r.n_max = 3.0f;
-    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
-    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f))
-        return bad("tmpt_temporal: n_max must be finite and at least 1 (0 = default)");
-    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
-        return bad("tmpt_temporal: sigma_depth must be finite and not negative (0 = default)");
-    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return bad("tmpt_temporal: unknown flag");
+    if (!d) return no(fn, "null descriptor");
+    if (int rc = check_frame(fn, d->width, d->height, nullptr)) return rc;
+    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return no(fn, "null argument");
+    if (!rgba32f_out && !rgba8_out) return no(fn, "no output (rgba32f_out and rgba8_out are both null)");
+    tmpt_temporal_desc r = *d;
+    if (int rc = temporal_defaults(fn, kTemporalNMax, &r.n_max, &r.sigma_depth)) return rc;
+    if (int rc = check_frame_flags(fn, d->flags)) return rc;
     const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    if (dev && (((reinterpret_cast<uintptr_t>(rgba32f_cur) | reinterpret_cast<uintptr_t>(motion) |
-                  reinterpret_cast<uintptr_t>(prev_motion) | reinterpret_cast<uintptr_t>(rgba32f_history) |
-                  reinterpret_cast<uintptr_t>(rgba32f_out)) & 15u) != 0 ||
-                (reinterpret_cast<uintptr_t>(rgba8_out) & 3u) != 0))
-        return bad("tmpt_temporal: device pointers must be 16-byte aligned (rgba8_out: 4)");
-    const size_t n = (size_t)r.width * (size_t)r.height;
-    if (rgba32f_out) {
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(rgba32f_out), h0 = reinterpret_cast<uintptr_t>(rgba32f_history);
-        if (o0 < h0 + n * sizeof(float4) && h0 < o0 + n * sizeof(float4))
-            return bad("tmpt_temporal: rgba32f_out overlaps rgba32f_history (its neighbours are read)");
-    }
-    if (!h) return bad("tmpt_temporal: null scene");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev && !aligned({rgba32f_cur, motion, prev_motion, rgba32f_history, rgba32f_out}, {rgba8_out}))
+        return no(fn, "device pointers must be 16-byte aligned (rgba8_out: 4)");
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4), mb = n * sizeof(tmpt_motion_pixel);
+    if (int rc = check_overlap(fn, fb, {{rgba32f_out, "rgba32f_out"}}, {{rgba32f_history, "rgba32f_history"}})) return rc;
+    if (!h) return no(fn, "null scene");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const float4* d_cur = reinterpret_cast<const float4*>(rgba32f_cur);
-    const float4* d_hist = reinterpret_cast<const float4*>(rgba32f_history);
-    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
-    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
-    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
-    DeviceBuffer<float4> own_cur, own_hist;
-    DeviceBuffer<tmpt_motion_pixel> own_m, own_pm;
-    DeviceBuffer<uint32_t> own_8;
-    if (!dev) {  // host pointers: staged on the device; the float result is blended in place there
-        if (!own_cur.alloc(n * sizeof(float4)) || !own_hist.alloc(n * sizeof(float4)) ||
-            !own_m.alloc(n * sizeof(tmpt_motion_pixel)) || !own_pm.alloc(n * sizeof(tmpt_motion_pixel)) ||
-            (rgba8_out && !own_8.alloc(n * 4)))
-            return bad("tmpt_temporal: out of device memory");
-        if (hipMemcpy(own_cur, rgba32f_cur, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_hist, rgba32f_history, n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_m, motion, n * sizeof(tmpt_motion_pixel), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(own_pm, prev_motion, n * sizeof(tmpt_motion_pixel), hipMemcpyHostToDevice) != hipSuccess)
-            return (set_error("tmpt_temporal: upload failed"), -1);
-        d_cur = own_cur;
-        d_hist = own_hist;
-        d_m = own_m;
-        d_pm = own_pm;
-        d_o32 = rgba32f_out ? own_cur.get() : nullptr;
-        d_o8 = own_8;
-    }
-    int rc = temporal(s, &r, d_cur, d_m, d_pm, d_hist, d_o32, d_o8);
-    if (!rc && !dev) {
-        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, n * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) ||
-            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error("tmpt_temporal: readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    Staging st(dev);
+    if (!st.reserve({{rgba32f_cur, fb}, {rgba32f_history, fb}, {motion, mb}, {prev_motion, mb}, {rgba8_out, n * 4}}))
+        return no(fn, "out of device memory");
+    const float4* d_cur = st.in<float4>(rgba32f_cur, fb);
+    const float4* d_hist = st.in<float4>(rgba32f_history, fb);
+    const tmpt_motion_pixel* d_m = st.in<tmpt_motion_pixel>(motion, mb);
+    const tmpt_motion_pixel* d_pm = st.in<tmpt_motion_pixel>(prev_motion, mb);
+    if (!st.uploaded()) return failed(fn, "upload failed");
+    float4* d_o32 = st.out_at<float4>(rgba32f_out, d_cur, fb);  // host form: blended in place in the staged frame
+    uint32_t* d_o8 = st.out<uint32_t>(rgba8_out, n * 4);
+    const int rc = temporal(s, &r, d_cur, d_m, d_pm, d_hist, d_o32, d_o8);
+    return finish(rc, s, fn, st, false);
     TMPT_GUARD_END
 }
 
@@ -1413,61 +1462,34 @@ int tmpt_sample_plan(tmpt_scene* h, const tmpt_temporal_desc* d, const tmpt_moti
                      const tmpt_motion_pixel* prev_motion, const float* moments_history, float* prior_out)
 {
     TMPT_GUARD_BEGIN
-    const char* const fn = "tmpt_sample_plan: ";
-    auto no = [&](const char* what) { return bad((std::string(fn) + what).c_str()); };
+    const char* const fn = "tmpt_sample_plan";
     // tmpt_temporal's checks in its order, its colour frames left out
-    if (!d) return no("null descriptor");
-    if (d->width < 1 || d->width > 10000) return no("invalid width");
-    if (d->height < 1 || d->height > 10000) return no("invalid height");
-    if (!motion || !prev_motion || !moments_history || !prior_out) return no("null argument");
-    tmpt_temporal_desc r = *d;  // the defaults, in one place: tmpt_temporal's
-    if (r.n_max == 0.0f) r.n_max = 3.0f;
-    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
-    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f)) return no("n_max must be finite and at least 1 (0 = default)");
-    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
-        return no("sigma_depth must be finite and not negative (0 = default)");
-    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
+    if (!d) return no(fn, "null descriptor");
+    if (int rc = check_frame(fn, d->width, d->height, nullptr)) return rc;
+    if (!motion || !prev_motion || !moments_history || !prior_out) return no(fn, "null argument");
+    tmpt_temporal_desc r = *d;
+    if (int rc = temporal_defaults(fn, kTemporalNMax, &r.n_max, &r.sigma_depth)) return rc;
+    if (int rc = check_frame_flags(fn, d->flags)) return rc;
     const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-    if (dev && ((at(motion) | at(prev_motion) | at(moments_history) | at(prior_out)) & 15u) != 0)
-        return no("device pointers must be 16-byte aligned");
-    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4);
-    if (at(prior_out) < at(moments_history) + fb && at(moments_history) < at(prior_out) + fb)
-        return no("prior_out overlaps moments_history (its neighbours are read)");
-    if (!h) return no("null scene");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev && !aligned({motion, prev_motion, moments_history, prior_out}))
+        return no(fn, "device pointers must be 16-byte aligned");
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4), mb = n * sizeof(tmpt_motion_pixel);
+    if (int rc = check_overlap(fn, fb, {{prior_out, "prior_out"}}, {{moments_history, "moments_history"}})) return rc;
+    if (!h) return no(fn, "null scene");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const float4* d_hist = reinterpret_cast<const float4*>(moments_history);
-    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
-    float4* d_out = reinterpret_cast<float4*>(prior_out);
-    if (!dev) {  // host pointers: staged in the scene's kept buffer, as tmpt_temporal_clip stages its own
-        const size_t mb = n * sizeof(tmpt_motion_pixel);
-        TMPT_HIP(hipStreamSynchronize(s.stream));
-        if (!s.clip_stage.reserve(2 * fb + 2 * mb)) return no("out of device memory");
-        char* at_dev = s.clip_stage.as<char>();
-        auto take = [&](size_t bytes) { char* p = at_dev; at_dev += bytes; return p; };
-        auto up = [&](const void* src, size_t bytes) -> char* {
-            char* p = take(bytes);
-            return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? p : nullptr;
-        };
-        d_hist = reinterpret_cast<const float4*>(up(moments_history, fb));
-        d_m = reinterpret_cast<const tmpt_motion_pixel*>(up(motion, mb));
-        d_pm = reinterpret_cast<const tmpt_motion_pixel*>(up(prev_motion, mb));
-        if (!d_hist || !d_m || !d_pm) return (set_error(std::string(fn) + "upload failed"), -1);
-        d_out = reinterpret_cast<float4*>(take(fb));
-    }
-    int rc = sample_plan(s, &r, d_m, d_pm, d_hist, d_out);
-    if (!rc && !dev && hipMemcpy(prior_out, d_out, fb, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = (set_error(std::string(fn) + "readback failed"), -1);
-    return rc;
+    if (int rc = enter(s)) return rc;
+    Staging st(dev);  // host form: in the scene's kept buffer, as tmpt_temporal_clip stages its own
+    if (!dev) TMPT_HIP(hipStreamSynchronize(s.stream));
+    if (!st.reserve({{moments_history, fb}, {motion, mb}, {prev_motion, mb}, {prior_out, fb}}, s.clip_stage))
+        return no(fn, "out of device memory");
+    const float4* d_hist = st.in<float4>(moments_history, fb);
+    const tmpt_motion_pixel* d_m = st.in<tmpt_motion_pixel>(motion, mb);
+    const tmpt_motion_pixel* d_pm = st.in<tmpt_motion_pixel>(prev_motion, mb);
+    if (!st.uploaded()) return failed(fn, "upload failed");
+    const int rc = sample_plan(s, &r, d_m, d_pm, d_hist, st.out<float4>(prior_out, fb));
+    return finish(rc, s, fn, st, false);
     TMPT_GUARD_END
 }
-
-// tmpt_temporal_clip's defaults: the grid point tools/temporal_clip_sweep.py's rule
-// chose (profiles/temporal_clip_sweep.log, DESIGN.md section 4, "History clipping")
-constexpr float kClipNMax = 3.0f, kClipGamma = 0.5f;
-constexpr int32_t kClipRadius = 1;
 
 int tmpt_temporal_clip(tmpt_scene* h, const tmpt_temporal_clip_desc* d, const float* rgba32f_cur,
                        const float* rgba32f_stat, const tmpt_motion_pixel* motion, const tmpt_motion_pixel* prev_motion,
@@ -1475,91 +1497,53 @@ int tmpt_temporal_clip(tmpt_scene* h, const tmpt_temporal_clip_desc* d, const fl
                        float* rgba32f_out, uint8_t* rgba8_out)
 {
     TMPT_GUARD_BEGIN
-    const char* const fn = "tmpt_temporal_clip: ";
-    auto no = [&](const char* what) { return bad((std::string(fn) + what).c_str()); };
+    const char* const fn = "tmpt_temporal_clip";
     // tmpt_temporal's checks in its order, the new ones where the header puts them
-    if (!d) return no("null descriptor");
-    if (d->width < 1 || d->width > 10000) return no("invalid width");
-    if (d->height < 1 || d->height > 10000) return no("invalid height");
-    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return no("null argument");
-    const bool aux = aux_cur || aux_history || aux_out;
-    if (aux && (!aux_cur || !aux_history || !aux_out))
-        return no("null argument (aux_cur, aux_history and aux_out: all three or none)");
-    if (!rgba32f_out && !rgba8_out) return no("no output (rgba32f_out and rgba8_out are both null)");
+    if (!d) return no(fn, "null descriptor");
+    if (int rc = check_frame(fn, d->width, d->height, nullptr)) return rc;
+    if (!rgba32f_cur || !motion || !prev_motion || !rgba32f_history) return no(fn, "null argument");
+    if ((aux_cur || aux_history || aux_out) && (!aux_cur || !aux_history || !aux_out))
+        return no(fn, "null argument (aux_cur, aux_history and aux_out: all three or none)");
+    if (!rgba32f_out && !rgba8_out) return no(fn, "no output (rgba32f_out and rgba8_out are both null)");
     tmpt_temporal_clip_desc r = *d;  // the defaults, in one place
-    if (r.n_max == 0.0f) r.n_max = kClipNMax;
-    if (r.sigma_depth == 0.0f) r.sigma_depth = 0.05f;
     if (r.gamma == 0.0f) r.gamma = kClipGamma;
     if (r.radius == 0) r.radius = kClipRadius;
-    if (!(r.n_max >= 1.0f) || !(r.n_max <= 3.0e38f)) return no("n_max must be finite and at least 1 (0 = default)");
-    if (!(r.sigma_depth >= 0.0f) || !(r.sigma_depth <= 3.0e38f))
-        return no("sigma_depth must be finite and not negative (0 = default)");
-    if (!(r.gamma >= 0.0f) || !(r.gamma <= 3.0e38f)) return no("gamma must be finite and not negative (0 = default)");
-    if (r.radius < 1 || r.radius > 3) return no("radius must be 1, 2 or 3 (0 = default)");
-    if (d->flags & ~(TMPT_FLAG_OUT_DEVICE | TMPT_FLAG_WAIT_STREAM)) return no("unknown flag");
+    if (int rc = temporal_defaults(fn, kClipNMax, &r.n_max, &r.sigma_depth)) return rc;
+    if (!(r.gamma >= 0.0f) || !(r.gamma <= 3.0e38f)) return no(fn, "gamma must be finite and not negative (0 = default)");
+    if (r.radius < 1 || r.radius > 3) return no(fn, "radius must be 1, 2 or 3 (0 = default)");
+    if (int rc = check_frame_flags(fn, d->flags)) return rc;
     const bool dev = (d->flags & TMPT_FLAG_OUT_DEVICE) != 0;
-    auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-    if (dev && (((at(rgba32f_cur) | at(rgba32f_stat) | at(motion) | at(prev_motion) | at(rgba32f_history) | at(aux_cur) |
-                  at(aux_history) | at(aux_out) | at(rgba32f_out)) & 15u) != 0 || (at(rgba8_out) & 3u) != 0))
-        return no("device pointers must be 16-byte aligned (rgba8_out: 4)");
-    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4);
-    {
-        const struct { const void* p; const char* name; } outs[] = {{rgba32f_out, "rgba32f_out"}, {aux_out, "aux_out"}},
-            ins[] = {{rgba32f_history, "rgba32f_history"}, {aux_history, "aux_history"}, {rgba32f_cur, "rgba32f_cur"},
-                     {rgba32f_stat, "rgba32f_stat"}};
-        for (const auto& o : outs)
-            for (const auto& i : ins)
-                if (o.p && i.p && at(o.p) < at(i.p) + fb && at(i.p) < at(o.p) + fb)
-                    return no((std::string(o.name) + " overlaps " + i.name + " (its neighbours are read)").c_str());
-    }
-    if (!h) return no("null scene");
-    (void)hipGetLastError();  // clear a stale error of an earlier failed call (launch checks read it)
+    if (dev && !aligned({rgba32f_cur, rgba32f_stat, motion, prev_motion, rgba32f_history, aux_cur, aux_history, aux_out,
+                         rgba32f_out},
+                        {rgba8_out}))
+        return no(fn, "device pointers must be 16-byte aligned (rgba8_out: 4)");
+    const size_t n = (size_t)r.width * (size_t)r.height, fb = n * sizeof(float4), mb = n * sizeof(tmpt_motion_pixel);
+    if (int rc = check_overlap(fn, fb, {{rgba32f_out, "rgba32f_out"}, {aux_out, "aux_out"}},
+                               {{rgba32f_history, "rgba32f_history"}, {aux_history, "aux_history"},
+                                {rgba32f_cur, "rgba32f_cur"}, {rgba32f_stat, "rgba32f_stat"}}))
+        return rc;
+    if (!h) return no(fn, "null scene");
     Scene& s = h->s;
-    TMPT_HIP(hipSetDevice(s.device));
-    const float4* d_cur = reinterpret_cast<const float4*>(rgba32f_cur);
-    const float4* d_stat = reinterpret_cast<const float4*>(rgba32f_stat);
-    const float4* d_hist = reinterpret_cast<const float4*>(rgba32f_history);
-    const float4* d_ac = reinterpret_cast<const float4*>(aux_cur);
-    const float4* d_ah = reinterpret_cast<const float4*>(aux_history);
-    const tmpt_motion_pixel *d_m = motion, *d_pm = prev_motion;
-    float4* d_ao = reinterpret_cast<float4*>(aux_out);
-    float4* d_o32 = reinterpret_cast<float4*>(rgba32f_out);
-    uint32_t* d_o8 = reinterpret_cast<uint32_t*>(rgba8_out);
-    if (!dev) {  // host pointers: staged in the scene's kept buffer, frame after frame
-        const size_t mb = n * sizeof(tmpt_motion_pixel);
-        const size_t total = fb * (3 + (rgba32f_stat ? 1 : 0) + (aux ? 3 : 0)) + 2 * mb + n * 4;
-        TMPT_HIP(hipStreamSynchronize(s.stream));
-        if (!s.clip_stage.reserve(total)) return no("out of device memory");
-        char* at_dev = s.clip_stage.as<char>();
-        auto take = [&](size_t bytes) { char* p = at_dev; at_dev += bytes; return p; };
-        auto up = [&](const void* src, size_t bytes) -> char* {
-            char* p = take(bytes);
-            return hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? p : nullptr;
-        };
-        d_cur = reinterpret_cast<const float4*>(up(rgba32f_cur, fb));
-        d_hist = reinterpret_cast<const float4*>(up(rgba32f_history, fb));
-        d_m = reinterpret_cast<const tmpt_motion_pixel*>(up(motion, mb));
-        d_pm = reinterpret_cast<const tmpt_motion_pixel*>(up(prev_motion, mb));
-        bool ok = d_cur && d_hist && d_m && d_pm;
-        if (rgba32f_stat) ok = (d_stat = reinterpret_cast<const float4*>(up(rgba32f_stat, fb))) && ok;
-        if (aux) {
-            ok = (d_ac = reinterpret_cast<const float4*>(up(aux_cur, fb))) && ok;
-            ok = (d_ah = reinterpret_cast<const float4*>(up(aux_history, fb))) && ok;
-            d_ao = reinterpret_cast<float4*>(take(fb));
-        }
-        if (!ok) return (set_error(std::string(fn) + "upload failed"), -1);
-        d_o32 = rgba32f_out ? reinterpret_cast<float4*>(take(fb)) : nullptr;
-        d_o8 = rgba8_out ? reinterpret_cast<uint32_t*>(take(n * 4)) : nullptr;
-    }
-    if (!d_stat) d_stat = d_cur;
-    int rc = temporal_clip(s, &r, d_cur, d_stat, d_m, d_pm, d_hist, d_ac, d_ah, d_ao, d_o32, d_o8);
-    if (!rc && !dev) {
-        if ((rgba32f_out && hipMemcpy(rgba32f_out, d_o32, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (aux && hipMemcpy(aux_out, d_ao, fb, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (rgba8_out && hipMemcpy(rgba8_out, d_o8, n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = (set_error(std::string(fn) + "readback failed"), -1);
-    }
-    return rc;
+    if (int rc = enter(s)) return rc;
+    Staging st(dev);  // host form: in the scene's kept buffer, frame after frame
+    if (!dev) TMPT_HIP(hipStreamSynchronize(s.stream));
+    if (!st.reserve({{rgba32f_cur, fb}, {rgba32f_history, fb}, {motion, mb}, {prev_motion, mb}, {rgba32f_stat, fb},
+                     {aux_cur, fb}, {aux_history, fb}, {aux_out, fb}, {rgba32f_out, fb}, {rgba8_out, n * 4}},
+                    s.clip_stage))
+        return no(fn, "out of device memory");
+    const float4* d_cur = st.in<float4>(rgba32f_cur, fb);
+    const float4* d_hist = st.in<float4>(rgba32f_history, fb);
+    const tmpt_motion_pixel* d_m = st.in<tmpt_motion_pixel>(motion, mb);
+    const tmpt_motion_pixel* d_pm = st.in<tmpt_motion_pixel>(prev_motion, mb);
+    const float4* d_stat = st.in<float4>(rgba32f_stat, fb);
+    const float4* d_ac = st.in<float4>(aux_cur, fb);
+    const float4* d_ah = st.in<float4>(aux_history, fb);
+    if (!st.uploaded()) return failed(fn, "upload failed");
+    float4* d_o32 = st.out<float4>(rgba32f_out, fb);
+    float4* d_ao = st.out<float4>(aux_out, fb);
+    uint32_t* d_o8 = st.out<uint32_t>(rgba8_out, n * 4);
+    const int rc = temporal_clip(s, &r, d_cur, d_stat ? d_stat : d_cur, d_m, d_pm, d_hist, d_ac, d_ah, d_ao, d_o32, d_o8);
+    return finish(rc, s, fn, st, false);
     TMPT_GUARD_END
 }
 
@@ -1570,7 +1554,7 @@ int tmpt_render_multi(const float* tris, int32_t n, const float* octree_box, con
     TMPT_GUARD_BEGIN
     if (!cam || !desc || !devices || ndevices < 1 || !rgba_full || (n > 0 && !tris))
         return bad("tmpt_render_multi: bad arguments");
-    if (desc->width < 1 || desc->width > 10000 || desc->height < 1 || desc->height > 10000)
+    if (bad_side(desc->width) || bad_side(desc->height))
         return bad("tmpt_render_multi: invalid width / height");
     const int nd = ndevices;
     const int W = desc->width, H = desc->height;
